@@ -1,6 +1,6 @@
 """Headline benchmark: HR tiles/sec of the tiled CFG-DDPM sampling path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 N > 1: one process per GPU over RCCL.  Under a launcher (torch.distributed.run sets WORLD_SIZE/RANK/LOCAL_RANK) this
 process is one rank; started bare with --gpus N > 1 it spawns the N ranks itself (child processes of
@@ -19,10 +19,17 @@ rank 0 and the HR outputs gathered to rank 0 over RCCL inside the timed region.
 ``--workload canvas --lr_size 2048`` is the secondary mode (BASELINE configs[3]): one 8192^2 image whose tiles are
 sharded over all ranks with a per-step tile all-gather (strong scaling).
 
-Prints ONE JSON line (rank 0).  `roofline` is the dominant kernel, conv3x3_bf16_kernel (89% of the FLOPs):
-algorithmic FLOPs / HIP-event time on the launch stream, collected in an extra profiled pass right
-after the timed region; `cpu_baseline` is the CPU oracle (oracle/srgd_oracle.py, a port of the
-reference's PyTorch path) timed on this box's host cores on a bounded sample.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline line
+(`value`, `ms_per_step`, ...).  ``--full`` adds what takes runs of its own: `roofline` is the dominant kernel,
+conv3x3_bf16_kernel (89% of the FLOPs): algorithmic FLOPs / HIP-event time on the launch stream, collected in an
+extra profiled pass right after the timed region (also `conv_all_tflops`, `kernel_time_share`, `hbm_kernels`);
+`cpu_baseline` is the CPU oracle (oracle/srgd_oracle.py, a port of the reference's PyTorch path) timed on this
+box's host cores on a bounded sample.  ``--no_profile`` / ``--no_cpu_baseline`` drop either part of a --full run.
+
+``--dump-outputs DIR`` (rank 0): after the timed steps, the float32 output of the last timed step - the last HR tile
+(``[1,3,H,W]`` in [0,1], as tiled_sample returns it) - goes to ``DIR/hr_tile.npy``; an output over 64 MB (the
+canvas workload at --lr_size 2048) is written as a fixed seeded sample of its elements, ``DIR/hr_tile_sample.npy``.
+Inputs (weights, LR images, device noise) are seeded, so equal arguments give equal inputs in every run.
 """
 from __future__ import annotations
 
@@ -73,8 +80,13 @@ def parse():
     ap.add_argument("--lr_size", type=int, default=256)
     ap.add_argument("--sub_batch", type=int, default=0, help="tiles per U-Net launch (0: all tiles of a lock-step group)")
     ap.add_argument("--dim", type=int, default=128)
-    ap.add_argument("--no_cpu_baseline", action="store_true")
-    ap.add_argument("--no_profile", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the profiled pass (roofline, kernel_time_share, hbm_kernels) and the CPU-oracle baseline; "
+                         "a plain run only times the steps")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output as DIR/<name>.npy (float32, at most 64 MB)")
+    ap.add_argument("--no_cpu_baseline", action="store_true", help="--full without the CPU-oracle baseline")
+    ap.add_argument("--no_profile", action="store_true", help="--full without the profiled pass")
     ap.add_argument("--cpu_tile_forwards", type=int, default=128,
                     help="U-Net tile-forwards of the timed CPU-oracle sample over all worker processes (SURVEY 8(d): >= 41 = two "
                          "DDPM steps of one HR tile)")
@@ -255,6 +267,24 @@ def cpu_baseline(sd, dim, n_tile_forwards, budget_s):
             "single_process_thread_sweep_tile_forwards_per_s": {str(k): round(v, 4) for k, v in sweep.items()}}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_ELEMENTS = 4 << 20
+
+
+def dump_outputs(out_dir, hr_tile):
+    """--dump-outputs: the last timed step's HR tile as float32 .npy; above 64 MB a fixed seeded sample of its elements
+    (the same flat indices in every run of the same geometry)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    x = hr_tile.detach().float().cpu().contiguous()
+    if x.numel() * 4 <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "hr_tile.npy"), x.numpy())
+        return
+    g = torch.Generator().manual_seed(0)
+    idx = torch.randint(0, x.numel(), (DUMP_SAMPLE_ELEMENTS,), generator=g).sort().values
+    np.save(os.path.join(out_dir, "hr_tile_sample.npy"), x.view(-1)[idx].numpy())
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--cpu_worker":
         return cpu_worker(sys.argv[2:])
@@ -362,6 +392,8 @@ def main():
     if dist and not canvas_mode and rank == 0:
         assert gathered is not None and len(gathered) == args.steps * world and all(g is not None for g in gathered)
     assert all(torch.isfinite(o).all() for o in outs)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outs[-1][-1:])
 
     if rank == 0 and canvas_mode:
         from srgd_amd.model import get_coord_and_pad, get_coords
@@ -426,7 +458,7 @@ def main():
             line["config"]["tile_forwards_per_step"] = None
             line["config"]["unet_passes_per_ddpm_step"] = passes
             line.pop("tflops_effective", None)
-        if not args.no_profile:
+        if args.full and not args.no_profile:
             eng = sampler.model.engine(args.precision)
             # the per-kernel events of the profiled pass time one kernel at a time: one lane (with two concurrent lanes -
             # srgd_amd.lanes, small steps only - a kernel's bracket would include the other lane's work)
@@ -482,7 +514,7 @@ def main():
                               "launches": prof["launches"][k], "avg_launch_us": round(1e3 * prof["ms"][k] / prof["launches"][k], 2),
                               "algorithmic_mb_per_launch": round(prof["bytes"][k] / prof["launches"][k] / 1e6, 2)}
             line["hbm_kernels"] = hbm
-        if not args.no_cpu_baseline and world == 1:          # reported once, at N = 1 (the other ranks would idle behind it)
+        if args.full and not args.no_cpu_baseline and world == 1:   # reported once, at N = 1 (the other ranks would idle behind it)
             line["cpu_baseline"] = cpu_baseline(sd, args.dim, args.cpu_tile_forwards, args.cpu_budget_s)
         print(json.dumps(line), flush=True)
     if dist:

@@ -26,6 +26,26 @@ from srgd_amd.synth import synth_state_dict     # noqa: E402
 from tests.golden import cases as C             # noqa: E402
 
 
+def make_schedule(rm=None):
+    """G2: the reference's log-SNR schedule as fp32 bit patterns.  torch.log runs on MKL's vector math, whose rounding
+    depends on the code path MKL picks for the host CPU (its AVX-512 path on Intel hosts, AVX2 / SSE paths elsewhere).
+    ``log_snr_<n>``: as this host computes it; ``log_snr_<n>_mkl_compatible``: under ``MKL_CBWR=COMPATIBLE``, the
+    same bits on every x86 CPU (``MKL_CBWR=COMPATIBLE python tests/golden/make_golden.py --schedule-only``).
+    Keys of the other kind are kept."""
+    if rm is None:
+        ref = refshim.load_reference()
+        assert ref is not None, "reference not present"
+        rm = ref[0]
+    path = os.path.join(HERE, "schedule.npz")
+    sched = dict(np.load(path)) if os.path.exists(path) else {}
+    suffix = "_mkl_compatible" if os.environ.get("MKL_CBWR") == "COMPATIBLE" else ""
+    for n in C.SCHEDULE_STEPS:
+        steps = torch.linspace(1.0, 0.0, n + 1)
+        ls = torch.stack([rm.beta_linear_log_snr(steps[i]) for i in range(n + 1)])
+        sched[f"log_snr_{n}{suffix}"] = ls.numpy()
+    np.savez(path, **sched)
+
+
 def main(only=None):
     ref = refshim.load_reference()
     assert ref is not None, "reference not present"
@@ -52,12 +72,7 @@ def main(only=None):
         json.dump(geo, f, indent=1)
 
     # ---- G2 schedule scalars (fp32, bit patterns) -------------------------------------------
-    sched = {}
-    for n in C.SCHEDULE_STEPS:
-        steps = torch.linspace(1.0, 0.0, n + 1)
-        ls = torch.stack([rm.beta_linear_log_snr(steps[i]) for i in range(n + 1)])
-        sched[f"log_snr_{n}"] = ls.numpy()
-    np.savez(os.path.join(HERE, "schedule.npz"), **sched)
+    make_schedule(rm)
 
     # ---- schemas ---------------------------------------------------------------------------
     for dim in (16, 128):
@@ -303,6 +318,8 @@ if __name__ == "__main__":
         main(only={"dim16_300x300_lrcfg"})
     elif "--edm-only" in sys.argv:
         make_edm()
+    elif "--schedule-only" in sys.argv:
+        make_schedule()
     elif "--edm-untiled-only" in sys.argv:
         make_edm_untiled()
     else:

@@ -2,6 +2,8 @@
 (tests/golden/*.npz|json, produced by tests/golden/make_golden.py running /root/reference)."""
 import json
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -12,6 +14,7 @@ from srgd_amd.synth import synth_state_dict
 from tests.golden import cases as C
 
 G = os.path.join(os.path.dirname(__file__), "golden")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _schema(dim):
@@ -50,12 +53,29 @@ def test_geometry_known_answers_survey_appendix_d():
     assert (len(e), len(o)) == (1089, 1024)
 
 
+_SCHEDULE_BITS = """
+import json, sys, numpy as np, torch
+from oracle import srgd_oracle as O
+out = {}
+for n in json.loads(sys.argv[1]):
+    steps = torch.linspace(1.0, 0.0, n + 1)
+    out[n] = torch.stack([O.log_snr_linear(steps[i]) for i in range(n + 1)]).numpy().view(np.uint32).tolist()
+print(json.dumps(out))
+"""
+
+
 def test_schedule_bit_exact():
+    # torch.log runs on MKL's vector math, which rounds differently on its AVX-512 path (Intel hosts) and its AVX2 / SSE
+    # paths (other x86 hosts).  So the bits are compared with MKL pinned to its CPU-independent path, MKL_CBWR=COMPATIBLE,
+    # under which the reference's schedule was recorded too; MKL reads the setting at start-up, hence a child process.
     z = np.load(os.path.join(G, "schedule.npz"))
+    env = dict(os.environ, MKL_CBWR="COMPATIBLE")
+    r = subprocess.run([sys.executable, "-s", "-c", _SCHEDULE_BITS, json.dumps(C.SCHEDULE_STEPS)], cwd=ROOT, env=env,
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    got = json.loads(r.stdout.strip().splitlines()[-1])
     for n in C.SCHEDULE_STEPS:
-        steps = torch.linspace(1.0, 0.0, n + 1)
-        got = torch.stack([O.log_snr_linear(steps[i]) for i in range(n + 1)]).numpy()
-        assert np.array_equal(got.view(np.uint32), z[f"log_snr_{n}"].view(np.uint32))
+        assert np.array_equal(np.array(got[str(n)], dtype=np.uint32), z[f"log_snr_{n}_mkl_compatible"].view(np.uint32)), n
     # SURVEY section 8(a5): range -10.00005 (t=1) ... 9.21029 (t=0)
     assert abs(float(O.log_snr_linear(torch.tensor(1.0))) + 10.00005) < 1e-4
     assert abs(float(O.log_snr_linear(torch.tensor(0.0))) - 9.21029) < 1e-4

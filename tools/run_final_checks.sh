@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r6m; mkdir -p $O; cd $R
 cp gpurun_out/parity_report.jsonl $O/ 2>/dev/null
 tail -4 $O/pytest_gpu.log
 grep -q "rc=0" $O/pytest_gpu.log || exit 1
-timeout -k 10 600 python bench.py > $O/bench_default.json 2>$O/bench_default.err || exit 1
+timeout -k 10 600 python bench.py --full > $O/bench_default.json 2>$O/bench_default.err || exit 1
 python - $O/bench_default.json <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
