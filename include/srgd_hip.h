@@ -131,6 +131,33 @@ int srgd_sampler_begin(srgd_engine* e, const srgd_sampler_geometry* g, const flo
                        const int32_t* tiles_even_host, const int32_t* tiles_odd_host, int n_steps,
                        const srgd_step_scalars* scalars_host, const float* log_snr_host, int class_id, void* stream);
 
+/* One image of a mixed-size run (srgd_sampler_begin_images): the ints srgd_sampler_geometry holds for ONE image of the
+ * reference's tiled_sample (model.py:3296-3342), plus its noise class.  The reference reseeds before every image
+ * (inference.py:73) and its draw sequence depends on the canvas only, so images of one canvas size (Hp, Wp) see the same
+ * noise: they form one noise class.  Classes are numbered 0, 1, ... in order of first appearance. */
+typedef struct srgd_sampler_image {
+  int32_t H, W;                 /* image size */
+  int32_t Hp, Wp;               /* its canvas */
+  int32_t left, top;            /* crop box origin inside the canvas */
+  int32_t inner_l, inner_t, inner_r, inner_b; /* bounding box of its odd grid */
+  int32_t n_even, n_odd;        /* tiles of its two grids */
+  int32_t noise_class;          /* images with the same (Hp, Wp) share one class */
+} srgd_sampler_image;
+
+/* srgd_sampler_begin for images of DIFFERENT sizes sampled in lock-step (one U-Net launch spans tiles of all of them); each
+ * image comes out bit-identical to a run of its own.  All buffers are flat concatenations in image order:
+ *   cond01:  device fp32, image i's [3,H_i,W_i] after those of images 0..i-1;
+ *   cond_canvas (written) and every img / x_start canvas of the run: image i's [3,Hp_i,Wp_i] likewise;
+ *   tiles_even_host / tiles_odd_host: host, image i's [n_even_i][2] / [n_odd_i][2] (y, x) likewise.
+ * Afterwards srgd_sampler_step / _step_tiles (sub_batch and tile ranges count the tiles of all images, image-major),
+ * srgd_sampler_q_start and srgd_sampler_end work on these flat buffers; host noise is per class, concatenated in class order:
+ * noise_tiles = class k's [n_k,3,tile,tile] draw of the step's grid, noise_canvas (ring and q_start) = class k's [3,Hp_k,Wp_k]
+ * draw.  srgd_sampler_end writes image i's [3,H_i,W_i] at its offset in cond01's layout.  srgd_sampler_exchange_tiles and
+ * srgd_sampler_unpack_gathered (one canvas sharded over ranks) return an error after this begin. */
+int srgd_sampler_begin_images(srgd_engine* e, int tile, int n_images, const srgd_sampler_image* images, const float* cond01,
+                              float* cond_canvas, const int32_t* tiles_even_host, const int32_t* tiles_odd_host, int n_steps,
+                              const srgd_step_scalars* scalars_host, const float* log_snr_host, int class_id, void* stream);
+
 /* One denoising step over every tile of grid (step % 2), `sub_batch` tiles per U-Net launch
  * (the reference's --batch_size; results do not depend on it).
  *   passes = 1: eps = unet(label, cond).                       (model.py:3155-3156)

@@ -48,6 +48,13 @@ class SamplerGeometry(C.Structure):
                 ("tile", C.c_int32), ("n_even", C.c_int32), ("n_odd", C.c_int32), ("n_images", C.c_int32)]
 
 
+class SamplerImage(C.Structure):          # srgd_sampler_image: one image of a mixed-size lock-step run
+    _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("Hp", C.c_int32), ("Wp", C.c_int32),
+                ("left", C.c_int32), ("top", C.c_int32),
+                ("inner_l", C.c_int32), ("inner_t", C.c_int32), ("inner_r", C.c_int32), ("inner_b", C.c_int32),
+                ("n_even", C.c_int32), ("n_odd", C.c_int32), ("noise_class", C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/srgd_hip.h declares
 PROTOTYPES = {
     "srgd_last_error": (C.c_char_p, []),
@@ -64,6 +71,9 @@ PROTOTYPES = {
     "srgd_sampler_begin": (C.c_int, [C.c_void_p, C.POINTER(SamplerGeometry), C.c_void_p, C.c_void_p,
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.POINTER(StepScalars),
                                      C.POINTER(C.c_float), C.c_int, C.c_void_p]),
+    "srgd_sampler_begin_images": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(SamplerImage), C.c_void_p, C.c_void_p,
+                                            C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.POINTER(StepScalars),
+                                            C.POINTER(C.c_float), C.c_int, C.c_void_p]),
     "srgd_sampler_step": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_int, C.c_int, C.c_float, C.c_int, C.c_uint64, C.c_void_p]),
     "srgd_sampler_step_tiles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,

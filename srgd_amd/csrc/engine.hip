@@ -310,6 +310,17 @@ struct srgd_engine {
   float* rng_tiles = nullptr; size_t rng_tiles_cap = 0;
   EdmScalars* d_edm = nullptr; int edm_cap = 0; bool run_is_edm = false;
   float* rng_canvas = nullptr; size_t rng_canvas_cap = 0;
+  // per-image records of the run (kernels.hpp ImageDesc): a same-sized run holds n_images records of one geometry, a mixed run
+  // (srgd_sampler_begin_images) one record per image; every canvas kernel and the DDPM step address through them
+  std::vector<ImageDesc> images;
+  ImageDesc* d_images = nullptr; size_t images_cap = 0;
+  bool run_mixed = false;
+  int n_grid[2] = {0, 0};                 // tiles of the even / odd grid over all images
+  int max_local[2] = {0, 0};              // most tiles of one image per grid (device tile noise: one draw serves every image)
+  long max_canvas = 0, max_image = 0;     // largest 3*Hp*Wp / 3*H*W of one image
+  struct NoiseClass { int Hp, Wp; long long cnoise_off; };
+  std::vector<NoiseClass> classes;        // in order of first appearance; canvas noise of class k at cnoise_off
+  size_t class_canvas_elems = 0;          // sum of the classes' 3*Hp*Wp
 
   // device-side step counter + per-run hipGraph cache: a DDPM step is one graph per (grid parity, guidance mode);
   // step-dependent values (conditioning row, schedule scalars, RNG stream) are read through d_step, so one captured
@@ -1253,7 +1264,7 @@ int srgd_destroy(srgd_engine* e) {
   e->pool.release_all();
   for (void* p : {(void*)e->gn_partial, (void*)e->coefA, (void*)e->la_ws, (void*)e->d_rows,
                   (void*)e->d_tiles_even, (void*)e->d_tiles_odd, (void*)e->d_sc, (void*)e->d_edm, (void*)e->rng_tiles,
-                  (void*)e->rng_canvas})
+                  (void*)e->rng_canvas, (void*)e->d_images})
     if (p) hipFree(p);
   for (CondTable* ct : {&e->ct_sampler, &e->ct_api})
     for (float* q : {ct->table, ct->ls, ct->feat, ct->h1, ct->t1, ct->trows, ct->c1, ct->c2})
@@ -1457,49 +1468,121 @@ int srgd_unet_forward(srgd_engine* e, const float* xin, const float* cond, const
   return 0;
 }
 
-// shared by the DDPM and the EDM sampler: geometry checks, tile lists, condition canvas, conditioning table for the
-// n_times "time" inputs of the run (rows 2i: with the class embedding, 2i+1: without)
-static int sampler_begin_common(srgd_engine* e, const srgd_sampler_geometry* g, const float* cond01, float* cond_canvas,
-                                const int32_t* tiles_even_host, const int32_t* tiles_odd_host, int n_steps,
-                                const float* times_host, int n_times, int class_id, hipStream_t st) {
+// one image of a run as the begin entries receive it: its geometry, its two tile grids (host [n][2] = (y, x)) and its noise class
+struct ImageIn { srgd_sampler_image g; const int32_t* tiles_even; const int32_t* tiles_odd; };
+
+// shared by the DDPM and the EDM sampler: geometry checks, tile lists, image records, condition canvas, conditioning table for
+// the n_times "time" inputs of the run (rows 2i: with the class embedding, 2i+1: without)
+static int sampler_begin_common(srgd_engine* e, int tile, const std::vector<ImageIn>& ims, const float* cond01, float* cond_canvas,
+                                int n_steps, const float* times_host, int n_times, int class_id, hipStream_t st) {
   if (!e || !e->finalized) SRGD_FAIL("srgd_sampler_begin: engine has no weights");
-  if (!g || !cond01 || !cond_canvas || !tiles_even_host || !tiles_odd_host || !times_host)
-    SRGD_FAIL("srgd_sampler_begin: null argument");
+  if (!cond01 || !cond_canvas || !times_host) SRGD_FAIL("srgd_sampler_begin: null argument");
   if (class_id >= 0 && e->cfg.num_classes <= 0) SRGD_FAIL("class label given but the U-Net has no class embedding");
-  if (g->tile <= 0 || g->n_even <= 0 || g->n_odd <= 0 || n_steps <= 0 || g->n_images < 1)
-    SRGD_FAIL("srgd_sampler_begin: bad geometry");
-  // F.pad(mode='reflect') requires pad < input size (model.py:3303 raises otherwise)
-  const int pl = g->left, pr = g->Wp - g->left - g->W, pt = g->top, pb = g->Hp - g->top - g->H;
-  if (pl >= g->W || pr >= g->W || pt >= g->H || pb >= g->H)
-    SRGD_FAIL("Padding size should be less than the corresponding input dimension (reflect pad)");
+  if (tile <= 0 || n_steps <= 0 || ims.empty()) SRGD_FAIL("srgd_sampler_begin: bad geometry");
+  std::vector<ImageDesc> recs;
+  std::vector<srgd_engine::NoiseClass> classes;
+  std::vector<int> class_n[2];
+  std::vector<int32_t> tl[2];                // device tile lists are image-major [(y, x, image)]: one U-Net batch may span images
+  long long canvas_off = 0, cond_off = 0, cnoise_off = 0;
+  int max_local[2] = {0, 0};
+  long max_canvas = 0, max_image = 0;
+  for (size_t im = 0; im < ims.size(); ++im) {
+    const srgd_sampler_image& g = ims[im].g;
+    if (g.H <= 0 || g.W <= 0 || g.Hp < tile || g.Wp < tile || g.n_even <= 0 || g.n_odd <= 0 || !ims[im].tiles_even || !ims[im].tiles_odd ||
+        g.left < 0 || g.top < 0 || g.left + g.W > g.Wp || g.top + g.H > g.Hp || g.inner_l < 0 || g.inner_t < 0 ||
+        g.inner_l > g.inner_r || g.inner_t > g.inner_b || g.inner_r > g.Wp || g.inner_b > g.Hp)
+      SRGD_FAIL("srgd_sampler_begin: bad geometry");
+    // F.pad(mode='reflect') requires pad < input size (model.py:3303 raises otherwise)
+    const int pl = g.left, pr = g.Wp - g.left - g.W, pt = g.top, pb = g.Hp - g.top - g.H;
+    if (pl >= g.W || pr >= g.W || pt >= g.H || pb >= g.H)
+      SRGD_FAIL("Padding size should be less than the corresponding input dimension (reflect pad)");
+    // noise classes are numbered in order of first appearance; one class = one canvas size = one draw sequence
+    const int k = g.noise_class;
+    if (k < 0 || k > (int)classes.size()) SRGD_FAIL("srgd_sampler_begin_images: noise classes must be numbered 0, 1, ... in order of first appearance");
+    if (k == (int)classes.size()) {
+      classes.push_back({g.Hp, g.Wp, cnoise_off});
+      class_n[0].push_back(g.n_even);
+      class_n[1].push_back(g.n_odd);
+      cnoise_off += 3LL * g.Hp * g.Wp;
+    } else if (classes[k].Hp != g.Hp || classes[k].Wp != g.Wp || class_n[0][k] != g.n_even || class_n[1][k] != g.n_odd) {
+      SRGD_FAIL("srgd_sampler_begin_images: images of one noise class must share their canvas and tile grids");
+    }
+    ImageDesc d{};
+    d.canvas_off = canvas_off; d.cond_off = cond_off; d.cnoise_off = classes[k].cnoise_off;
+    d.Hp = g.Hp; d.Wp = g.Wp; d.left = g.left; d.top = g.top; d.H = g.H; d.W = g.W;
+    d.inner_l = g.inner_l; d.inner_t = g.inner_t; d.inner_r = g.inner_r; d.inner_b = g.inner_b;
+    d.noise_class = k;
+    for (int par = 0; par < 2; ++par) {
+      const int nl = par ? g.n_odd : g.n_even;
+      const int32_t* src = par ? ims[im].tiles_odd : ims[im].tiles_even;
+      d.tile0[par] = (int)(tl[par].size() / 3);
+      d.tnoise0[par] = 0;
+      for (int j = 0; j < k; ++j) d.tnoise0[par] += class_n[par][j];
+      for (int t = 0; t < nl; ++t) {
+        const int y = src[2 * t], x = src[2 * t + 1];
+        if (y < 0 || x < 0 || y + tile > g.Hp || x + tile > g.Wp)
+          SRGD_FAIL(par ? "srgd_sampler_begin: odd-grid tile outside the canvas" : "srgd_sampler_begin: even-grid tile outside the canvas");
+        tl[par].insert(tl[par].end(), {y, x, (int32_t)im});
+      }
+      max_local[par] = std::max(max_local[par], nl);
+    }
+    recs.push_back(d);
+    canvas_off += 3LL * g.Hp * g.Wp;
+    cond_off += 3LL * g.H * g.W;
+    max_canvas = std::max(max_canvas, 3L * g.Hp * g.Wp);
+    max_image = std::max(max_image, 3L * g.H * g.W);
+  }
   SRGD_HIP(hipSetDevice(e->cfg.device));
   drop_step_graphs(e);                       // graphs bake in canvas / table / tile-list pointers of one run
-  e->geo = *g;
   e->n_steps = n_steps;
   e->run_class = class_id;
-  // device tile lists are image-major [(y, x, image)]: one U-Net batch may span several images
-  std::vector<int32_t> tl_even, tl_odd;
-  for (int im = 0; im < g->n_images; ++im) {
-    for (int t = 0; t < g->n_even; ++t)
-      tl_even.insert(tl_even.end(), {tiles_even_host[2 * t], tiles_even_host[2 * t + 1], im});
-    for (int t = 0; t < g->n_odd; ++t) tl_odd.insert(tl_odd.end(), {tiles_odd_host[2 * t], tiles_odd_host[2 * t + 1], im});
+  e->images = recs;
+  e->classes = classes;
+  e->class_canvas_elems = (size_t)cnoise_off;
+  for (int par = 0; par < 2; ++par) {
+    e->n_grid[par] = (int)(tl[par].size() / 3);
+    e->max_local[par] = max_local[par];
   }
-  for (size_t t = 0; t < tl_even.size(); t += 3)
-    if (tl_even[t] < 0 || tl_even[t + 1] < 0 || tl_even[t] + g->tile > g->Hp || tl_even[t + 1] + g->tile > g->Wp)
-      SRGD_FAIL("srgd_sampler_begin: even-grid tile outside the canvas");
-  for (size_t t = 0; t < tl_odd.size(); t += 3)
-    if (tl_odd[t] < 0 || tl_odd[t + 1] < 0 || tl_odd[t] + g->tile > g->Hp || tl_odd[t + 1] + g->tile > g->Wp)
-      SRGD_FAIL("srgd_sampler_begin: odd-grid tile outside the canvas");
-  SRGD_TRY(ensure(e, &e->d_tiles_even, &e->tiles_cap_even, tl_even.size()));
-  SRGD_TRY(ensure(e, &e->d_tiles_odd, &e->tiles_cap_odd, tl_odd.size()));
-  SRGD_HIP(hipMemcpyAsync(e->d_tiles_even, tl_even.data(), tl_even.size() * 4, hipMemcpyHostToDevice, st));
-  SRGD_HIP(hipMemcpyAsync(e->d_tiles_odd, tl_odd.data(), tl_odd.size() * 4, hipMemcpyHostToDevice, st));
+  e->max_canvas = max_canvas;
+  e->max_image = max_image;
+  SRGD_TRY(ensure(e, &e->d_tiles_even, &e->tiles_cap_even, tl[0].size()));
+  SRGD_TRY(ensure(e, &e->d_tiles_odd, &e->tiles_cap_odd, tl[1].size()));
+  SRGD_TRY(ensure(e, &e->d_images, &e->images_cap, recs.size()));
+  SRGD_HIP(hipMemcpyAsync(e->d_tiles_even, tl[0].data(), tl[0].size() * 4, hipMemcpyHostToDevice, st));
+  SRGD_HIP(hipMemcpyAsync(e->d_tiles_odd, tl[1].data(), tl[1].size() * 4, hipMemcpyHostToDevice, st));
+  SRGD_HIP(hipMemcpyAsync(e->d_images, recs.data(), recs.size() * sizeof(ImageDesc), hipMemcpyHostToDevice, st));
   { Prof p(e, KC_CANVAS, st);
-    SRGD_TRY(canvas_prepare_cond(cond01, 3 * g->n_images, g->H, g->W, g->left, g->top, g->Hp, g->Wp, g->inner_l, g->inner_t, g->inner_r,
-                                 g->inner_b, cond_canvas, st)); }
+    SRGD_TRY(canvas_prepare_cond(cond01, e->d_images, (int)recs.size(), max_canvas, cond_canvas, st)); }
   SRGD_TRY(compute_conditioning(e, e->ct_sampler, times_host, n_times, class_id, st));
   // the host arrays (ours and the caller's) may be reused right after this returns
   SRGD_HIP(hipStreamSynchronize(st));
+  return 0;
+}
+
+// a same-sized run: n_images records of one geometry, one noise class
+static int sampler_begin_uniform(srgd_engine* e, const srgd_sampler_geometry* g, const float* cond01, float* cond_canvas,
+                                 const int32_t* tiles_even_host, const int32_t* tiles_odd_host, int n_steps,
+                                 const float* times_host, int n_times, int class_id, hipStream_t st) {
+  if (!g || !tiles_even_host || !tiles_odd_host) SRGD_FAIL("srgd_sampler_begin: null argument");
+  if (g->n_images < 1) SRGD_FAIL("srgd_sampler_begin: bad geometry");
+  const srgd_sampler_image one{g->H, g->W, g->Hp, g->Wp, g->left, g->top, g->inner_l, g->inner_t, g->inner_r, g->inner_b,
+                               g->n_even, g->n_odd, 0};
+  const std::vector<ImageIn> ims(g->n_images, ImageIn{one, tiles_even_host, tiles_odd_host});
+  SRGD_TRY(sampler_begin_common(e, g->tile, ims, cond01, cond_canvas, n_steps, times_host, n_times, class_id, st));
+  e->geo = *g;
+  e->run_mixed = false;
+  return 0;
+}
+
+static int upload_step_scalars(srgd_engine* e, int n_steps, const srgd_step_scalars* scalars_host, hipStream_t st) {
+  SRGD_HIP(hipSetDevice(e->cfg.device));
+  if (e->sc_cap < n_steps) {
+    if (e->d_sc) hipFree(e->d_sc);
+    e->d_sc = nullptr;
+    SRGD_HIP(hipMalloc((void**)&e->d_sc, (size_t)n_steps * sizeof(StepScalars)));
+    e->sc_cap = n_steps;
+  }
+  SRGD_HIP(hipMemcpyAsync(e->d_sc, scalars_host, (size_t)n_steps * sizeof(StepScalars), hipMemcpyHostToDevice, st));
   return 0;
 }
 
@@ -1508,19 +1591,35 @@ int srgd_sampler_begin(srgd_engine* e, const srgd_sampler_geometry* g, const flo
                        const srgd_step_scalars* scalars_host, const float* log_snr_host, int class_id, void* stream) {
   if (!scalars_host) SRGD_FAIL("srgd_sampler_begin: null argument");
   hipStream_t st = (hipStream_t)stream;
-  if (e && n_steps > 0) {
-    SRGD_HIP(hipSetDevice(e->cfg.device));
-    if (e->sc_cap < n_steps) {
-      if (e->d_sc) hipFree(e->d_sc);
-      e->d_sc = nullptr;
-      SRGD_HIP(hipMalloc((void**)&e->d_sc, (size_t)n_steps * sizeof(StepScalars)));
-      e->sc_cap = n_steps;
-    }
-    static_assert(sizeof(StepScalars) == sizeof(srgd_step_scalars), "step scalar layout");
-    SRGD_HIP(hipMemcpyAsync(e->d_sc, scalars_host, (size_t)n_steps * sizeof(StepScalars), hipMemcpyHostToDevice, st));
+  static_assert(sizeof(StepScalars) == sizeof(srgd_step_scalars), "step scalar layout");
+  if (e && n_steps > 0) SRGD_TRY(upload_step_scalars(e, n_steps, scalars_host, st));
+  SRGD_TRY(sampler_begin_uniform(e, g, cond01, cond_canvas, tiles_even_host, tiles_odd_host, n_steps, log_snr_host, n_steps,
+                                 class_id, st));
+  e->run_active = true;
+  e->run_is_edm = false;
+  return 0;
+}
+
+int srgd_sampler_begin_images(srgd_engine* e, int tile, int n_images, const srgd_sampler_image* images, const float* cond01,
+                              float* cond_canvas, const int32_t* tiles_even_host, const int32_t* tiles_odd_host, int n_steps,
+                              const srgd_step_scalars* scalars_host, const float* log_snr_host, int class_id, void* stream) {
+  if (!images || !scalars_host || !tiles_even_host || !tiles_odd_host) SRGD_FAIL("srgd_sampler_begin_images: null argument");
+  if (n_images < 1) SRGD_FAIL("srgd_sampler_begin_images: n_images must be >= 1");
+  hipStream_t st = (hipStream_t)stream;
+  std::vector<ImageIn> ims;
+  size_t oe = 0, oo = 0;
+  for (int i = 0; i < n_images; ++i) {
+    if (images[i].n_even <= 0 || images[i].n_odd <= 0) SRGD_FAIL("srgd_sampler_begin: bad geometry");
+    ims.push_back(ImageIn{images[i], tiles_even_host + 2 * oe, tiles_odd_host + 2 * oo});
+    oe += images[i].n_even;
+    oo += images[i].n_odd;
   }
-  SRGD_TRY(sampler_begin_common(e, g, cond01, cond_canvas, tiles_even_host, tiles_odd_host, n_steps, log_snr_host, n_steps,
-                                class_id, st));
+  if (e && n_steps > 0) SRGD_TRY(upload_step_scalars(e, n_steps, scalars_host, st));
+  SRGD_TRY(sampler_begin_common(e, tile, ims, cond01, cond_canvas, n_steps, log_snr_host, n_steps, class_id, st));
+  e->geo = srgd_sampler_geometry{};
+  e->geo.tile = tile;
+  e->geo.n_images = n_images;
+  e->run_mixed = true;
   e->run_active = true;
   e->run_is_edm = false;
   return 0;
@@ -1543,8 +1642,8 @@ int srgd_edm_begin(srgd_engine* e, const srgd_sampler_geometry* g, const float* 
     SRGD_HIP(hipMemcpyAsync(e->d_edm, scalars_host, (size_t)n_steps * sizeof(EdmScalars), hipMemcpyHostToDevice, st));
   }
   // two network evaluations per step: rows 4i..4i+1 for c_noise(sigma_hat_i), 4i+2..4i+3 for c_noise(sigma_next_i)
-  SRGD_TRY(sampler_begin_common(e, g, cond01, cond_canvas, tiles_even_host, tiles_odd_host, n_steps, c_noise_host,
-                                2 * n_steps, class_id, st));
+  SRGD_TRY(sampler_begin_uniform(e, g, cond01, cond_canvas, tiles_even_host, tiles_odd_host, n_steps, c_noise_host,
+                                 2 * n_steps, class_id, st));
   e->run_active = true;
   e->run_is_edm = true;
   return 0;
@@ -1571,7 +1670,7 @@ static int edm_step_launch(srgd_engine* e, bool last, int parity, int tile_first
   for (int first = tile_first; first < n; first += sub_batch) {
     const int nt = std::min(sub_batch, n - first);
     const int nb = nt * passes;
-    TileBatch tb{tiles, first, nt, g.Hp, g.Wp, g.tile, n_local};
+    TileBatch tb{tiles, first, nt, g.Hp, g.Wp, g.tile, n_local, e->d_images, parity};
     for (int ep = 0; ep < (last ? 1 : 2); ++ep) {
       void* x0 = e->pool.get((size_t)nb * g.tile * g.tile * e->dim * e->es);
       if (!x0) return -1;
@@ -1611,8 +1710,8 @@ static int edm_step_launch(srgd_engine* e, bool last, int parity, int tile_first
       SRGD_TRY(philox_normal(e->rng_canvas, canvas1, seed, (1ull << 32) | 0x80000000ull, e->d_step, st));
       nc = e->rng_canvas;
     }
-    SRGD_TRY(canvas_ring_renoise(img, 3 * g.n_images, nc, g.Hp, g.Wp, g.inner_l, g.inner_t, g.inner_r, g.inner_b,
-                                 &e->d_edm[0].ring_sigma, (int)(sizeof(EdmScalars) / sizeof(float)), e->d_step, st));
+    SRGD_TRY(canvas_ring_renoise(img, e->d_images, g.n_images, e->max_canvas, nc, &e->d_edm[0].ring_sigma,
+                                 (int)(sizeof(EdmScalars) / sizeof(float)), e->d_step, st));
   }
   return 0;
 }
@@ -1702,7 +1801,7 @@ int srgd_edm_dpmpp_step(srgd_engine* e, int step, float* img, const float* cond_
   for (int first = 0; first < n; first += sub_batch) {
     const int nt = std::min(sub_batch, n - first);
     const int nb = nt * passes;
-    TileBatch tb{tiles, first, nt, g.Hp, g.Wp, g.tile, n_local};
+    TileBatch tb{tiles, first, nt, g.Hp, g.Wp, g.tile, n_local, e->d_images, parity};
     void* x0 = e->pool.get((size_t)nb * g.tile * g.tile * e->dim * e->es);
     if (!x0) return -1;
     {
@@ -1743,15 +1842,15 @@ static int sampler_step_launch(srgd_engine* e, bool last, int parity, int tile_f
                                int sub_batch, uint64_t seed, hipStream_t st) {
   const srgd_sampler_geometry& g = e->geo;
   const int* tiles = parity ? e->d_tiles_odd : e->d_tiles_even;
-  const int n_local = parity ? g.n_odd : g.n_even;
   const int n = tile_first + tile_count;               // this call covers tiles [tile_first, n) of the image-major list
   const size_t tile_elems = (size_t)3 * g.tile * g.tile;
   const float* nz = nullptr;
   if (!last) {
     nz = noise_tiles;
-    if (!nz) {   // one image's worth of tile noise, shared by every image and independent of sub_batch
+    if (!nz) {   // the largest image's worth of tile noise, shared by every image (counter-based: a prefix of it is what a
+                 // smaller image draws alone) and independent of sub_batch
       Prof p(e, KC_CANVAS, st);
-      SRGD_TRY(philox_normal(e->rng_tiles, (size_t)n_local * tile_elems, seed, 1ull << 32, e->d_step, st));
+      SRGD_TRY(philox_normal(e->rng_tiles, (size_t)e->max_local[parity] * tile_elems, seed, 1ull << 32, e->d_step, st));
       nz = e->rng_tiles;
     }
   }
@@ -1760,7 +1859,7 @@ static int sampler_step_launch(srgd_engine* e, bool last, int parity, int tile_f
   for (int first = tile_first; first < n; first += sub_batch) {
     const int nt = std::min(sub_batch, n - first);
     const int nb = nt * passes;
-    TileBatch tb{tiles, first, nt, g.Hp, g.Wp, g.tile, n_local};
+    TileBatch tb{tiles, first, nt, g.Hp, g.Wp, g.tile, 0, e->d_images, parity};
     void* x0 = e->pool.get((size_t)nb * g.tile * g.tile * e->dim * e->es);
     if (!x0) return -1;
     const int mask = (passes == 2 && guidance_kind == 2) ? 0x1 : 0x3;
@@ -1783,6 +1882,7 @@ static int sampler_step_launch(srgd_engine* e, bool last, int parity, int tile_f
     FinalStepArgs fa;
     fa.act = act; fa.C = e->dim; fa.passes = passes; fa.guidance = guidance_scale;
     fa.w = e->final_w; fa.bias = e->final_b; fa.img = img; fa.x_start = x_start; fa.noise = nz;
+    fa.noise_per_class = noise_tiles ? 1 : 0;
     fa.sc = e->d_sc; fa.step_ptr = e->d_step;
     fa.eps4 = x.eps4_done ? eps4 : nullptr;
     { Prof p(e, KC_FINAL, st);
@@ -1798,12 +1898,14 @@ static int sampler_step_launch(srgd_engine* e, bool last, int parity, int tile_f
   if (parity == 1 && ring) {
     Prof p(e, KC_CANVAS, st);
     const float* nc = noise_canvas;
-    if (!nc) {
-      SRGD_TRY(philox_normal(e->rng_canvas, (size_t)3 * g.Hp * g.Wp, seed, (1ull << 32) | 0x80000000ull, e->d_step, st));
+    if (!nc) {   // one draw per noise class (canvas size): what each of its images draws alone
+      for (const auto& k : e->classes)
+        SRGD_TRY(philox_normal(e->rng_canvas + k.cnoise_off, (size_t)3 * k.Hp * k.Wp, seed, (1ull << 32) | 0x80000000ull,
+                               e->d_step, st));
       nc = e->rng_canvas;
     }
-    SRGD_TRY(canvas_ring_renoise(img, 3 * g.n_images, nc, g.Hp, g.Wp, g.inner_l, g.inner_t, g.inner_r, g.inner_b,
-                                 &e->d_sc[0].sigma_next, (int)(sizeof(StepScalars) / sizeof(float)), e->d_step, st));
+    SRGD_TRY(canvas_ring_renoise(img, e->d_images, (int)e->images.size(), e->max_canvas, nc, &e->d_sc[0].sigma_next,
+                                 (int)(sizeof(StepScalars) / sizeof(float)), e->d_step, st));
   }
   return 0;
 }
@@ -1836,8 +1938,7 @@ int srgd_sampler_step_tiles(srgd_engine* e, int step, int tile_first, int tile_c
   SRGD_HIP(hipSetDevice(e->cfg.device));
   const srgd_sampler_geometry& g = e->geo;
   const int parity = step & 1;
-  const int n_local = parity ? g.n_odd : g.n_even;
-  const int n = n_local * g.n_images;
+  const int n = e->n_grid[parity];
   const bool last = step == e->n_steps - 1;
   if (tile_count < 0) tile_count = n - tile_first;
   if (tile_first < 0 || tile_count < 0 || tile_first + tile_count > n) SRGD_FAIL("srgd_sampler_step_tiles: tile range outside the grid");
@@ -1851,8 +1952,8 @@ int srgd_sampler_step_tiles(srgd_engine* e, int step, int tile_first, int tile_c
   e->pool.reset_busy();
   // every allocation happens here, before any capture
   SRGD_TRY(ensure_scratch(e, sub_batch * passes, g.tile, g.tile));
-  if (!noise_tiles) SRGD_TRY(ensure(e, &e->rng_tiles, &e->rng_tiles_cap, (size_t)n_local * 3 * g.tile * g.tile));
-  if (!noise_canvas && ring) SRGD_TRY(ensure(e, &e->rng_canvas, &e->rng_canvas_cap, (size_t)3 * g.Hp * g.Wp));
+  if (!noise_tiles) SRGD_TRY(ensure(e, &e->rng_tiles, &e->rng_tiles_cap, (size_t)e->max_local[parity] * 3 * g.tile * g.tile));
+  if (!noise_canvas && ring) SRGD_TRY(ensure(e, &e->rng_canvas, &e->rng_canvas_cap, e->class_canvas_elems));
   if (!e->d_step) SRGD_HIP(hipMalloc((void**)&e->d_step, sizeof(int)));
   hipLaunchKernelGGL(set_step_kernel, dim3(1), dim3(1), 0, st, e->d_step, step);
 
@@ -1872,6 +1973,7 @@ int srgd_sampler_exchange_tiles(srgd_engine* e, int parity, int tile_first, int 
                                 int to_canvas, void* stream) {
   if (!e || !e->run_active) SRGD_FAIL("srgd_sampler_exchange_tiles: call srgd_sampler_begin first");
   if (!canvas || !tiles) SRGD_FAIL("srgd_sampler_exchange_tiles: null argument");
+  if (e->run_mixed) SRGD_FAIL("srgd_sampler_exchange_tiles: not available after srgd_sampler_begin_images (one canvas per image size)");
   const srgd_sampler_geometry& g = e->geo;
   const int n = (parity & 1 ? g.n_odd : g.n_even) * g.n_images;
   if (tile_first < 0 || tile_count < 0 || tile_first + tile_count > n)
@@ -1887,6 +1989,7 @@ int srgd_sampler_unpack_gathered(srgd_engine* e, int parity, int world, int slic
                                  const float* gathered, void* stream) {
   if (!e || !e->run_active) SRGD_FAIL("srgd_sampler_unpack_gathered: call srgd_sampler_begin first");
   if (!canvas || !gathered) SRGD_FAIL("srgd_sampler_unpack_gathered: null argument");
+  if (e->run_mixed) SRGD_FAIL("srgd_sampler_unpack_gathered: not available after srgd_sampler_begin_images (one canvas per image size)");
   if (world < 1 || slice_w < 1 || part_w < 1 || part_off < 0 || part_off + part_w > slice_w)
     SRGD_FAIL("srgd_sampler_unpack_gathered: the part [part_off, part_off + part_w) must lie inside a slice of slice_w tiles");
   const srgd_sampler_geometry& g = e->geo;
@@ -1901,24 +2004,22 @@ int srgd_sampler_q_start(srgd_engine* e, const float* cond01, const float* noise
   if (!e || !e->run_active) SRGD_FAIL("srgd_sampler_q_start: call srgd_sampler_begin first");
   if (!cond01 || !img) SRGD_FAIL("srgd_sampler_q_start: null argument");
   hipStream_t st = (hipStream_t)stream;
-  const srgd_sampler_geometry& g = e->geo;
   Prof p(e, KC_CANVAS, st);
   const float* nz = noise_canvas;
-  if (!nz) {
-    const size_t cn = (size_t)3 * g.Hp * g.Wp;
-    SRGD_TRY(ensure(e, &e->rng_canvas, &e->rng_canvas_cap, cn));
-    SRGD_TRY(philox_normal(e->rng_canvas, cn, seed, 0, nullptr, st));
+  if (!nz) {   // one draw per noise class, as in the ring re-noise
+    SRGD_TRY(ensure(e, &e->rng_canvas, &e->rng_canvas_cap, e->class_canvas_elems));
+    for (const auto& k : e->classes)
+      SRGD_TRY(philox_normal(e->rng_canvas + k.cnoise_off, (size_t)3 * k.Hp * k.Wp, seed, 0, nullptr, st));
     nz = e->rng_canvas;
   }
-  return canvas_q_start(cond01, 3 * g.n_images, g.H, g.W, g.left, g.top, g.Hp, g.Wp, nz, alpha, sigma, img, st);
+  return canvas_q_start(cond01, e->d_images, (int)e->images.size(), e->max_canvas, nz, alpha, sigma, img, st);
 }
 
 int srgd_sampler_end(srgd_engine* e, const float* img, float* out01, void* stream) {
   if (!e || !e->run_active) SRGD_FAIL("srgd_sampler_end: no active run");
   hipStream_t st = (hipStream_t)stream;
-  const srgd_sampler_geometry& g = e->geo;
   Prof p(e, KC_CANVAS, st);
-  SRGD_TRY(canvas_finish(img, 3 * g.n_images, g.Hp, g.Wp, g.left, g.top, g.H, g.W, out01, st));
+  SRGD_TRY(canvas_finish(img, e->d_images, (int)e->images.size(), e->max_image, out01, st));
   e->run_active = false;
   return 0;
 }

@@ -210,13 +210,30 @@ struct EdmScalars {        // == srgd_edm_scalars (include/srgd_hip.h); fp32 val
   float clamp;                       // != 0: clamp the denoised prediction to [-1, 1]
   float dpm_gamma, pad1;             // srgd_edm_dpmpp_step: multistep weight (dt / half_dt hold its two update coefficients)
 };
+// One image of a run (device table, one record per image; same-sized runs hold n_images equal records but for the offsets).
+// Images of one noise class have the same canvas (Hp, Wp) and therefore the same reference draw sequence (model.py:3311,
+// :3186, :3394): they share their noise exactly as same-sized images in lock-step do.
+struct ImageDesc {
+  long long canvas_off;    // its [3][Hp][Wp] canvas inside the flat canvas buffers (img, cond canvas, x_start), elements
+  long long cond_off;      // its [3][H][W] image inside the flat cond01 / out01 buffers, elements
+  long long cnoise_off;    // its noise class's [3][Hp][Wp] draw inside the concatenated canvas noise (ring, q_start), elements
+  int Hp, Wp;              // canvas
+  int left, top, H, W;     // crop box inside the canvas (model.py:3301-3303)
+  int inner_l, inner_t, inner_r, inner_b;   // bounding box of the odd grid (model.py:3337-3342)
+  int tile0[2];            // global index of its first tile in the even / odd tile list (tiles are image-major)
+  int tnoise0[2];          // host noise: first tile of its class's draw in the concatenated tile noise of an even / odd step
+  int noise_class;
+  int pad;
+};
 struct TileBatch {
-  const int* tile_yx;      // device [n_images * n_local][3] = (y, x, image) of each tile, image-major
+  const int* tile_yx;      // device [n_tiles][3] = (y, x, image) of each tile, image-major
   int first;               // first tile of this sub-batch in tile_yx
   int ntiles;              // tiles in this sub-batch
-  int Hp, Wp;              // canvas size
+  int Hp, Wp;              // canvas size (EDM / canvas exchange: one size for all images)
   int tile;                // tile edge (256)
-  int n_local;             // tiles per image (noise is indexed by the tile's position inside its image)
+  int n_local;             // tiles per image (EDM / canvas exchange)
+  const ImageDesc* images = nullptr;   // device [n_images]: the DDPM step and the gather address every tile through its image
+  int parity = 0;          // grid of this batch (selects ImageDesc::tile0 / tnoise0)
 };
 // 7x7 input convolution (model.py:583) on MFMA: gather the 6 input planes of every tile into a zero-haloed NHWC image
 // [entries][H+6][W+8][8 ch] (ch 6,7 = 0; position px holds input column px-3), after which output pixel (y,x), tap row
@@ -246,6 +263,7 @@ struct FinalStepArgs {
   float* img;              // canvas, updated in place
   float* x_start;          // optional canvas
   const float* noise;
+  int noise_per_class = 0;       // 1: noise holds the per-class draws concatenated (ImageDesc::tnoise0); 0: one draw shared by all images
   const float* eps4 = nullptr;   // when set: the output convolution was already applied (ConvArgs::eps4); act / w / bias unused
   const StepScalars* sc;   // device pointer
   const int* step_ptr;     // optional device step counter indexing sc
@@ -258,17 +276,17 @@ int final_step(const FinalStepArgs& a, const TileBatch& tb, bool is_bf16, hipStr
 int final_step_edm(const FinalStepArgs& a, const EdmScalars* sc, float* work, size_t canvas_elems, int edm_pass,
                    const TileBatch& tb, bool is_bf16, hipStream_t st);
 
-// canvas kernels (model.py:3296-3303, :3337-3342, :3392-3396, :3403-3405)
-// `planes` = 3 * n_images; the noise canvas [3][Hp][Wp] is shared by every image (index taken modulo 3*Hp*Wp)
-int canvas_prepare_cond(const float* cond01 /*[planes][H][W]*/, int planes, int H, int W, int pad_l, int pad_t, int Hp,
-                        int Wp, int il, int it, int ir, int ib, float* cond_canvas, hipStream_t st);
-int canvas_q_start(const float* cond01, int planes, int H, int W, int pad_l, int pad_t, int Hp, int Wp,
-                   const float* noise, float alpha, float sigma, float* img, hipStream_t st);
+// canvas kernels (model.py:3296-3303, :3337-3342, :3392-3396, :3403-3405): ONE launch covers every image of the run (grid
+// row blockIdx.y = image, addressed through its ImageDesc); max_canvas / max_image = the largest 3*Hp*Wp / 3*H*W of the table
+int canvas_prepare_cond(const float* cond01, const ImageDesc* images, int n_images, long max_canvas, float* cond_canvas,
+                        hipStream_t st);
+// noise: the concatenated [3][Hp][Wp] draws of the noise classes (ImageDesc::cnoise_off)
+int canvas_q_start(const float* cond01, const ImageDesc* images, int n_images, long max_canvas, const float* noise, float alpha,
+                   float sigma, float* img, hipStream_t st);
 // sigma = sigma_base[*step_ptr * sigma_stride] (a float field of the per-step scalar records of either sampler)
-int canvas_ring_renoise(float* img, int planes, const float* noise /*[3][Hp][Wp]*/, int Hp, int Wp, int il, int it,
-                        int ir, int ib, const float* sigma_base, int sigma_stride, const int* step_ptr, hipStream_t st);
-int canvas_finish(const float* img, int planes, int Hp, int Wp, int left, int top, int H, int W, float* out01,
-                  hipStream_t st);
+int canvas_ring_renoise(float* img, const ImageDesc* images, int n_images, long max_canvas, const float* noise,
+                        const float* sigma_base, int sigma_stride, const int* step_ptr, hipStream_t st);
+int canvas_finish(const float* img, const ImageDesc* images, int n_images, long max_image, float* out01, hipStream_t st);
 // copies the tiles [tb.first, tb.first+tb.ntiles) between a canvas and a packed [ntiles][3][tile][tile] buffer
 // (the exchange unit when one canvas is sharded over ranks: SURVEY section 8(e), config 4)
 int canvas_unpack_gathered(float* canvas, const float* gathered, const TileBatch& tb, int w, int off, int pw, int n_grid, hipStream_t st);

@@ -14,11 +14,12 @@ struct InitSrc {
   const float* cond;       // condition planes (may be null)
   int canvas;              // 1: tiles of a canvas, 0: plain NCHW batch
   const int* tile_yx;
+  const ImageDesc* images; // canvas mode: each tile's canvas through its image's record
   int first, ntiles;       // canvas mode: entries = passes * ntiles
   int use_cond_mask;       // bit p: pass p sees the condition
   int H, W;                // tile / image size
-  int row_stride;          // canvas width or W
-  long plane_stride;       // canvas plane or H*W
+  int row_stride;          // plain mode: W
+  long plane_stride;       // plain mode: H*W
   // EDM (canvas mode only): x = (x + hat_coef * (s_noise * z)) * c_in, scalars read on the device
   const EdmScalars* edm;   // null: plain gather
   const int* step_ptr;
@@ -40,29 +41,34 @@ __global__ __launch_bounds__(256) void init_gather_kernel(InitSrc s, int entries
     float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (y >= 0 && y < s.H && x >= 0 && x < s.W) {
       long origin, zorigin = 0;
+      int row_stride = s.row_stride;
+      long plane_stride = s.plane_stride;
       bool use_cond = s.cond != nullptr;
       if (s.canvas) {
         const int pass = entry / s.ntiles, tt = entry - pass * s.ntiles;
         const int* tyx = s.tile_yx + 3 * (s.first + tt);
-        zorigin = (long)tyx[0] * s.row_stride + tyx[1];
-        origin = (long)tyx[2] * 3 * s.plane_stride + zorigin;
+        const ImageDesc* im = s.images + tyx[2];
+        row_stride = im->Wp;
+        plane_stride = (long)im->Hp * im->Wp;
+        zorigin = (long)tyx[0] * row_stride + tyx[1];
+        origin = im->canvas_off + zorigin;
         use_cond = use_cond && ((s.use_cond_mask >> pass) & 1);
       } else {
-        origin = (long)entry * 3 * s.plane_stride;
+        origin = (long)entry * 3 * plane_stride;
       }
-      const long o = origin + (long)y * s.row_stride + x;
+      const long o = origin + (long)y * row_stride + x;
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
-        v[c] = s.x[o + c * s.plane_stride];
-        if (use_cond) v[3 + c] = s.cond[o + c * s.plane_stride];
+        v[c] = s.x[o + c * plane_stride];
+        if (use_cond) v[3 + c] = s.cond[o + c * plane_stride];
       }
       if (s.edm) {
         const EdmScalars sc = s.edm[s.step_ptr ? *s.step_ptr : 0];
-        const long oz = zorigin + (long)y * s.row_stride + x;
+        const long oz = zorigin + (long)y * row_stride + x;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
           float xv = v[c];
-          if (s.z) xv = xv + sc.hat_coef * (sc.s_noise * s.z[oz + c * s.plane_stride]);   // pass 0 of the Heun step only
+          if (s.z) xv = xv + sc.hat_coef * (sc.s_noise * s.z[oz + c * plane_stride]);   // pass 0 of the Heun step only
           v[c] = (s.edm_pass == 1 ? sc.c_in_next : sc.c_in_hat) * xv;
         }
       }
@@ -186,9 +192,12 @@ __global__ __launch_bounds__(256) void final_step_kernel(FinalStepArgs a, TileBa
   const StepScalars sc = a.sc[a.step_ptr ? *a.step_ptr : 0];
   const int* tyx = tb.tile_yx + 3 * (tb.first + t);
   const int ty = tyx[0], tx = tyx[1];
-  const long plane = (long)tb.Hp * tb.Wp;
-  const long o = (long)tyx[2] * 3 * plane + (long)(ty + y) * tb.Wp + tx + x;
-  const int tl = (tb.first + t) % tb.n_local;       // tile index inside its image: selects the noise tile
+  const ImageDesc* im = tb.images + tyx[2];          // uniform per block: the block lies inside one tile
+  const int Wp = im->Wp;
+  const long plane = (long)im->Hp * Wp;
+  const long o = im->canvas_off + (long)(ty + y) * Wp + tx + x;
+  // tile index inside its image selects the noise tile; host noise of a mixed run: inside its class's draw
+  const int tl = tb.first + t - im->tile0[tb.parity] + (a.noise_per_class ? im->tnoise0[tb.parity] : 0);
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const float xt = a.img[c * plane + o];
@@ -289,72 +298,84 @@ __global__ __launch_bounds__(256) void final_step_edm_kernel(FinalStepArgs a, co
 }
 
 // ------------------------------------------------------------------ canvas kernels
-__global__ void canvas_prepare_cond_kernel(const float* __restrict__ c01, int planes, int H, int W, int pad_l, int pad_t,
-                                           int Hp, int Wp, int il, int it, int ir, int ib,
+// grid row blockIdx.y = image: the record is uniform per block; the x blocks stride over that image's canvas (or crop)
+
+__device__ __forceinline__ int reflect_index(int v, int n) {      // F.pad(mode='reflect'), pad < n
+  if (v < 0) v = -v;
+  if (v >= n) v = 2 * (n - 1) - v;
+  return v;
+}
+
+__global__ void canvas_prepare_cond_kernel(const float* __restrict__ c01, const ImageDesc* __restrict__ images,
                                            float* __restrict__ canvas) {
-  const long n = (long)planes * Hp * Wp;
+  const ImageDesc im = images[blockIdx.y];
+  const long plane = (long)im.Hp * im.Wp, n = 3 * plane;
+  const float* src = c01 + im.cond_off;
+  float* dst = canvas + im.canvas_off;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-    const int c = (int)(i / ((long)Hp * Wp));
-    const long rem = i - (long)c * Hp * Wp;
-    const int Y = (int)(rem / Wp), X = (int)(rem - (long)Y * Wp);
+    const int c = (int)(i / plane);
+    const long rem = i - (long)c * plane;
+    const int Y = (int)(rem / im.Wp), X = (int)(rem - (long)Y * im.Wp);
     float v = 0.f;
-    if (Y >= it && Y < ib && X >= il && X < ir) {
-      int y = Y - pad_t, x = X - pad_l;
-      if (y < 0) y = -y;
-      if (y >= H) y = 2 * (H - 1) - y;
-      if (x < 0) x = -x;
-      if (x >= W) x = 2 * (W - 1) - x;
-      v = c01[((long)c * H + y) * W + x] * 2.0f - 1.0f;
+    if (Y >= im.inner_t && Y < im.inner_b && X >= im.inner_l && X < im.inner_r) {
+      const int y = reflect_index(Y - im.top, im.H), x = reflect_index(X - im.left, im.W);
+      v = src[((long)c * im.H + y) * im.W + x] * 2.0f - 1.0f;
     }
-    canvas[i] = v;
+    dst[i] = v;
   }
 }
 
 // q_sample start of a run (model.py:3305-3308, :3312-3315): img = reflect_pad(2*cond-1) * alpha + noise * sigma over
-// the WHOLE canvas (the condition is not yet zeroed outside the inner box at that point of the reference).
-__global__ void canvas_q_start_kernel(const float* __restrict__ c01, int planes, int H, int W, int pad_l, int pad_t,
-                                      int Hp, int Wp, const float* __restrict__ noise, float alpha, float sigma,
-                                      float* __restrict__ img) {
-  const long n = (long)planes * Hp * Wp;
-  const long nmod = 3L * Hp * Wp;
+// the WHOLE canvas (the condition is not yet zeroed outside the inner box at that point of the reference).  Both products are
+// rounded before the sum, as the reference's two tensor ops do: a contracted form is not unique (the compiler may fuse either
+// product, differently in different copies of the loop body), and a result that depends on the launch shape would break
+// the bit-identity of an image in a group with its solo run.
+__global__ void canvas_q_start_kernel(const float* __restrict__ c01, const ImageDesc* __restrict__ images,
+                                      const float* __restrict__ noise, float alpha, float sigma, float* __restrict__ img) {
+#pragma clang fp contract(off)
+  const ImageDesc im = images[blockIdx.y];
+  const long plane = (long)im.Hp * im.Wp, n = 3 * plane;
+  const float* src = c01 + im.cond_off;
+  const float* nz = noise + im.cnoise_off;
+  float* dst = img + im.canvas_off;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-    const int c = (int)(i / ((long)Hp * Wp));
-    const long rem = i - (long)c * Hp * Wp;
-    const int Y = (int)(rem / Wp), X = (int)(rem - (long)Y * Wp);
-    int y = Y - pad_t, x = X - pad_l;
-    if (y < 0) y = -y;
-    if (y >= H) y = 2 * (H - 1) - y;
-    if (x < 0) x = -x;
-    if (x >= W) x = 2 * (W - 1) - x;
-    const float v = c01[((long)c * H + y) * W + x] * 2.0f - 1.0f;
-    img[i] = v * alpha + noise[i % nmod] * sigma;
+    const int c = (int)(i / plane);
+    const long rem = i - (long)c * plane;
+    const int Y = (int)(rem / im.Wp), X = (int)(rem - (long)Y * im.Wp);
+    const int y = reflect_index(Y - im.top, im.H), x = reflect_index(X - im.left, im.W);
+    const float v = src[((long)c * im.H + y) * im.W + x] * 2.0f - 1.0f;
+    dst[i] = v * alpha + nz[i] * sigma;
   }
 }
 
-__global__ void canvas_ring_renoise_kernel(float* __restrict__ img, int planes, const float* __restrict__ noise, int Hp,
-                                           int Wp, int il, int it, int ir, int ib,
-                                           const float* __restrict__ sigma_base, int sigma_stride,
-                                           const int* __restrict__ step_ptr) {
+__global__ void canvas_ring_renoise_kernel(float* __restrict__ img, const ImageDesc* __restrict__ images,
+                                           const float* __restrict__ noise, const float* __restrict__ sigma_base,
+                                           int sigma_stride, const int* __restrict__ step_ptr) {
   const float sigma = sigma_base[(long)(step_ptr ? *step_ptr : 0) * sigma_stride];
-  const long n = (long)planes * Hp * Wp;
-  const long nmod = 3L * Hp * Wp;
+  const ImageDesc im = images[blockIdx.y];
+  const long plane = (long)im.Hp * im.Wp, n = 3 * plane;
+  const float* nz = noise + im.cnoise_off;
+  float* dst = img + im.canvas_off;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-    const long rem = i % ((long)Hp * Wp);
-    const int Y = (int)(rem / Wp), X = (int)(rem - (long)Y * Wp);
-    if (!(Y >= it && Y < ib && X >= il && X < ir)) img[i] = noise[i % nmod] * sigma;
+    const long rem = i % plane;
+    const int Y = (int)(rem / im.Wp), X = (int)(rem - (long)Y * im.Wp);
+    if (!(Y >= im.inner_t && Y < im.inner_b && X >= im.inner_l && X < im.inner_r)) dst[i] = nz[i] * sigma;
   }
 }
 
-__global__ void canvas_finish_kernel(const float* __restrict__ img, int planes, int Hp, int Wp, int left, int top, int H,
-                                     int W, float* __restrict__ out) {
-  const long n = (long)planes * H * W;
+__global__ void canvas_finish_kernel(const float* __restrict__ img, const ImageDesc* __restrict__ images,
+                                     float* __restrict__ out) {
+  const ImageDesc im = images[blockIdx.y];
+  const long hw = (long)im.H * im.W, n = 3 * hw;
+  const float* src = img + im.canvas_off;
+  float* dst = out + im.cond_off;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-    const int c = (int)(i / ((long)H * W));
-    const long rem = i - (long)c * H * W;
-    const int y = (int)(rem / W), x = (int)(rem - (long)y * W);
-    float v = img[((long)c * Hp + top + y) * Wp + left + x];
+    const int c = (int)(i / hw);
+    const long rem = i - (long)c * hw;
+    const int y = (int)(rem / im.W), x = (int)(rem - (long)y * im.W);
+    float v = src[((long)c * im.Hp + im.top + y) * im.Wp + im.left + x];
     v = fminf(fmaxf(v, -1.0f), 1.0f);
-    out[i] = (v + 1.0f) * 0.5f;
+    dst[i] = (v + 1.0f) * 0.5f;
   }
 }
 
@@ -448,6 +469,10 @@ __global__ void philox_normal_kernel(float* __restrict__ dst, size_t n, uint64_t
 }
 
 int grid_for(long n) { return (int)std::min<long>((n + 255) / 256, 256L * 16); }
+// canvas kernels: one grid row per image, the same total block budget as grid_for
+dim3 grid_per_image(long max_elems, int n_images) {
+  return dim3((unsigned)std::max(1, std::min(grid_for(max_elems), 256 * 16 / std::max(1, n_images))), (unsigned)n_images);
+}
 
 }  // namespace
 
@@ -461,9 +486,9 @@ int init_gather_from_canvas_edm(const float* img, const float* z, const float* c
                                 bool is_bf16, hipStream_t st) {
   if (sc && edm_pass == 0 && !z) SRGD_FAIL("init_gather: EDM pass 0 needs the noise canvas");
   InitSrc s;
-  s.x = img; s.cond = cond; s.canvas = 1; s.tile_yx = tb.tile_yx; s.first = tb.first; s.ntiles = tb.ntiles;
-  s.use_cond_mask = use_cond_mask; s.H = tb.tile; s.W = tb.tile; s.row_stride = tb.Wp;
-  s.plane_stride = (long)tb.Hp * tb.Wp;
+  if (!tb.images) SRGD_FAIL("init_gather: tile batch without image records");
+  s.x = img; s.cond = cond; s.canvas = 1; s.tile_yx = tb.tile_yx; s.images = tb.images; s.first = tb.first; s.ntiles = tb.ntiles;
+  s.use_cond_mask = use_cond_mask; s.H = tb.tile; s.W = tb.tile; s.row_stride = 0; s.plane_stride = 0;
   s.edm = sc; s.step_ptr = step_ptr; s.z = z; s.edm_pass = edm_pass;
   const int entries = passes * tb.ntiles;
   const int grid = grid_for((long)entries * (s.H + 6) * (s.W + 8));
@@ -476,7 +501,7 @@ int init_gather_from_canvas_edm(const float* img, const float* z, const float* c
 int init_gather_from_nchw(const float* x, const float* cond, int B, int H, int W, void* padded, bool is_bf16,
                           hipStream_t st) {
   InitSrc s;
-  s.x = x; s.cond = cond; s.canvas = 0; s.tile_yx = nullptr; s.first = 0; s.ntiles = B; s.use_cond_mask = 1;
+  s.x = x; s.cond = cond; s.canvas = 0; s.tile_yx = nullptr; s.images = nullptr; s.first = 0; s.ntiles = B; s.use_cond_mask = 1;
   s.H = H; s.W = W; s.row_stride = W; s.plane_stride = (long)H * W;
   s.edm = nullptr; s.step_ptr = nullptr; s.z = nullptr; s.edm_pass = 0;
   const int grid = grid_for((long)B * (H + 6) * (W + 8));
@@ -506,6 +531,7 @@ int final_step(const FinalStepArgs& a, const TileBatch& tb, bool is_bf16, hipStr
   const int grid = (int)((n + 255) / 256);
   if (a.C % (is_bf16 ? 8 : 4) != 0) SRGD_FAIL("final_step: C must be a multiple of the vector width");
   if (((long)tb.tile * tb.tile) % 256 != 0) SRGD_FAIL("final_step: tile area must be a multiple of 256");
+  if (!tb.images) SRGD_FAIL("final_step: tile batch without image records");
   if (is_bf16) hipLaunchKernelGGL((final_step_kernel<bf16>), dim3(grid), dim3(256), 0, st, a, tb);
   else hipLaunchKernelGGL((final_step_kernel<float>), dim3(grid), dim3(256), 0, st, a, tb);
   SRGD_HIP(hipGetLastError());
@@ -525,34 +551,32 @@ int final_step_edm(const FinalStepArgs& a, const EdmScalars* sc, float* work, si
   return 0;
 }
 
-int canvas_prepare_cond(const float* cond01, int planes, int H, int W, int pad_l, int pad_t, int Hp, int Wp, int il,
-                        int it, int ir, int ib, float* cond_canvas, hipStream_t st) {
-  hipLaunchKernelGGL(canvas_prepare_cond_kernel, dim3(grid_for((long)planes * Hp * Wp)), dim3(256), 0, st, cond01, planes,
-                     H, W, pad_l, pad_t, Hp, Wp, il, it, ir, ib, cond_canvas);
+int canvas_prepare_cond(const float* cond01, const ImageDesc* images, int n_images, long max_canvas, float* cond_canvas,
+                        hipStream_t st) {
+  hipLaunchKernelGGL(canvas_prepare_cond_kernel, grid_per_image(max_canvas, n_images), dim3(256), 0, st, cond01, images,
+                     cond_canvas);
   SRGD_HIP(hipGetLastError());
   return 0;
 }
 
-int canvas_q_start(const float* cond01, int planes, int H, int W, int pad_l, int pad_t, int Hp, int Wp,
-                   const float* noise, float alpha, float sigma, float* img, hipStream_t st) {
-  hipLaunchKernelGGL(canvas_q_start_kernel, dim3(grid_for((long)planes * Hp * Wp)), dim3(256), 0, st, cond01, planes, H, W,
-                     pad_l, pad_t, Hp, Wp, noise, alpha, sigma, img);
+int canvas_q_start(const float* cond01, const ImageDesc* images, int n_images, long max_canvas, const float* noise, float alpha,
+                   float sigma, float* img, hipStream_t st) {
+  hipLaunchKernelGGL(canvas_q_start_kernel, grid_per_image(max_canvas, n_images), dim3(256), 0, st, cond01, images, noise, alpha,
+                     sigma, img);
   SRGD_HIP(hipGetLastError());
   return 0;
 }
 
-int canvas_ring_renoise(float* img, int planes, const float* noise, int Hp, int Wp, int il, int it, int ir, int ib,
+int canvas_ring_renoise(float* img, const ImageDesc* images, int n_images, long max_canvas, const float* noise,
                         const float* sigma_base, int sigma_stride, const int* step_ptr, hipStream_t st) {
-  hipLaunchKernelGGL(canvas_ring_renoise_kernel, dim3(grid_for((long)planes * Hp * Wp)), dim3(256), 0, st, img, planes,
-                     noise, Hp, Wp, il, it, ir, ib, sigma_base, sigma_stride, step_ptr);
+  hipLaunchKernelGGL(canvas_ring_renoise_kernel, grid_per_image(max_canvas, n_images), dim3(256), 0, st, img, images, noise,
+                     sigma_base, sigma_stride, step_ptr);
   SRGD_HIP(hipGetLastError());
   return 0;
 }
 
-int canvas_finish(const float* img, int planes, int Hp, int Wp, int left, int top, int H, int W, float* out01,
-                  hipStream_t st) {
-  hipLaunchKernelGGL(canvas_finish_kernel, dim3(grid_for((long)planes * H * W)), dim3(256), 0, st, img, planes, Hp, Wp,
-                     left, top, H, W, out01);
+int canvas_finish(const float* img, const ImageDesc* images, int n_images, long max_image, float* out01, hipStream_t st) {
+  hipLaunchKernelGGL(canvas_finish_kernel, grid_per_image(max_image, n_images), dim3(256), 0, st, img, images, out01);
   SRGD_HIP(hipGetLastError());
   return 0;
 }

@@ -11,7 +11,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._lib import SamplerGeometry, StepScalars, UnetConfig, check
+from ._lib import SamplerGeometry, SamplerImage, StepScalars, UnetConfig, check
 
 _PRECISIONS = {"fp32": _lib.PRECISION_FP32, "bf16": _lib.PRECISION_BF16, "bf16_w8": _lib.PRECISION_BF16_W8,
                "fp8": _lib.PRECISION_FP8, "fp8_mixed": _lib.PRECISION_FP8_MIXED, "f16x3": _lib.PRECISION_F16X3, "f16mx2": _lib.PRECISION_F16MX2}
@@ -123,6 +123,21 @@ class HipEngine:
         with torch.cuda.device(self.device):
             check(self._L.srgd_sampler_begin(self._h, C.byref(geo), _dev_ptr(cond01), _dev_ptr(cond_canvas), te, to, n,
                                              sc, ls, int(class_id), _stream_ptr(self.device)), "srgd_sampler_begin")
+
+    def sampler_begin_images(self, tile: int, images: Sequence[SamplerImage], cond01: torch.Tensor, cond_canvas: torch.Tensor,
+                             tiles_even: Sequence[Tuple[int, int]], tiles_odd: Sequence[Tuple[int, int]],
+                             scalars: Sequence[StepScalars], log_snr: Sequence[float], class_id: int) -> None:
+        """Mixed-size lock-step run (srgd_sampler_begin_images): flat buffers and tile lists in image order."""
+        n = len(scalars)
+        im = (SamplerImage * len(images))(*images)
+        te = (C.c_int32 * (2 * len(tiles_even)))(*[v for yx in tiles_even for v in yx])
+        to = (C.c_int32 * (2 * len(tiles_odd)))(*[v for yx in tiles_odd for v in yx])
+        sc = (StepScalars * n)(*scalars)
+        ls = (C.c_float * n)(*[float(v) for v in log_snr])
+        with torch.cuda.device(self.device):
+            check(self._L.srgd_sampler_begin_images(self._h, int(tile), len(images), im, _dev_ptr(cond01), _dev_ptr(cond_canvas),
+                                                    te, to, n, sc, ls, int(class_id), _stream_ptr(self.device)),
+                  "srgd_sampler_begin_images")
 
     def sampler_step(self, step: int, img: torch.Tensor, cond_canvas: torch.Tensor, x_start: Optional[torch.Tensor],
                      noise_tiles: Optional[torch.Tensor], noise_canvas: Optional[torch.Tensor], passes: int,

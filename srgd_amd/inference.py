@@ -22,7 +22,7 @@ import torch
 from PIL import Image
 
 from .config import load_config
-from .model import get_model
+from .model import ConditionalElucidatedDiffusionSR, get_model
 
 logger = logging.getLogger("srgd_amd")
 
@@ -56,9 +56,13 @@ def parse_args(argv=None):
                         "throughput modes of the MI355X engine (explicit opt-in, not within 1e-3)")
     p.add_argument("--device_noise", action="store_true",
                    help="draw DDPM noise on the GPU (Philox) instead of replaying torch's CPU stream")
-    p.add_argument("--lockstep", type=int, default=1,
-                   help="sample up to N consecutive same-sized images together (their tiles share U-Net launches, "
-                        "--batch_size tiles per image and launch); every image comes out bit-identical to its solo run")
+    group = p.add_mutually_exclusive_group()
+    group.add_argument("--lockstep", type=int, default=1,
+                       help="sample up to N consecutive same-sized images together (their tiles share U-Net launches, "
+                            "--batch_size tiles per image and launch); every image comes out bit-identical to its solo run")
+    group.add_argument("--lockstep_tiles", type=int, default=None, metavar="T",
+                       help="sample consecutive images of ANY size together, up to T tiles per even step (an image larger "
+                            "than T runs alone); every image comes out bit-identical to its solo run (DDPM configs only)")
     return p.parse_args(argv)
 
 
@@ -167,6 +171,27 @@ def sr_target_images(images, sr_model, scale=4, batch_size=8, test_label=2, cond
     return outs
 
 
+def sr_target_images_mixed(images, sr_model, scale=4, batch_size=8, test_label=2, cond_scale=1.0, guidance_start_steps=0,
+                           class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0,
+                           num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71):
+    """``sr_target_image`` for several images of any sizes in lock-step (engine extension): one ``tiled_sample`` call on a list
+    of conditions.  Each image comes out bit-identical to its own ``sr_target_image`` run."""
+    conds = [upsample_bicubic_on_device(im, scale, sr_model.device) for im in images]
+    label = torch.LongTensor([test_label]).to(sr_model.device) if test_label is not None else None
+    seed_everything(seed)
+    sr_model.device_noise_seed = seed
+    with torch.inference_mode():
+        output = sr_model.tiled_sample(batch_size=batch_size * len(images), condition_x=conds, class_label=label,
+                                       cond_scale=cond_scale, guidance_start_steps=guidance_start_steps,
+                                       class_cond_scale=class_cond_scale,
+                                       class_guidance_start_steps=class_guidance_start_steps,
+                                       generation_start_steps=generation_start_steps,
+                                       num_sample_steps=num_sample_steps, amp=enable_amp)
+    outs = [unit_tensor_to_pil_on_device(o[0]) for o in output]
+    assert all(o.size == (im.size[0] * 4, im.size[1] * 4) for o, im in zip(outs, images))
+    return outs
+
+
 def try_open_image(image_path):
     try:
         return Image.open(image_path).convert("RGB")
@@ -177,7 +202,10 @@ def try_open_image(image_path):
 def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=8, test_label=2, cond_scale=1.0,
                            guidance_start_steps=0, class_cond_scale=1.0, class_guidance_start_steps=0,
                            generation_start_steps=0, num_sample_steps=250, start_index=0, end_index=None,
-                           enable_amp=False, interpolation="bicubic", seed=71, lockstep=1):
+                           enable_amp=False, interpolation="bicubic", seed=71, lockstep=1, lockstep_tiles=None):
+    """``lockstep``: groups of up to N consecutive same-sized images; ``lockstep_tiles``: groups of consecutive images of any
+    size up to that many tiles per even step (srgd_amd.lockstep.plan_lockstep_groups)."""
+    from .lockstep import even_step_tiles, plan_lockstep_groups
     print(f"save images at: {output_dir}")
     os.makedirs(output_dir, exist_ok=True)
     kw = dict(scale=scale, batch_size=batch_size, test_label=test_label, cond_scale=cond_scale,
@@ -191,8 +219,14 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
         def flush():
             if not pending:
                 return
+            if lockstep_tiles is not None:
+                sizes = [im.size for im, _ in pending]
+                tiles = sum(even_step_tiles(h * scale, w * scale) for (w, h) in sizes)
+                print(f"lock-step group: {len(pending)} images, {tiles} tiles per even step")
             if len(pending) == 1:
                 outs = [sr_target_image(pending[0][0], sr_model, **kw)]
+            elif lockstep_tiles is not None:
+                outs = sr_target_images_mixed([im for im, _ in pending], sr_model, **kw)
             else:
                 outs = sr_target_images([im for im, _ in pending], sr_model, **kw)
             for (_, path), sr in zip(pending, outs):
@@ -207,6 +241,12 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
             image = try_open_image(filename)
             if image is None:
                 print("Invalid image or unable to open image:", filename)
+                continue
+            if lockstep_tiles is not None:
+                hr = [(h * scale, w * scale) for (w, h) in [im.size for im, _ in pending] + [image.size]]
+                if len(plan_lockstep_groups(hr, lockstep_tiles)) > 1:      # the image would push the group over the budget
+                    flush()
+                pending.append((image, save_path))
                 continue
             if pending and (len(pending) >= max(1, lockstep) or pending[0][0].size != image.size):
                 flush()
@@ -246,6 +286,9 @@ def main(argv=None):
         args.start_index, args.end_index = rank_file_range(n_files, args.start_index, args.end_index, rank, world)
         print(f"rank {rank}/{world}: files [{args.start_index}:{args.end_index}] of {n_files}")
     sr_model = ema_model.module.eval().to(torch.device("cuda", torch.cuda.current_device()))
+    if args.lockstep_tiles is not None and isinstance(sr_model, ConditionalElucidatedDiffusionSR):
+        raise SystemExit("--lockstep_tiles: mixed-size lock-step is built for the DDPM sampler (model: conditional_continuous) only; "
+                         "this config samples with EDM - use --lockstep N for same-sized images")
     sr_model.noise_source = "device" if args.device_noise else "host"
     sr_model.precision = args.precision
     print(f"engine precision: {args.precision} (noise: {sr_model.noise_source})")
@@ -272,7 +315,7 @@ def main(argv=None):
                            generation_start_steps=args.generation_start_steps,
                            num_sample_steps=args.num_sample_steps, start_index=args.start_index,
                            end_index=args.end_index, enable_amp=args.amp, interpolation=args.interpolation,
-                           seed=args.seed, lockstep=args.lockstep)
+                           seed=args.seed, lockstep=args.lockstep, lockstep_tiles=args.lockstep_tiles)
 
 
 if __name__ == "__main__":

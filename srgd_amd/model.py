@@ -311,6 +311,16 @@ class ConditionalSRUnet(nn.Module):
 # ---------------------------------------------------------------------------------------------
 # the sampler
 # ---------------------------------------------------------------------------------------------
+def _step_guidance(i, cond_scale, guidance_start_steps, class_cond_scale, class_guidance_start_steps):
+    """(passes, guidance_kind, scale) of DDPM step i (model.py:3147-3156)."""
+    cur_cond_scale = 1.0 if i < guidance_start_steps else cond_scale
+    cur_class_scale = 1.0 if i < class_guidance_start_steps else class_cond_scale
+    if cur_cond_scale != 1.0:
+        return 2, 2, cur_cond_scale
+    if cur_class_scale != 1.0:
+        return 2, 1, cur_class_scale
+    return 1, 0, 1.0
+
 class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
     def __init__(self, model, *, image_size, channels=3, noise_schedule="linear", num_sample_steps=500,
                  clip_sample_denoised=True, learned_schedule_net_hidden_dim=1024,
@@ -367,8 +377,25 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
         ``[B,3,H,W]``: B same-sized images sampled in lock-step, each exactly as the reference would
         sample it on its own after ``seed_everything(seed)`` (inference.py:73) - i.e. all B see the
         same noise stream - with every U-Net launch spanning tiles of all images (fills the GPU
-        better than 25/16 tiles of one image do).  ``batch_size`` counts tiles across all images."""
+        better than 25/16 tiles of one image do).  ``batch_size`` counts tiles across all images.
+
+        ``condition_x`` may also be a list or tuple of ``[1,3,H_i,W_i]`` tensors of different sizes: they are sampled in
+        lock-step the same way (mixed-size lock-step, ``_tiled_sample_images``) and a list of ``[1,3,H_i,W_i]`` outputs is
+        returned, each bit-identical to a call with that image alone."""
         num_sample_steps = self.num_sample_steps if num_sample_steps is None else num_sample_steps
+        if isinstance(condition_x, (list, tuple)):
+            if with_images or with_x0_images:
+                raise NotImplementedError("with_images / with_x0_images of a mixed-size group (trajectories of different shapes)")
+            if self.canvas_group is not None:
+                raise NotImplementedError("mixed-size lock-step on a canvas sharded over ranks (canvas_group)")
+            if cond_scale != 1.0 and class_cond_scale != 1.0:
+                raise NotImplementedError("Currently, you cannot specify both cond_scale and class_cond_scale at the same time.")
+            if tile_size != 256 or tile_stride != 256:
+                raise NotImplementedError("tile_size/tile_stride other than 256 are unusable in the reference too "
+                                          "(get_coord_and_pad is called without them, model.py:3301)")
+            return self._tiled_sample_images(batch_size, tile_size, list(condition_x), class_label, cond_scale,
+                                             guidance_start_steps, class_cond_scale, class_guidance_start_steps,
+                                             generation_start_steps, num_sample_steps, start_white_noise, precision)
         if cond_scale != 1.0 and class_cond_scale != 1.0:
             raise NotImplementedError("Currently, you cannot specify both cond_scale and class_cond_scale at the same time.")
         if tile_size != 256 or tile_stride != 256:
@@ -428,14 +455,8 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
         for i in range(num_sample_steps):
             if i < generation_start_steps:
                 continue
-            cur_cond_scale = 1.0 if i < guidance_start_steps else cond_scale
-            cur_class_scale = 1.0 if i < class_guidance_start_steps else class_cond_scale
-            if cur_cond_scale != 1.0:
-                passes, kind, scale = 2, 2, cur_cond_scale
-            elif cur_class_scale != 1.0:
-                passes, kind, scale = 2, 1, cur_class_scale
-            else:
-                passes, kind, scale = 1, 0, 1.0
+            passes, kind, scale = _step_guidance(i, cond_scale, guidance_start_steps, class_cond_scale,
+                                                 class_guidance_start_steps)
             n_tiles = len(grids[i % 2])
             last = i == num_sample_steps - 1
             noise_tiles = noise_canvas = None
@@ -475,6 +496,115 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
         if with_images:
             return (out, image_list, x0_image_list) if with_x0_images else (out, image_list)
         return out
+
+    def _tiled_sample_images(self, batch_size, tile_size, conds, class_label, cond_scale, guidance_start_steps,
+                             class_cond_scale, class_guidance_start_steps, generation_start_steps, num_sample_steps,
+                             start_white_noise, precision):
+        """Mixed-size lock-step (srgd_sampler_begin_images): every image keeps its own canvas, crop box, padding, inner box and
+        tile grids; a step's tiles of all images share the U-Net launches.  Noise: the images of one noise class (canvas size)
+        see the draw sequence a run of one of them alone sees.  Host noise: the generator state is taken once at entry and
+        each class draws from its own generator started at that state, in the reference's order; on return the caller's
+        generator (``host_generator`` or torch's global one) holds the state a run of the FIRST image alone would leave."""
+        from .lockstep import plan_mixed_group
+        dev = self.device
+        if dev.type != "cuda":
+            raise _lib.SrgdHipError("tiled_sample runs on MI355X only (no CPU fallback)")
+        if not conds:
+            raise ValueError("condition_x: empty list")
+        for c in conds:
+            if not torch.is_tensor(c) or c.dim() != 4 or c.shape[0] != 1 or c.shape[1] != 3:
+                raise ValueError("a list condition_x holds [1,3,H,W] tensors")
+        plans, classes = plan_mixed_group([(int(c.shape[2]), int(c.shape[3])) for c in conds], tile_size)
+        prec = precision or self.precision
+        eng = self.model.engine(prec)
+        class_id = _single_class_id(class_label)
+        images = [_lib.SamplerImage(H=p.H, W=p.W, Hp=p.Hp, Wp=p.Wp, left=p.box[0], top=p.box[1], inner_l=p.inner[0],
+                                    inner_t=p.inner[1], inner_r=p.inner[2], inner_b=p.inner[3], n_even=len(p.coords0),
+                                    n_odd=len(p.coords1), noise_class=p.noise_class) for p in plans]
+        tiles_even = [(a, c_) for p in plans for (a, _, c_, _) in p.coords0]
+        tiles_odd = [(a, c_) for p in plans for (a, _, c_, _) in p.coords1]
+        scalars, log_snrs = _schedule(num_sample_steps)
+        cond01 = torch.cat([c.to(dev, torch.float32).reshape(-1) for c in conds])
+        cond_canvas = torch.empty(sum(3 * p.Hp * p.Wp for p in plans), device=dev, dtype=torch.float32)
+
+        def begin(e_, canvas):
+            e_.sampler_begin_images(tile_size, images, cond01, canvas, tiles_even, tiles_odd, scalars, log_snrs, class_id)
+        begin(eng, cond_canvas)
+
+        first_of_class = [next(p for p in plans if p.noise_class == k) for k in range(len(classes))]
+        host_noise = self.noise_source == "host"
+        if host_noise:
+            caller_gen = self.host_generator if self.host_generator is not None else torch.default_generator
+            state = caller_gen.get_state()
+            gens = []
+            for _ in classes:
+                g_ = torch.Generator()
+                g_.set_state(state)
+                gens.append(g_)
+
+            def draw(shape_of_class):       # per-class draws in class order, concatenated (the engine's noise layout)
+                return torch.cat([_host_randn(g_, *shape_of_class(k)).reshape(-1) for k, g_ in enumerate(gens)]).to(dev)
+
+            def canvas_draw():
+                return draw(lambda k: (1, 3) + classes[k])
+        if generation_start_steps > 0 or not start_white_noise:
+            t0 = (1.0 - torch.tensor(generation_start_steps / num_sample_steps)) if generation_start_steps > 0 \
+                else torch.tensor(1.0)
+            ls0 = beta_linear_log_snr(t0)
+            img = torch.empty_like(cond_canvas)
+            eng.sampler_q_start(cond01, canvas_draw() if host_noise else None, float(ls0.sigmoid().sqrt()),
+                                float((-ls0).sigmoid().sqrt()), img, self.device_noise_seed)
+        else:
+            if host_noise:
+                start = canvas_draw()
+            else:                           # the counter-based draw of each class's canvas, as a run alone draws it
+                start = torch.cat([eng.randn_(torch.empty(3 * hp * wp, device=dev), self.device_noise_seed, 0)
+                                   for (hp, wp) in classes])
+            offs = [0]
+            for (hp, wp) in classes:
+                offs.append(offs[-1] + 3 * hp * wp)
+            img = torch.cat([start[offs[p.noise_class]:offs[p.noise_class + 1]] for p in plans])
+
+        sub_batch = self.max_tiles_per_launch or batch_size
+        n_grid = (len(tiles_even), len(tiles_odd))
+        lanes = None
+        for i in range(num_sample_steps):
+            if i < generation_start_steps:
+                continue
+            passes, kind, scale = _step_guidance(i, cond_scale, guidance_start_steps, class_cond_scale,
+                                                 class_guidance_start_steps)
+            last = i == num_sample_steps - 1
+            noise_tiles = noise_canvas = None
+            if host_noise:                  # each class in the reference's order: the step's tile noise, then the odd-step ring
+                if not last:
+                    noise_tiles = draw(lambda k: (len((first_of_class[k].coords0, first_of_class[k].coords1)[i % 2]), 3,
+                                                  tile_size, tile_size))
+                if i % 2 == 1:
+                    noise_canvas = canvas_draw()
+            n_step = n_grid[i % 2]
+            n_lanes = lanes_wanted(n_step, passes, sub_batch, self.step_lanes, prec)
+            if n_lanes > 1:
+                if lanes is None or len(lanes.engines) != n_lanes:   # further engines: the same mixed run, own condition canvas
+                    more = [self.model.engine(prec, lane=k) for k in range(1, n_lanes)]
+                    for e_ in more:
+                        begin(e_, torch.empty_like(cond_canvas))
+                    lanes = StepLanes([eng] + more, dev)
+                lanes.run(n_step, lambda e_, first, count, ring: e_.sampler_step_tiles(
+                    i, first, count, ring, img, cond_canvas, None, noise_tiles, noise_canvas, passes, kind, scale, sub_batch,
+                    seed=self.device_noise_seed))
+            else:
+                eng.sampler_step(i, img, cond_canvas, None, noise_tiles, noise_canvas, passes, kind, scale, sub_batch,
+                                 seed=self.device_noise_seed)
+
+        out = torch.empty(sum(3 * p.H * p.W for p in plans), device=dev, dtype=torch.float32)
+        eng.sampler_end(img, out)
+        if host_noise:
+            caller_gen.set_state(gens[plans[0].noise_class].get_state())
+        outs, off = [], 0
+        for p in plans:
+            outs.append(out[off:off + 3 * p.H * p.W].view(1, 3, p.H, p.W))
+            off += 3 * p.H * p.W
+        return outs
 
     @torch.inference_mode()
     def sample(self, batch_size=16, condition_x=None, class_label=None, cond_scale=1.0, guidance_start_steps=0,
@@ -668,6 +798,9 @@ class ConditionalElucidatedDiffusionSR(nn.Module):
         """Reference model.py:2309-2475 (``start_white_noise`` and ``amp`` are accepted and unused there too; ``precision``
         is the engine-only override of ``self.precision``)."""
         n = self.num_sample_steps if num_sample_steps is None else num_sample_steps
+        if isinstance(condition_x, (list, tuple)):
+            raise NotImplementedError("mixed-size lock-step (a list condition_x) is built for the DDPM sampler only; "
+                                      "sample EDM images one size at a time")
         if cond_scale != 1.0 and class_cond_scale != 1.0:
             raise NotImplementedError("Currently, you cannot specify both cond_scale and class_cond_scale at the same time.")
         if tile_size != 256 or tile_stride != 256:
