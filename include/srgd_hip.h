@@ -61,6 +61,12 @@ typedef struct srgd_engine srgd_engine;
                                  * the three-MFMA arithmetic - that is where the error is made: within 1.4-1.8x of SRGD_PRECISION_F16X3
                                  * on every reference fixture, +7 % throughput.  Everything else as SRGD_PRECISION_F16X3. */
 
+/* Non-finite values, in EVERY precision above: a NaN or an infinity that enters a kernel reaches every output that the same
+ * operation of the reference would make non-finite, and no other output changes.  In particular the sampler's clamps keep a NaN
+ * (torch.clamp's rule), the RMSNorms' max(norm, 1e-12) keeps a NaN norm, and the f16 (hi, lo) split of SRGD_PRECISION_F16X3 /
+ * _F16MX2 turns a NaN or an infinite activation into NaN; only a FINITE activation beyond f16's range (|x| > 65504) saturates
+ * there.  MX-fp8 operands: a NaN becomes the e4m3 NaN byte, an infinity saturates to +-448 like any out-of-range value. */
+
 /* Constructor arguments of ConditionalSRUnet (model.py:537-556) as get_model passes them
  * (model.py:3504-3514).  Unsupported combinations are rejected by srgd_create. */
 typedef struct srgd_unet_config {

@@ -21,7 +21,9 @@ import torch.nn.functional as F
 def halves(x: torch.Tensor, kind: str):
     dt = torch.float16 if kind == "f16" else torch.bfloat16
     if kind == "f16":
-        x = x.clamp(-65504.0, 65504.0)          # the kernels saturate instead of producing inf - inf
+        # the kernels saturate a FINITE value beyond f16's range instead of producing inf - inf; a NaN or an infinity becomes NaN
+        # in both halves (sat_f16_keep_nonfinite, srgd_amd/csrc/common.hpp)
+        x = torch.where(torch.isfinite(x), x.clamp(-65504.0, 65504.0), torch.full_like(x, float("nan")))
     hi = x.to(dt).float()
     lo = (x - hi).to(dt).float()
     return hi, lo
@@ -60,7 +62,7 @@ def mixed_split_conv2d(x, w, b=None, stride=1, padding=0, mode="f16x2_w1"):
     wh, wl = halves(w * s, "f16")
     xh, xl = halves(x, "f16")
     if mode == "f16mx2":
-        xl = x.clamp(-65504.0, 65504.0) - xh     # the prototype kernel (conv3x3_mx2.hip) quantises x - x_hi itself, not its f16 rounding
+        xl = x.clamp(-65504.0, 65504.0) - xh     # (xh is NaN for a non-finite x, and so is this) the prototype kernel (conv3x3_mx2.hip) quantises x - x_hi itself, not its f16 rounding
     y = F.conv2d(xh, wh, None, stride=stride, padding=padding)
     if mode == "f16x2_w1":
         y = y + F.conv2d(xl, wh, None, stride=stride, padding=padding)

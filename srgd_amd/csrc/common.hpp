@@ -70,6 +70,28 @@ template <bool PRECISE> __device__ __forceinline__ float silu(float x) {
   return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x));
 }
 
+// ---- non-finite values stay visible (the rule is stated in include/srgd_hip.h) ----------
+// fminf / fmaxf return the OTHER operand for a NaN, so clamp = fminf(fmaxf(x, lo), hi) turns NaN into lo and max(norm, eps) turns a
+// NaN norm into eps.  The compare-and-select forms leave a NaN alone, as torch.clamp / clamp_min do, and give the same value as the
+// fminf / fmaxf forms for every other input (+-0 and +-Inf included).  (The DDPM epilogue, the canvas kernels and the norms compile
+// to the arithmetic they had, finite results bit-identical.  In the EDM epilogue the compiler now contracts one of the three
+// c_skip * x + c_out * net sums differently (two multiplies and an add where it had mul + fma): EDM results move in the last bit,
+// 1e-7 on a [0, 1] image.  A select over the old v_med3 and an asm select-back were tried; both moved more.)
+__device__ __forceinline__ float clamp_keep_nan(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
+__device__ __forceinline__ float max_keep_nan(float x, float floor_) { return x < floor_ ? floor_ : x; }
+// The split kernels' saturation ahead of the f16 (hi, lo) split: a finite value beyond f16's range becomes +-65504 (v_med3), a NaN
+// or an infinity becomes NaN (v_med3 alone maps NaN to -65504 and Inf to +-65504 on gfx950).  x * 0 is +-0 for every finite x - the
+// sum is then the clamped value bit for bit (it is +-0 only where x is, with x's sign) - and NaN for NaN and +-Inf: ONE v_fma per
+// element, against two for v_cmp_class + v_cndmask, in staging loops that run beside the MFMAs.  Through asm, because plain -O3
+// SLP-packs two neighbouring __builtin_fmaf into one v_pk_fma_f32, and packed fp32 VALU beside MFMAs costs more than the two scalar
+// instructions it replaces (VALU -> VALU: no wait states needed on either side of it).
+__device__ __forceinline__ float sat_f16_keep_nonfinite(float x) {
+  const float c = __builtin_amdgcn_fmed3f(x, -65504.f, 65504.f);
+  float r;
+  asm("v_fma_f32 %0, %1, 0, %2" : "=v"(r) : "v"(x), "v"(c));
+  return r;
+}
+
 // Sum over the 16 lanes of a DPP row (lanes 16k..16k+15), result in every lane of the row: two quad permutes, then
 // row_half_mirror and row_mirror (after the quad steps a quad is uniform, so the mirrors fetch "the other quad / half").
 // VALU-only - 4 DPP moves instead of 4 ds_bpermute round trips through the LDS crossbar.

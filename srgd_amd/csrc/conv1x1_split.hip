@@ -72,14 +72,13 @@ struct Split1Args {
     __builtin_amdgcn_sched_barrier(0);   \
   } while (0)
 
-// 8 fp32 (two 16-byte loads) -> the hi and lo f16 fragments (saturating, as conv3x3_split.hip)
+// 8 fp32 (two 16-byte loads) -> the hi and lo f16 fragments (finite values saturate, non-finite ones become NaN, as conv3x3_split.hip)
 __device__ __forceinline__ void split8(const u32x4& r0, const u32x4& r1, u32x4& hi, u32x4& lo) {
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    float a = __builtin_bit_cast(float, k < 2 ? r0[2 * k] : r1[2 * k - 4]);
-    float b = __builtin_bit_cast(float, k < 2 ? r0[2 * k + 1] : r1[2 * k - 3]);
-    a = __builtin_amdgcn_fmed3f(a, -65504.f, 65504.f);
-    b = __builtin_amdgcn_fmed3f(b, -65504.f, 65504.f);
+    const unsigned ua = k < 2 ? r0[2 * k] : r1[2 * k - 4], ub = k < 2 ? r0[2 * k + 1] : r1[2 * k - 3];
+    const float a = sat_f16_keep_nonfinite(__uint_as_float(ua));
+    const float b = sat_f16_keep_nonfinite(__uint_as_float(ub));
     const f16x2 h = __builtin_convertvector(f32x2{a, b}, f16x2);
     const f32x2 hf = __builtin_convertvector(h, f32x2);
     const f16x2 l = __builtin_convertvector(f32x2{a - hf[0], b - hf[1]}, f16x2);
@@ -296,8 +295,8 @@ __global__ __launch_bounds__(NT, 2) void conv1x1_split_kernel(Split1Args p) {
     // x / max(||x||, 1e-12)
     ss0 = xor32_sum(xor16_sum(ss0));
     ss1 = xor32_sum(xor16_sum(ss1));
-    ws0 = ws / fmaxf(sqrtf(ss0), 1e-12f);
-    ws1 = ws / fmaxf(sqrtf(ss1), 1e-12f);
+    ws0 = ws / max_keep_nan(sqrtf(ss0), 1e-12f);
+    ws1 = ws / max_keep_nan(sqrtf(ss1), 1e-12f);
   }
   f32x4 v0_[8] = {c00 * ws0 + bs0, c01 * ws0 + bs1, c02 * ws0 + bs2, c03 * ws0 + bs3, c04 * ws0 + bs4, c05 * ws0 + bs5, c06 * ws0 + bs6, c07 * ws0 + bs7};
   f32x4 v1_[8] = {c10 * ws1 + bs0, c11 * ws1 + bs1, c12 * ws1 + bs2, c13 * ws1 + bs3, c14 * ws1 + bs4, c15 * ws1 + bs5, c16 * ws1 + bs6, c17 * ws1 + bs7};
@@ -321,7 +320,7 @@ __global__ __launch_bounds__(NT, 2) void conv1x1_split_kernel(Split1Args p) {
     }
     t0 = xor32_sum(xor16_sum(t0));
     t1 = xor32_sum(xor16_sum(t1));
-    const float i0 = 1.0f / fmaxf(sqrtf(t0), 1e-12f), i1 = 1.0f / fmaxf(sqrtf(t1), 1e-12f);
+    const float i0 = 1.0f / max_keep_nan(sqrtf(t0), 1e-12f), i1 = 1.0f / max_keep_nan(sqrtf(t1), 1e-12f);
 #pragma unroll
     for (int J = 0; J < 8; ++J) { v0_[J] = v0_[J] * i0 * g_[J] + r0_[J]; v1_[J] = v1_[J] * i1 * g_[J] + r1_[J]; }
   }

@@ -93,8 +93,8 @@ __device__ __forceinline__ void split8f(const u32x4& r0, const u32x4& r1, u32x4&
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const unsigned ua = k < 2 ? r0[2 * k] : r1[2 * k - 4], ub = k < 2 ? r0[2 * k + 1] : r1[2 * k - 3];
-    const float a = __builtin_amdgcn_fmed3f(__uint_as_float(ua), -65504.f, 65504.f);
-    const float b = __builtin_amdgcn_fmed3f(__uint_as_float(ub), -65504.f, 65504.f);
+    const float a = sat_f16_keep_nonfinite(__uint_as_float(ua));
+    const float b = sat_f16_keep_nonfinite(__uint_as_float(ub));
     const f16x2 h = __builtin_convertvector(f32x2{a, b}, f16x2);
     const f32x2 hf = __builtin_convertvector(h, f32x2);
     hi[k] = __builtin_bit_cast(unsigned, h);

@@ -70,17 +70,18 @@ struct Split3Args {
 
 __device__ __forceinline__ int row_swz(int row) { return (row >> 1) & 3; }
 
-// 8 fp32 -> 8 hi + 8 lo 16-bit values (each a 16-byte vector).  F16: values beyond f16's range saturate (finite garbage instead
-// of inf - inf = NaN; activations on this path are O(1..100)).
+// 8 fp32 -> 8 hi + 8 lo 16-bit values (each a 16-byte vector).  F16: a FINITE value beyond f16's range saturates at +-65504 (finite
+// garbage instead of inf - inf = NaN; activations on this path are O(1..100)); a NaN or an infinity leaves as NaN in both halves
+// and so reaches every output it contributes to (sat_f16_keep_nonfinite, common.hpp).  bf16 halves share fp32's range: no clamp.
 template <bool F16>
 __device__ __forceinline__ void split8(const u32x4& r0, const u32x4& r1, u32x4& hi, u32x4& lo) {
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    float a = __builtin_bit_cast(float, k < 2 ? r0[2 * k] : r1[2 * k - 4]);
-    float b = __builtin_bit_cast(float, k < 2 ? r0[2 * k + 1] : r1[2 * k - 3]);
+    const unsigned ua = k < 2 ? r0[2 * k] : r1[2 * k - 4], ub = k < 2 ? r0[2 * k + 1] : r1[2 * k - 3];
+    float a = __uint_as_float(ua), b = __uint_as_float(ub);
     if constexpr (F16) {
-      a = __builtin_amdgcn_fmed3f(a, -65504.f, 65504.f);
-      b = __builtin_amdgcn_fmed3f(b, -65504.f, 65504.f);
+      a = sat_f16_keep_nonfinite(a);
+      b = sat_f16_keep_nonfinite(b);
       const f16x2 h = __builtin_convertvector(f32x2{a, b}, f16x2);
       const f32x2 hf = __builtin_convertvector(h, f32x2);
       const f16x2 l = __builtin_convertvector(f32x2{a - hf[0], b - hf[1]}, f16x2);

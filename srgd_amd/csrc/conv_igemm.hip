@@ -352,8 +352,8 @@ __device__ __forceinline__ void split4(const f32x4& x, unsigned (&hi)[2], unsign
   for (int k = 0; k < 2; ++k) {
     float a = x[2 * k], b = x[2 * k + 1];
     if constexpr (F16) {
-      a = __builtin_amdgcn_fmed3f(a, -65504.f, 65504.f);
-      b = __builtin_amdgcn_fmed3f(b, -65504.f, 65504.f);
+      a = sat_f16_keep_nonfinite(a);        // finite out-of-range saturates, NaN / Inf become NaN (common.hpp)
+      b = sat_f16_keep_nonfinite(b);
       const f16x2 hh = __builtin_convertvector(f32x2{a, b}, f16x2);
       const f32x2 hf = __builtin_convertvector(hh, f32x2);
       const f16x2 ll = __builtin_convertvector(f32x2{a - hf[0], b - hf[1]}, f16x2);

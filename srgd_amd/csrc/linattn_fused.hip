@@ -90,7 +90,7 @@ __device__ __forceinline__ void row_rinv(const char* tile, float* rinv, int tid)
   }
   ss += __shfl_xor(ss, 1, 64);
   ss += __shfl_xor(ss, 2, 64);
-  if (part == 0) rinv[row] = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
+  if (part == 0) rinv[row] = 1.0f / max_keep_nan(sqrtf(ss), 1e-12f);
 }
 
 // raw v_exp_f32 (arguments here are <= 0 up to rounding: no denormal-range rescue needed)
@@ -439,7 +439,7 @@ __global__ __launch_bounds__(NTH, 2) void la2_kernel(La2Args p) {
     {
       const float n0 = sS[r] + sS[TM + r] + sS[2 * TM + r] + sS[3 * TM + r];
       const float n1 = sS[32 + r] + sS[TM + 32 + r] + sS[2 * TM + 32 + r] + sS[3 * TM + 32 + r];
-      const float r0 = 1.0f / fmaxf(sqrtf(n0), 1e-12f), r1 = 1.0f / fmaxf(sqrtf(n1), 1e-12f);
+      const float r0 = 1.0f / max_keep_nan(sqrtf(n0), 1e-12f), r1 = 1.0f / max_keep_nan(sqrtf(n1), 1e-12f);
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const bf16x4 w0 = pack4(o0[4 * g] * r0 * g2v[4 * g], o0[4 * g + 1] * r0 * g2v[4 * g + 1], o0[4 * g + 2] * r0 * g2v[4 * g + 2],

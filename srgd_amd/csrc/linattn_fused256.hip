@@ -71,7 +71,7 @@ __device__ __forceinline__ void row_rinv2(const char* tile, float* rinv, int tid
   ss += __shfl_xor(ss, 1, 64);
   ss += __shfl_xor(ss, 2, 64);
   ss += __shfl_xor(ss, 4, 64);
-  if (part == 0) rinv[row] = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
+  if (part == 0) rinv[row] = 1.0f / max_keep_nan(sqrtf(ss), 1e-12f);
 }
 
 // the DMA pieces of the youngest staged tile may stay in flight (PIECES is a template constant: s_waitcnt takes an immediate)
@@ -354,7 +354,7 @@ __global__ __launch_bounds__(NTH2, C == 128 ? 3 : 2) void la2_t_kernel(La2Args25
     LB_SYNC();                                              // also: every wave is done reading the att tile
     {
       const float n0 = sS[r] + sS[TM2 + r] + sS[2 * TM2 + r] + sS[3 * TM2 + r];
-      const float rn = 1.0f / fmaxf(sqrtf(n0), 1e-12f);
+      const float rn = 1.0f / max_keep_nan(sqrtf(n0), 1e-12f);
       // y = RMSNorm(o) * g2 + x formed in place: this lane owns pixel r, channels c..c+3 of each block
 #pragma unroll
       for (int g = 0; g < 4; ++g) {

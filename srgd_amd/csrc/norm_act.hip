@@ -159,7 +159,7 @@ __global__ __launch_bounds__(256) void rms_norm_kernel(const T* __restrict__ x, 
       for (int j = 0; j < N; ++j) ss += t.get(j) * t.get(j);
     }
     for (int o = L >> 1; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
-    const float inv = sqrtC / fmaxf(sqrtf(ss), 1e-12f);
+    const float inv = sqrtC / max_keep_nan(sqrtf(ss), 1e-12f);
     for (int v = sub; v < vpp; v += L) {
       Vec16<T> t = xp[v], o, r;
       if (res) r = reinterpret_cast<const Vec16<T>*>(res)[p * vpp + v];

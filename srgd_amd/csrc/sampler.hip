@@ -202,7 +202,7 @@ __global__ __launch_bounds__(256) void final_step_kernel(FinalStepArgs a, TileBa
   for (int c = 0; c < 3; ++c) {
     const float xt = a.img[c * plane + o];
     float x0 = (xt - sc.sigma * eps[c][threadIdx.x]) / sc.alpha;                // model.py:3160
-    x0 = fminf(fmaxf(x0, -1.0f), 1.0f);                                        // :3163
+    x0 = clamp_keep_nan(x0, -1.0f, 1.0f);                                       // :3163
     float mean = sc.alpha_next * (xt * sc.one_minus_c / sc.alpha + sc.c * x0);  // :3164
     if (a.noise) mean += sc.noise_scale * a.noise[((long)tl * 3 + c) * per_tile + r];   // :3187-3188
     a.img[c * plane + o] = mean;
@@ -266,7 +266,7 @@ __global__ __launch_bounds__(256) void final_step_edm_kernel(FinalStepArgs a, co
     if (edm_pass == 2) {                      // DPM-Solver++(2M) update of the un-tiled loop (model.py:2528-2547)
       const float xi = a.img[c * plane + o];
       float den = sc.c_skip_hat * xi + sc.c_out_hat * net;
-      if (sc.clamp != 0.0f) den = fminf(fmaxf(den, -1.0f), 1.0f);
+      if (sc.clamp != 0.0f) den = clamp_keep_nan(den, -1.0f, 1.0f);
       const float den_d = (1.0f - sc.dpm_gamma) * den + sc.dpm_gamma * nxt_c[c * plane + o];     // :2539 (gamma 0: den)
       a.img[c * plane + o] = sc.dt * xi - sc.half_dt * den_d;                                    // :2541
       nxt_c[c * plane + o] = den;                                                                // old_denoised :2542
@@ -276,7 +276,7 @@ __global__ __launch_bounds__(256) void final_step_edm_kernel(FinalStepArgs a, co
     const float xh = a.img[c * plane + o] + sc.hat_coef * (sc.s_noise * a.noise[c * plane + oz]);     // :2389
     if (edm_pass == 0) {
       float den = sc.c_skip_hat * xh + sc.c_out_hat * net;                     // :2149
-      if (sc.clamp != 0.0f) den = fminf(fmaxf(den, -1.0f), 1.0f);              // :2180-2181
+      if (sc.clamp != 0.0f) den = clamp_keep_nan(den, -1.0f, 1.0f);              // :2180-2181
       const float d = (xh - den) / sc.sigma_hat;                               // :2406
       const float nx = xh + sc.dt * d;                                         // :2407
       if (last) {
@@ -289,7 +289,7 @@ __global__ __launch_bounds__(256) void final_step_edm_kernel(FinalStepArgs a, co
     } else {
       const float nx = nxt_c[c * plane + o], d = d_c[c * plane + o];
       float den = sc.c_skip_next * nx + sc.c_out_next * net;
-      if (sc.clamp != 0.0f) den = fminf(fmaxf(den, -1.0f), 1.0f);
+      if (sc.clamp != 0.0f) den = clamp_keep_nan(den, -1.0f, 1.0f);
       const float d2 = (nx - den) / sc.sigma_next;                             // :2413
       a.img[c * plane + o] = xh + sc.half_dt * (d + d2);                       // :2414
       if (a.x_start) a.x_start[c * plane + o] = d2;                            // :2421-2422
@@ -374,7 +374,7 @@ __global__ void canvas_finish_kernel(const float* __restrict__ img, const ImageD
     const long rem = i - (long)c * hw;
     const int y = (int)(rem / im.W), x = (int)(rem - (long)y * im.W);
     float v = src[((long)c * im.Hp + im.top + y) * im.Wp + im.left + x];
-    v = fminf(fmaxf(v, -1.0f), 1.0f);
+    v = clamp_keep_nan(v, -1.0f, 1.0f);
     dst[i] = (v + 1.0f) * 0.5f;
   }
 }

@@ -70,8 +70,12 @@ def test_misuse_returns_errors_and_engine_stays_usable():
     geo = _lib.SamplerGeometry(H=100, W=300, Hp=512, Wp=768, left=234, top=206, inner_l=128, inner_t=128, inner_r=640, inner_b=384,
                                tile=256, n_even=2, n_odd=1, n_images=1)
     tiles = (C.c_int32 * 4)(0, 0, 0, 256)
-    sc = (_lib.StepScalars * 2)()
-    lsn = (C.c_float * 2)(0.5, -0.5)
+    # the 2-step schedule of the product (all-zero scalars would make the "valid step" below compute x_start = 0 / 0: the sampler's
+    # clamp keeps a NaN as torch.clamp does, so a degenerate schedule is no valid step)
+    from srgd_amd.model import _schedule
+    scalars, log_snrs = _schedule(2)
+    sc = (_lib.StepScalars * 2)(*scalars)
+    lsn = (C.c_float * 2)(*log_snrs)
     cond = torch.zeros(1, 3, 100, 300, device="cuda")
     canvas = torch.zeros(1, 3, 512, 768, device="cuda")
     assert "Padding size" in _err(L, L.srgd_sampler_begin(h, C.byref(geo), C.c_void_p(cond.data_ptr()), C.c_void_p(canvas.data_ptr()),

@@ -31,6 +31,9 @@ def test_halves_carry_22_bits_and_are_exact_on_small_integers():
     big = torch.tensor([1e6, -1e6, 65504.0])                        # beyond f16's range: saturates, stays finite
     hi, lo = halves(big, "f16")
     assert torch.isfinite(hi).all() and torch.isfinite(lo).all() and hi[0] == 65504.0
+    bad = torch.tensor([float("nan"), float("inf"), float("-inf")])  # non-finite: not saturated, NaN in both halves (stays visible)
+    hi, lo = halves(bad, "f16")
+    assert torch.isnan(hi).all() and torch.isnan(lo).all()
 
 
 def test_weight_scale_is_a_power_of_two_that_puts_the_maximum_at_2_10():
