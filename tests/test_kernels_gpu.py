@@ -315,8 +315,9 @@ def test_conv3x3_bf16_integer_exact():
 
 
 @pytest.mark.parametrize("C", [128, 256])
-@pytest.mark.parametrize("cfg", [(1, 16, 16), (2, 32, 64), (1, 128, 128), (3, 8, 8)], ids=lambda s: "B%d_%dx%d" % s)
+@pytest.mark.parametrize("cfg", [(1, 16, 16), (2, 32, 64), (1, 128, 128), (3, 8, 8), (2, 8, 24), (1, 24, 40)], ids=lambda s: "B%d_%dx%d" % s)
 def test_linear_attention_block_fused(cfg, C):
+    # (8x24 = 192 and 24x40 = 960 positions: tile counts that are no power of two - a ragged single strip, a ragged last strip)
     # linattn_fused.hip (C = 128) / linattn_fused256.hip (C = 256): RMSNorm -> qkv -> linear attention -> to_out ->
     # RMSNorm -> + x in two kernels, against the oracle's LinearAttention block on bf16-rounded inputs/weights.
     B, H, W = cfg
