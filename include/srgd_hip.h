@@ -108,6 +108,12 @@ int srgd_finalize_weights(srgd_engine* e); /* fails if any tensor is missing (st
 int srgd_unet_forward(srgd_engine* e, const float* x, const float* cond, const float* log_snr_host, int class_id,
                       float* eps_out, int B, int H, int W, void* stream);
 
+/* srgd_unet_forward with one class label per sample (the reference's [B] class_label, model.py:692-694):
+ * class_ids_host: host [B], each in [0, num_classes).  Sample b comes out bit-identical to srgd_unet_forward of the same
+ * batch with class_id = class_ids_host[b].  Errors: a label out of range; a U-Net without a class embedding. */
+int srgd_unet_forward_labels(srgd_engine* e, const float* x, const float* cond, const float* log_snr_host,
+                             const int32_t* class_ids_host, float* eps_out, int B, int H, int W, void* stream);
+
 /* ---- tiled sampler --------------------------------------------------------------------------
  * replaces: ConditionalContinuousTimeGaussianDiffusionSR.tiled_sample (model.py:3288-3413) and,
  * per step, p_sample / p_mean_variance (model.py:3122-3188) and q_sample (model.py:3434-3447). */
@@ -163,6 +169,16 @@ typedef struct srgd_sampler_image {
 int srgd_sampler_begin_images(srgd_engine* e, int tile, int n_images, const srgd_sampler_image* images, const float* cond01,
                               float* cond_canvas, const int32_t* tiles_even_host, const int32_t* tiles_odd_host, int n_steps,
                               const srgd_step_scalars* scalars_host, const float* log_snr_host, int class_id, void* stream);
+
+/* Gives the images of a begun run their own class labels: class_ids_host is host [n_images], each in [0, num_classes),
+ * in the image order of the begin.  Valid after srgd_sampler_begin, srgd_sampler_begin_images or srgd_edm_begin and before the
+ * run's first step (srgd_sampler_q_start may come before or after); it replaces the begin's class_id.  The conditioning table
+ * is rebuilt with K + 1 rows per time value for the K distinct labels (label k's rows exactly as a run with that label alone
+ * computes them, then the no-label row), and every tile of a step reads the row of its image: each image comes out
+ * bit-identical to a run of its own with its own label, under class guidance and condition guidance alike.
+ * Errors (< 0, nothing launched): no begun run; n_images different from the run's; a label < 0 or >= num_classes
+ * ("class label out of range"); a U-Net without a class embedding; a call after the first step. */
+int srgd_sampler_image_labels(srgd_engine* e, const int32_t* class_ids_host, int n_images, void* stream);
 
 /* One denoising step over every tile of grid (step % 2), `sub_batch` tiles per U-Net launch
  * (the reference's --batch_size; results do not depend on it).

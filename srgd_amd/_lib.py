@@ -68,6 +68,9 @@ PROTOTYPES = {
     "srgd_finalize_weights": (C.c_int, [C.c_void_p]),
     "srgd_unet_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_void_p,
                                     C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "srgd_unet_forward_labels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int32),
+                                           C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "srgd_sampler_image_labels": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_void_p]),
     "srgd_sampler_begin": (C.c_int, [C.c_void_p, C.POINTER(SamplerGeometry), C.c_void_p, C.c_void_p,
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.POINTER(StepScalars),
                                      C.POINTER(C.c_float), C.c_int, C.c_void_p]),

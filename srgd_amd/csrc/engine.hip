@@ -86,10 +86,24 @@ __global__ void fill_rows_kernel(int* rows, int n, int split, int v0, int v1) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < n) rows[i] = (i < split) ? v0 : v1;
 }
+// Per-image labels: batch row i of a launch is pass i / nt of tile first + i % nt.  The tile's image (third int of its
+// tile-list record, the index TileBatch addresses ImageDesc with) selects the image's label slot; pass 1 takes null_row
+// under class guidance (null_row >= 0) and the label row otherwise.  base: row offset of the evaluation inside a step.
+__global__ void fill_rows_labels_kernel(int* rows, int n, int nt, const int* tile_yx, int first, const int* slots, int base,
+                                        int null_row) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int pass = i / nt, image = tile_yx[3 * (first + (i - pass * nt)) + 2];
+  rows[i] = base + ((pass == 1 && null_row >= 0) ? null_row : slots[image]);
+}
 __global__ void set_step_kernel(int* step, int v) { *step = v; }
 __global__ void rows_api_kernel(int* rows, int n, int odd) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < n) rows[i] = 2 * i + odd;
+}
+__global__ void rows_api_labels_kernel(int* rows, int n, int stride, const int* slots) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) rows[i] = stride * i + slots[i];
 }
 
 
@@ -212,7 +226,8 @@ struct Pool {
 
 struct CondTable {
   float* table = nullptr;   // [rows][ss_stride]
-  int rows_cap = 0;
+  int rows_cap = 0;          // time values the buffers hold ...
+  int labels_cap = 0;        // ... at this many label rows per time value (+ the null row)
   float *ls = nullptr, *feat = nullptr, *h1 = nullptr, *t1 = nullptr, *trows = nullptr, *c1 = nullptr, *c2 = nullptr;
 };
 
@@ -307,6 +322,14 @@ struct srgd_engine {
   StepScalars* d_sc = nullptr; int sc_cap = 0;
   int n_steps = 0, run_class = -1;
   bool run_active = false;
+  // per-image labels (srgd_sampler_image_labels): the run's K distinct labels own rows 0..K-1 of every time value's K + 1
+  // conditioning rows (row K: no label); d_slots[image] is the image's row.  K = 1 without the call: rows (label | none).
+  int n_labels = 1;
+  bool run_labels = false, run_stepped = false;
+  std::vector<float> run_times;           // the run's "time" inputs, kept to rebuild the table for other labels
+  int* d_slots = nullptr; size_t slots_cap = 0;
+  int* d_slots_api = nullptr; size_t slots_api_cap = 0;   // srgd_unet_forward_labels: label row of each sample
+  std::vector<int> slots_host, slots_api_host;            // sources of the uploads (alive until the next one)
   float* rng_tiles = nullptr; size_t rng_tiles_cap = 0;
   EdmScalars* d_edm = nullptr; int edm_cap = 0; bool run_is_edm = false;
   float* rng_canvas = nullptr; size_t rng_canvas_cap = 0;
@@ -1139,41 +1162,82 @@ int unet_body(Ctx& x, void* x0, void** out) {
   return 0;
 }
 
-// Conditioning table: rows 2i (with class embedding if class_id >= 0) and 2i+1 (without) for
-// every log-SNR value i; columns = concatenated per-ResnetBlock (scale | shift) vectors.
-int compute_conditioning(srgd_engine* e, CondTable& ct, const float* ls_host, int n, int class_id, hipStream_t st) {
+// Conditioning table: K + 1 rows for every log-SNR value i - row i*(K+1) + k carries the class embedding of class_ids[k],
+// row i*(K+1) + K none; columns = concatenated per-ResnetBlock (scale | shift) vectors.  K = 1 is the one-label layout
+// (rows 2i, 2i+1; class_ids[0] < 0: no label, both rows alike).  Every label's rows come from the launches a run with
+// that label alone makes, so they hold the same bits.
+int compute_conditioning(srgd_engine* e, CondTable& ct, const float* ls_host, int n, const int* class_ids, int K, hipStream_t st) {
   Prof p(e, KC_COND, st);
   const int td = e->time_dim, half = e->cfg.sinus_dim / 2, nf = e->cfg.sinus_dim + 1;
-  if (class_id >= e->cfg.num_classes) SRGD_FAIL("class label out of range");
-  if (n > ct.rows_cap) {
+  if (K < 1) SRGD_FAIL("internal: conditioning table without a label row");
+  for (int k = 0; k < K; ++k) {
+    if (class_ids[k] >= e->cfg.num_classes) SRGD_FAIL("class label out of range");
+    if (class_ids[k] < 0 && K > 1) SRGD_FAIL("class label out of range");
+  }
+  const int K1 = K + 1;
+  if (n > ct.rows_cap || K > ct.labels_cap) {
+    const int nc = std::max(n, ct.rows_cap), kc = std::max(K, ct.labels_cap);
     for (float** q : {&ct.table, &ct.ls, &ct.feat, &ct.h1, &ct.t1, &ct.trows, &ct.c1, &ct.c2})
       if (*q) { hipFree(*q); *q = nullptr; }
-    SRGD_HIP(hipMalloc((void**)&ct.table, (size_t)2 * n * e->ss_stride * 4));
-    SRGD_HIP(hipMalloc((void**)&ct.ls, (size_t)n * 4));
-    SRGD_HIP(hipMalloc((void**)&ct.feat, (size_t)n * nf * 4));
-    SRGD_HIP(hipMalloc((void**)&ct.h1, (size_t)n * td * 4));
-    SRGD_HIP(hipMalloc((void**)&ct.trows, (size_t)2 * n * td * 4));
+    ct.rows_cap = ct.labels_cap = 0;
+    SRGD_HIP(hipMalloc((void**)&ct.table, (size_t)(kc + 1) * nc * e->ss_stride * 4));
+    SRGD_HIP(hipMalloc((void**)&ct.ls, (size_t)nc * 4));
+    SRGD_HIP(hipMalloc((void**)&ct.feat, (size_t)nc * nf * 4));
+    SRGD_HIP(hipMalloc((void**)&ct.h1, (size_t)nc * td * 4));
+    SRGD_HIP(hipMalloc((void**)&ct.trows, (size_t)(kc + 1) * nc * td * 4));
     SRGD_HIP(hipMalloc((void**)&ct.c1, (size_t)td * 4));
     SRGD_HIP(hipMalloc((void**)&ct.c2, (size_t)td * 4));
-    ct.rows_cap = n;
+    ct.rows_cap = nc;
+    ct.labels_cap = kc;
   }
   SRGD_HIP(hipMemcpyAsync(ct.ls, ls_host, (size_t)n * 4, hipMemcpyHostToDevice, st));
   SRGD_TRY(time_features(ct.ls, e->sin_w, half, n, ct.feat, st));
   SRGD_TRY(linear_rows(ct.feat, nf, e->time1.w, e->time1.b, ct.h1, td, n, nf, td, ACT_GELU, nullptr, 0, st));
-  // rows 2i+1: t ; rows 2i: t + class embedding
-  SRGD_TRY(linear_rows(ct.h1, td, e->time3.w, e->time3.b, ct.trows + td, 2 * td, n, td, td, ACT_NONE, nullptr, 0, st));
-  if (class_id >= 0) {
-    SRGD_TRY(linear_rows(e->cls_emb + (size_t)class_id * e->dim, e->dim, e->cls1.w, e->cls1.b, ct.c1, td, 1, e->dim, td,
-                         ACT_GELU, nullptr, 0, st));
-    SRGD_TRY(linear_rows(ct.c1, td, e->cls3.w, e->cls3.b, ct.c2, td, 1, td, td, ACT_NONE, nullptr, 0, st));
-    SRGD_TRY(linear_rows(ct.h1, td, e->time3.w, e->time3.b, ct.trows, 2 * td, n, td, td, ACT_NONE, ct.c2, 0, st));
-  } else {
-    SRGD_TRY(linear_rows(ct.h1, td, e->time3.w, e->time3.b, ct.trows, 2 * td, n, td, td, ACT_NONE, nullptr, 0, st));
+  // rows i*K1 + K: t ; rows i*K1 + k: t + class embedding k
+  SRGD_TRY(linear_rows(ct.h1, td, e->time3.w, e->time3.b, ct.trows + (size_t)K * td, K1 * td, n, td, td, ACT_NONE, nullptr, 0, st));
+  for (int k = 0; k < K; ++k) {
+    float* rows_k = ct.trows + (size_t)k * td;
+    if (class_ids[k] >= 0) {
+      SRGD_TRY(linear_rows(e->cls_emb + (size_t)class_ids[k] * e->dim, e->dim, e->cls1.w, e->cls1.b, ct.c1, td, 1, e->dim, td,
+                           ACT_GELU, nullptr, 0, st));
+      SRGD_TRY(linear_rows(ct.c1, td, e->cls3.w, e->cls3.b, ct.c2, td, 1, td, td, ACT_NONE, nullptr, 0, st));
+      SRGD_TRY(linear_rows(ct.h1, td, e->time3.w, e->time3.b, rows_k, K1 * td, n, td, td, ACT_NONE, ct.c2, 0, st));
+    } else {
+      SRGD_TRY(linear_rows(ct.h1, td, e->time3.w, e->time3.b, rows_k, K1 * td, n, td, td, ACT_NONE, nullptr, 0, st));
+    }
   }
   for (ResW* r : e->all_rb)
-    SRGD_TRY(linear_rows(ct.trows, td, r->mlp.w, r->mlp.b, ct.table + r->ss_offset, e->ss_stride, 2 * n, td, 2 * r->Cout,
+    SRGD_TRY(linear_rows(ct.trows, td, r->mlp.w, r->mlp.b, ct.table + r->ss_offset, e->ss_stride, K1 * n, td, 2 * r->Cout,
                          ACT_SILU_IN, nullptr, 0, st));
   return 0;
+}
+
+// The distinct labels of ids[0..n) in order of first appearance, and each entry's index among them
+int label_slots(const srgd_engine* e, const int32_t* ids, int n, std::vector<int>& labels, std::vector<int>& slots) {
+  labels.clear();
+  slots.resize(n);
+  for (int i = 0; i < n; ++i) {
+    if (ids[i] < 0 || ids[i] >= e->cfg.num_classes) SRGD_FAIL("class label out of range");
+    const auto it = std::find(labels.begin(), labels.end(), (int)ids[i]);
+    slots[i] = (int)(it - labels.begin());
+    if (it == labels.end()) labels.push_back(ids[i]);
+  }
+  return 0;
+}
+
+// Conditioning rows of one U-Net launch of a sampler step: evaluation `ev` of the step (EDM: 0 at sigma_hat, 1 at sigma_next),
+// entries [0, nt) = pass 0, [nt, nb) = pass 1 (the null row under class guidance).  The step's own rows are added on the
+// device (Ctx::step_mul).
+void launch_step_rows(srgd_engine* e, int nb, int nt, const int* tiles, int first, int ev, bool pass1_null, hipStream_t st) {
+  if (e->run_labels) {
+    const int K = e->n_labels;
+    hipLaunchKernelGGL(fill_rows_labels_kernel, dim3(cdiv(nb, 256)), dim3(256), 0, st, e->d_rows, nb, nt, tiles, first,
+                       e->d_slots, ev * (K + 1), pass1_null ? K : -1);
+    return;
+  }
+  const int row_label = e->run_class >= 0 ? 0 : 1, row_null = 1;
+  hipLaunchKernelGGL(fill_rows_kernel, dim3(cdiv(nb, 256)), dim3(256), 0, st, e->d_rows, nb, nt, 2 * ev + row_label,
+                     2 * ev + (pass1_null ? row_null : row_label));
 }
 
 }  // namespace
@@ -1264,7 +1328,7 @@ int srgd_destroy(srgd_engine* e) {
   e->pool.release_all();
   for (void* p : {(void*)e->gn_partial, (void*)e->coefA, (void*)e->la_ws, (void*)e->d_rows,
                   (void*)e->d_tiles_even, (void*)e->d_tiles_odd, (void*)e->d_sc, (void*)e->d_edm, (void*)e->rng_tiles,
-                  (void*)e->rng_canvas, (void*)e->d_images})
+                  (void*)e->rng_canvas, (void*)e->d_images, (void*)e->d_slots, (void*)e->d_slots_api})
     if (p) hipFree(p);
   for (CondTable* ct : {&e->ct_sampler, &e->ct_api})
     for (float* q : {ct->table, ct->ls, ct->feat, ct->h1, ct->t1, ct->trows, ct->c1, ct->c2})
@@ -1439,16 +1503,9 @@ int srgd_finalize_weights(srgd_engine* e) {
   return 0;
 }
 
-int srgd_unet_forward(srgd_engine* e, const float* xin, const float* cond, const float* log_snr_host, int class_id,
-                      float* eps_out, int B, int H, int W, void* stream) {
-  if (!e || !e->finalized) SRGD_FAIL("srgd_unet_forward: engine has no weights");
-  if (class_id >= 0 && e->cfg.num_classes <= 0) SRGD_FAIL("class label given but the U-Net has no class embedding");
-  hipStream_t st = (hipStream_t)stream;
-  SRGD_HIP(hipSetDevice(e->cfg.device));
-  e->pool.reset_busy();
-  SRGD_TRY(ensure_scratch(e, B, H, W));
-  SRGD_TRY(compute_conditioning(e, e->ct_api, log_snr_host, B, class_id, st));
-  hipLaunchKernelGGL(rows_api_kernel, dim3(cdiv(B, 256)), dim3(256), 0, st, e->d_rows, B, class_id >= 0 ? 0 : 1);
+// the U-Net evaluation of the forward entries once ct_api and d_rows are set
+static int unet_forward_with_rows(srgd_engine* e, const float* xin, const float* cond, float* eps_out, int B, int H, int W,
+                                  hipStream_t st) {
   void* x0 = e->pool.get((size_t)B * H * W * e->dim * e->es);
   if (!x0) return -1;
   {
@@ -1466,6 +1523,38 @@ int srgd_unet_forward(srgd_engine* e, const float* xin, const float* cond, const
   e->pool.put(act);
   e->pool.put(x0);
   return 0;
+}
+
+int srgd_unet_forward(srgd_engine* e, const float* xin, const float* cond, const float* log_snr_host, int class_id,
+                      float* eps_out, int B, int H, int W, void* stream) {
+  if (!e || !e->finalized) SRGD_FAIL("srgd_unet_forward: engine has no weights");
+  if (class_id >= 0 && e->cfg.num_classes <= 0) SRGD_FAIL("class label given but the U-Net has no class embedding");
+  hipStream_t st = (hipStream_t)stream;
+  SRGD_HIP(hipSetDevice(e->cfg.device));
+  e->pool.reset_busy();
+  SRGD_TRY(ensure_scratch(e, B, H, W));
+  SRGD_TRY(compute_conditioning(e, e->ct_api, log_snr_host, B, &class_id, 1, st));
+  hipLaunchKernelGGL(rows_api_kernel, dim3(cdiv(B, 256)), dim3(256), 0, st, e->d_rows, B, class_id >= 0 ? 0 : 1);
+  return unet_forward_with_rows(e, xin, cond, eps_out, B, H, W, st);
+}
+
+int srgd_unet_forward_labels(srgd_engine* e, const float* xin, const float* cond, const float* log_snr_host,
+                             const int32_t* class_ids_host, float* eps_out, int B, int H, int W, void* stream) {
+  if (!e || !e->finalized) SRGD_FAIL("srgd_unet_forward_labels: engine has no weights");
+  if (!class_ids_host || B < 1) SRGD_FAIL("srgd_unet_forward_labels: null argument");
+  if (e->cfg.num_classes <= 0) SRGD_FAIL("class label given but the U-Net has no class embedding");
+  std::vector<int> labels;
+  SRGD_TRY(label_slots(e, class_ids_host, B, labels, e->slots_api_host));
+  const int K = (int)labels.size();
+  hipStream_t st = (hipStream_t)stream;
+  SRGD_HIP(hipSetDevice(e->cfg.device));
+  e->pool.reset_busy();
+  SRGD_TRY(ensure_scratch(e, B, H, W));
+  SRGD_TRY(ensure(e, &e->d_slots_api, &e->slots_api_cap, (size_t)B));
+  SRGD_HIP(hipMemcpyAsync(e->d_slots_api, e->slots_api_host.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
+  SRGD_TRY(compute_conditioning(e, e->ct_api, log_snr_host, B, labels.data(), K, st));
+  hipLaunchKernelGGL(rows_api_labels_kernel, dim3(cdiv(B, 256)), dim3(256), 0, st, e->d_rows, B, K + 1, e->d_slots_api);
+  return unet_forward_with_rows(e, xin, cond, eps_out, B, H, W, st);
 }
 
 // one image of a run as the begin entries receive it: its geometry, its two tile grids (host [n][2] = (y, x)) and its noise class
@@ -1536,6 +1625,9 @@ static int sampler_begin_common(srgd_engine* e, int tile, const std::vector<Imag
   drop_step_graphs(e);                       // graphs bake in canvas / table / tile-list pointers of one run
   e->n_steps = n_steps;
   e->run_class = class_id;
+  e->n_labels = 1;
+  e->run_labels = e->run_stepped = false;
+  e->run_times.assign(times_host, times_host + n_times);
   e->images = recs;
   e->classes = classes;
   e->class_canvas_elems = (size_t)cnoise_off;
@@ -1553,7 +1645,7 @@ static int sampler_begin_common(srgd_engine* e, int tile, const std::vector<Imag
   SRGD_HIP(hipMemcpyAsync(e->d_images, recs.data(), recs.size() * sizeof(ImageDesc), hipMemcpyHostToDevice, st));
   { Prof p(e, KC_CANVAS, st);
     SRGD_TRY(canvas_prepare_cond(cond01, e->d_images, (int)recs.size(), max_canvas, cond_canvas, st)); }
-  SRGD_TRY(compute_conditioning(e, e->ct_sampler, times_host, n_times, class_id, st));
+  SRGD_TRY(compute_conditioning(e, e->ct_sampler, times_host, n_times, &class_id, 1, st));
   // the host arrays (ours and the caller's) may be reused right after this returns
   SRGD_HIP(hipStreamSynchronize(st));
   return 0;
@@ -1649,6 +1741,28 @@ int srgd_edm_begin(srgd_engine* e, const srgd_sampler_geometry* g, const float* 
   return 0;
 }
 
+int srgd_sampler_image_labels(srgd_engine* e, const int32_t* class_ids_host, int n_images, void* stream) {
+  if (!e || !e->run_active) SRGD_FAIL("srgd_sampler_image_labels: call srgd_sampler_begin, srgd_sampler_begin_images or srgd_edm_begin first");
+  if (!class_ids_host) SRGD_FAIL("srgd_sampler_image_labels: null argument");
+  if (e->cfg.num_classes <= 0) SRGD_FAIL("class label given but the U-Net has no class embedding");
+  if (n_images != (int)e->images.size()) SRGD_FAIL("srgd_sampler_image_labels: one label per image of the run");
+  if (e->run_stepped) SRGD_FAIL("srgd_sampler_image_labels: the run has taken a step (labels are set before the first)");
+  std::vector<int> labels, slots;
+  SRGD_TRY(label_slots(e, class_ids_host, n_images, labels, slots));
+  hipStream_t st = (hipStream_t)stream;
+  SRGD_HIP(hipSetDevice(e->cfg.device));
+  drop_step_graphs(e);                       // graphs bake in the table pointer and the rows per step
+  SRGD_TRY(ensure(e, &e->d_slots, &e->slots_cap, (size_t)n_images));
+  e->slots_host = slots;
+  SRGD_HIP(hipMemcpyAsync(e->d_slots, e->slots_host.data(), (size_t)n_images * sizeof(int), hipMemcpyHostToDevice, st));
+  SRGD_TRY(compute_conditioning(e, e->ct_sampler, e->run_times.data(), (int)e->run_times.size(), labels.data(), (int)labels.size(), st));
+  e->n_labels = (int)labels.size();
+  e->run_labels = true;
+  e->run_class = labels[0];
+  SRGD_HIP(hipStreamSynchronize(st));
+  return 0;
+}
+
 // all launches of one EDM step (model.py:2377-2455); step-dependent values come through e->d_step
 static int edm_step_launch(srgd_engine* e, bool last, int parity, int tile_first, int tile_count, bool ring, float* img,
                            const float* cond_canvas, float* x_start, float* work, const float* noise_canvas,
@@ -1665,7 +1779,6 @@ static int edm_step_launch(srgd_engine* e, bool last, int parity, int tile_first
     SRGD_TRY(philox_normal(e->rng_tiles, canvas1, seed, 2ull << 32, e->d_step, st));
     z = e->rng_tiles;
   }
-  const int row_label = e->run_class >= 0 ? 0 : 1, row_null = 1;
   const int mask = (passes == 2 && guidance_kind == 2) ? 0x1 : 0x3;
   for (int first = tile_first; first < n; first += sub_batch) {
     const int nt = std::min(sub_batch, n - first);
@@ -1683,10 +1796,10 @@ static int edm_step_launch(srgd_engine* e, bool last, int parity, int tile_first
         SRGD_TRY(run_init7(e, padded, nb, g.tile, g.tile, x0, st));
         e->pool.put(padded);
       }
-      // conditioning row = base + 4 * step, base = 2 * (evaluation: 0 at sigma_hat, 1 at sigma_next) + (0 label / 1 none)
-      hipLaunchKernelGGL(fill_rows_kernel, dim3(cdiv(nb, 256)), dim3(256), 0, st, e->d_rows, nb, nt, 2 * ep + row_label,
-                         2 * ep + ((passes == 2 && guidance_kind == 1) ? row_null : row_label));
-      Ctx x{e, nb, g.tile, g.tile, e->d_rows, e->ct_sampler.table, st, e->d_step, 4};
+      // conditioning row = base + 2(K+1) * step, base = (K+1) * (evaluation: 0 at sigma_hat, 1 at sigma_next) + (label row / K: none);
+      // K = 1 unless the run has per-image labels
+      launch_step_rows(e, nb, nt, tiles, first, ep, passes == 2 && guidance_kind == 1, st);
+      Ctx x{e, nb, g.tile, g.tile, e->d_rows, e->ct_sampler.table, st, e->d_step, 2 * (e->n_labels + 1)};
       void* act = nullptr;
       float* eps4 = final_fusion_possible(e) ? (float*)e->pool.get((size_t)nb * g.tile * g.tile * 16) : nullptr;
       if (final_fusion_possible(e) && !eps4) return -1;
@@ -1746,6 +1859,7 @@ int srgd_edm_step_tiles(srgd_engine* e, int step, int tile_first, int tile_count
   if (tile_count < 0) tile_count = n - tile_first;
   if (tile_first < 0 || tile_count < 0 || tile_first + tile_count > n) SRGD_FAIL("srgd_edm_step_tiles: tile range outside the grid");
   const bool ring = do_ring != 0;
+  e->run_stepped = true;
   sub_batch = std::max(1, std::min(sub_batch, std::max(tile_count, 1)));
   // balanced launches: the same number of U-Net launches, but of (almost) equal size - 1,089 tiles at a limit of 125 run as
   // 9 x 121, not 8 x 125 + 89, and a rank's 137-tile slice of a sharded canvas as 69 + 68, not 125 + 12 (a 12-tile launch
@@ -1796,8 +1910,8 @@ int srgd_edm_dpmpp_step(srgd_engine* e, int step, float* img, const float* cond_
   SRGD_TRY(ensure_scratch(e, sub_batch * passes, g.tile, g.tile));
   if (!e->d_step) SRGD_HIP(hipMalloc((void**)&e->d_step, sizeof(int)));
   hipLaunchKernelGGL(set_step_kernel, dim3(1), dim3(1), 0, st, e->d_step, step);
-  const int row_label = e->run_class >= 0 ? 0 : 1, row_null = 1;
   const int mask = (passes == 2 && guidance_kind == 2) ? 0x1 : 0x3;
+  e->run_stepped = true;
   for (int first = 0; first < n; first += sub_batch) {
     const int nt = std::min(sub_batch, n - first);
     const int nb = nt * passes;
@@ -1814,9 +1928,8 @@ int srgd_edm_dpmpp_step(srgd_engine* e, int step, float* img, const float* cond_
       e->pool.put(padded);
     }
     // conditioning rows of evaluation 0 (c_noise at sigma_i), as in edm_step_launch
-    hipLaunchKernelGGL(fill_rows_kernel, dim3(cdiv(nb, 256)), dim3(256), 0, st, e->d_rows, nb, nt, row_label,
-                       (passes == 2 && guidance_kind == 1) ? row_null : row_label);
-    Ctx x{e, nb, g.tile, g.tile, e->d_rows, e->ct_sampler.table, st, e->d_step, 4};
+    launch_step_rows(e, nb, nt, tiles, first, 0, passes == 2 && guidance_kind == 1, st);
+    Ctx x{e, nb, g.tile, g.tile, e->d_rows, e->ct_sampler.table, st, e->d_step, 2 * (e->n_labels + 1)};
     void* act = nullptr;
     float* eps4 = final_fusion_possible(e) ? (float*)e->pool.get((size_t)nb * g.tile * g.tile * 16) : nullptr;
     if (final_fusion_possible(e) && !eps4) return -1;
@@ -1854,8 +1967,6 @@ static int sampler_step_launch(srgd_engine* e, bool last, int parity, int tile_f
       nz = e->rng_tiles;
     }
   }
-  const int row_label = e->run_class >= 0 ? 0 : 1;       // + 2 * step inside gn_finalize
-  const int row_null = 1;
   for (int first = tile_first; first < n; first += sub_batch) {
     const int nt = std::min(sub_batch, n - first);
     const int nb = nt * passes;
@@ -1871,9 +1982,8 @@ static int sampler_step_launch(srgd_engine* e, bool last, int parity, int tile_f
       SRGD_TRY(run_init7(e, padded, nb, g.tile, g.tile, x0, st));
       e->pool.put(padded);
     }
-    hipLaunchKernelGGL(fill_rows_kernel, dim3(cdiv(nb, 256)), dim3(256), 0, st, e->d_rows, nb, nt, row_label,
-                       (passes == 2 && guidance_kind == 1) ? row_null : row_label);
-    Ctx x{e, nb, g.tile, g.tile, e->d_rows, e->ct_sampler.table, st, e->d_step};
+    launch_step_rows(e, nb, nt, tiles, first, 0, passes == 2 && guidance_kind == 1, st);   // + (K+1) * step inside gn_finalize
+    Ctx x{e, nb, g.tile, g.tile, e->d_rows, e->ct_sampler.table, st, e->d_step, e->n_labels + 1};
     void* act = nullptr;
     float* eps4 = final_fusion_possible(e) ? (float*)e->pool.get((size_t)nb * g.tile * g.tile * 16) : nullptr;
     if (final_fusion_possible(e) && !eps4) return -1;
@@ -1943,6 +2053,7 @@ int srgd_sampler_step_tiles(srgd_engine* e, int step, int tile_first, int tile_c
   if (tile_count < 0) tile_count = n - tile_first;
   if (tile_first < 0 || tile_count < 0 || tile_first + tile_count > n) SRGD_FAIL("srgd_sampler_step_tiles: tile range outside the grid");
   const bool ring = do_ring != 0;
+  e->run_stepped = true;
   sub_batch = std::max(1, std::min(sub_batch, std::max(tile_count, 1)));
   // balanced launches: the same number of U-Net launches, but of (almost) equal size - 1,089 tiles at a limit of 125 run as
   // 9 x 121, not 8 x 125 + 89, and a rank's 137-tile slice of a sharded canvas as 69 + 68, not 125 + 12 (a 12-tile launch

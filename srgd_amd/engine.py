@@ -111,6 +111,22 @@ class HipEngine:
                                             _dev_ptr(out), b, h, w, _stream_ptr(self.device)), "srgd_unet_forward")
         return out
 
+    def unet_forward_labels(self, x: torch.Tensor, log_snr: torch.Tensor, class_ids: Sequence[int],
+                            cond: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``unet_forward`` with one class label per sample (srgd_unet_forward_labels)."""
+        b, c, h, w = x.shape
+        x = x.contiguous().float()
+        cond = None if cond is None else cond.contiguous().float()
+        ls = log_snr.detach().to("cpu", torch.float32).contiguous()
+        assert ls.numel() == b and len(class_ids) == b
+        ids = (C.c_int32 * b)(*[int(v) for v in class_ids])
+        out = torch.empty_like(x)
+        with torch.cuda.device(self.device):
+            check(self._L.srgd_unet_forward_labels(self._h, _dev_ptr(x), _dev_ptr(cond),
+                                                   C.cast(C.c_void_p(ls.data_ptr()), C.POINTER(C.c_float)), ids,
+                                                   _dev_ptr(out), b, h, w, _stream_ptr(self.device)), "srgd_unet_forward_labels")
+        return out
+
     # ---------------------------------------------------------------- tiled sampler
     def sampler_begin(self, geo: SamplerGeometry, cond01: torch.Tensor, cond_canvas: torch.Tensor,
                       tiles_even: Sequence[Tuple[int, int]], tiles_odd: Sequence[Tuple[int, int]],
@@ -138,6 +154,13 @@ class HipEngine:
             check(self._L.srgd_sampler_begin_images(self._h, int(tile), len(images), im, _dev_ptr(cond01), _dev_ptr(cond_canvas),
                                                     te, to, n, sc, ls, int(class_id), _stream_ptr(self.device)),
                   "srgd_sampler_begin_images")
+
+    def sampler_image_labels(self, class_ids: Sequence[int]) -> None:
+        """One class label per image of the begun run (DDPM, mixed-size or EDM), before its first step."""
+        ids = (C.c_int32 * len(class_ids))(*[int(v) for v in class_ids])
+        with torch.cuda.device(self.device):
+            check(self._L.srgd_sampler_image_labels(self._h, ids, len(class_ids), _stream_ptr(self.device)),
+                  "srgd_sampler_image_labels")
 
     def sampler_step(self, step: int, img: torch.Tensor, cond_canvas: torch.Tensor, x_start: Optional[torch.Tensor],
                      noise_tiles: Optional[torch.Tensor], noise_canvas: Optional[torch.Tensor], passes: int,

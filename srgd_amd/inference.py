@@ -63,7 +63,59 @@ def parse_args(argv=None):
     group.add_argument("--lockstep_tiles", type=int, default=None, metavar="T",
                        help="sample consecutive images of ANY size together, up to T tiles per even step (an image larger "
                             "than T runs alone); every image comes out bit-identical to its solo run (DDPM configs only)")
-    return p.parse_args(argv)
+    p.add_argument("--label_file", type=str, default=None, metavar="PATH",
+                   help="text file of `file_name label` lines: the images of --input_dir named there are sampled with that class "
+                        "label, the others with --test_label; lock-step groups may mix labels (engine extension)")
+    args = p.parse_args(argv)
+    args.labels = None
+    if args.label_file is not None:
+        args.labels = parse_label_file(args.label_file, args.input_dir, load_config(args.conf).num_classes)
+    return args
+
+
+def parse_label_file(path, input_dir, num_classes):
+    """``--label_file``: ``{file name: label}`` from lines of ``file_name label`` (blank lines and ``#`` comments skipped).
+    Every name must be a file of ``input_dir`` and every label an integer in ``[0, num_classes)``; anything else ends the
+    run here (``SystemExit``), before the model is built."""
+    try:
+        with open(path) as f:
+            lines = f.read().splitlines()
+    except OSError as err:
+        raise SystemExit(f"--label_file: cannot read {path}: {err}")
+    if not num_classes:
+        raise SystemExit("--label_file: the configured U-Net has no class embedding (num_classes is not set)")
+    present = {os.path.basename(f) for f in glob.glob(f"{input_dir}/*")}
+    labels = {}
+    for no, line in enumerate(lines, 1):
+        line = line.split("#", 1)[0].strip()
+        if not line:
+            continue
+        parts = line.rsplit(None, 1)
+        if len(parts) != 2:
+            raise SystemExit(f"--label_file {path}:{no}: expected `file_name label`")
+        name, text = parts[0].strip(), parts[1]
+        try:
+            label = int(text)
+        except ValueError:
+            raise SystemExit(f"--label_file {path}:{no}: label {text!r} is not an integer")
+        if not 0 <= label < num_classes:
+            raise SystemExit(f"--label_file {path}:{no}: label {label} outside [0, {num_classes})")
+        if name not in present:
+            raise SystemExit(f"--label_file {path}:{no}: {name!r} is not a file of {input_dir}")
+        labels[name] = label
+    return labels
+
+
+def _label_tensor(test_label, n_images, device):
+    """``test_label``: None, one label for all images (the reference's ``[1]`` tensor) or a sequence of one per image."""
+    if test_label is None:
+        return None
+    if isinstance(test_label, (list, tuple)):
+        assert len(test_label) == n_images, "one label per lock-step image"
+        ids = list(test_label) if len(set(test_label)) > 1 else [test_label[0]]
+    else:
+        ids = [test_label]
+    return torch.LongTensor(ids).to(device)
 
 
 def seed_everything(seed):
@@ -152,11 +204,12 @@ def sr_target_images(images, sr_model, scale=4, batch_size=8, test_label=2, cond
                      num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71):
     """``sr_target_image`` for several same-sized images in lock-step (engine extension): one ``tiled_sample`` call on a
     ``[B,3,H,W]`` condition.  Each image is sampled exactly as it would be alone after the reference's per-image
-    ``seed_everything(seed)`` (inference.py:73) - bit-identical outputs - while their tiles fill the U-Net launches."""
+    ``seed_everything(seed)`` (inference.py:73) - bit-identical outputs - while their tiles fill the U-Net launches.
+    ``test_label`` may be a sequence of one label per image."""
     assert len({im.size for im in images}) == 1, "lock-step images must have the same size"
     width, height = images[0].size
     condition_x = torch.cat([upsample_bicubic_on_device(im, scale, sr_model.device) for im in images], 0)
-    label = torch.LongTensor([test_label]).to(sr_model.device) if test_label is not None else None
+    label = _label_tensor(test_label, len(images), sr_model.device)
     seed_everything(seed)
     sr_model.device_noise_seed = seed
     with torch.inference_mode():
@@ -175,9 +228,10 @@ def sr_target_images_mixed(images, sr_model, scale=4, batch_size=8, test_label=2
                            class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0,
                            num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71):
     """``sr_target_image`` for several images of any sizes in lock-step (engine extension): one ``tiled_sample`` call on a list
-    of conditions.  Each image comes out bit-identical to its own ``sr_target_image`` run."""
+    of conditions.  Each image comes out bit-identical to its own ``sr_target_image`` run (with its own label where
+    ``test_label`` is a sequence of one label per image)."""
     conds = [upsample_bicubic_on_device(im, scale, sr_model.device) for im in images]
-    label = torch.LongTensor([test_label]).to(sr_model.device) if test_label is not None else None
+    label = _label_tensor(test_label, len(images), sr_model.device)
     seed_everything(seed)
     sr_model.device_noise_seed = seed
     with torch.inference_mode():
@@ -202,34 +256,38 @@ def try_open_image(image_path):
 def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=8, test_label=2, cond_scale=1.0,
                            guidance_start_steps=0, class_cond_scale=1.0, class_guidance_start_steps=0,
                            generation_start_steps=0, num_sample_steps=250, start_index=0, end_index=None,
-                           enable_amp=False, interpolation="bicubic", seed=71, lockstep=1, lockstep_tiles=None):
+                           enable_amp=False, interpolation="bicubic", seed=71, lockstep=1, lockstep_tiles=None, labels=None):
     """``lockstep``: groups of up to N consecutive same-sized images; ``lockstep_tiles``: groups of consecutive images of any
-    size up to that many tiles per even step (srgd_amd.lockstep.plan_lockstep_groups)."""
+    size up to that many tiles per even step (srgd_amd.lockstep.plan_lockstep_groups).  ``labels``: ``{file name: label}``
+    (``--label_file``) for the images that do not take ``test_label``; a group may mix labels."""
     from .lockstep import even_step_tiles, plan_lockstep_groups
     print(f"save images at: {output_dir}")
     os.makedirs(output_dir, exist_ok=True)
-    kw = dict(scale=scale, batch_size=batch_size, test_label=test_label, cond_scale=cond_scale,
+    labels = labels or {}
+    kw = dict(scale=scale, batch_size=batch_size, cond_scale=cond_scale,
               guidance_start_steps=guidance_start_steps, class_cond_scale=class_cond_scale,
               class_guidance_start_steps=class_guidance_start_steps, generation_start_steps=generation_start_steps,
               num_sample_steps=num_sample_steps, enable_amp=enable_amp, interpolation=interpolation, seed=seed)
     from concurrent.futures import ThreadPoolExecutor
-    pending, saves = [], []                              # (image, save_path) of the current lock-step group; PNG writers
+    pending, saves = [], []                              # (image, save_path, label) of the current lock-step group; PNG writers
 
     with ThreadPoolExecutor(max_workers=2) as pool:      # PNG encoding overlaps the next group's sampling
         def flush():
             if not pending:
                 return
             if lockstep_tiles is not None:
-                sizes = [im.size for im, _ in pending]
+                sizes = [im.size for im, _, _ in pending]
                 tiles = sum(even_step_tiles(h * scale, w * scale) for (w, h) in sizes)
                 print(f"lock-step group: {len(pending)} images, {tiles} tiles per even step")
+            group_labels = [lb for _, _, lb in pending]
+            one_label = group_labels[0] if len(set(group_labels)) == 1 else group_labels
             if len(pending) == 1:
-                outs = [sr_target_image(pending[0][0], sr_model, **kw)]
+                outs = [sr_target_image(pending[0][0], sr_model, test_label=group_labels[0], **kw)]
             elif lockstep_tiles is not None:
-                outs = sr_target_images_mixed([im for im, _ in pending], sr_model, **kw)
+                outs = sr_target_images_mixed([im for im, _, _ in pending], sr_model, test_label=one_label, **kw)
             else:
-                outs = sr_target_images([im for im, _ in pending], sr_model, **kw)
-            for (_, path), sr in zip(pending, outs):
+                outs = sr_target_images([im for im, _, _ in pending], sr_model, test_label=one_label, **kw)
+            for (_, path, _), sr in zip(pending, outs):
                 saves.append(pool.submit(sr.save, path))
             pending.clear()
 
@@ -242,15 +300,18 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
             if image is None:
                 print("Invalid image or unable to open image:", filename)
                 continue
+            label = labels.get(os.path.basename(filename), test_label)
+            if pending and (label is None) != (pending[0][2] is None):     # an unlabelled image does not join a labelled group
+                flush()
             if lockstep_tiles is not None:
-                hr = [(h * scale, w * scale) for (w, h) in [im.size for im, _ in pending] + [image.size]]
+                hr = [(h * scale, w * scale) for (w, h) in [im.size for im, _, _ in pending] + [image.size]]
                 if len(plan_lockstep_groups(hr, lockstep_tiles)) > 1:      # the image would push the group over the budget
                     flush()
-                pending.append((image, save_path))
+                pending.append((image, save_path, label))
                 continue
             if pending and (len(pending) >= max(1, lockstep) or pending[0][0].size != image.size):
                 flush()
-            pending.append((image, save_path))
+            pending.append((image, save_path, label))
             if len(pending) >= max(1, lockstep):
                 flush()
         flush()
@@ -315,7 +376,7 @@ def main(argv=None):
                            generation_start_steps=args.generation_start_steps,
                            num_sample_steps=args.num_sample_steps, start_index=args.start_index,
                            end_index=args.end_index, enable_amp=args.amp, interpolation=args.interpolation,
-                           seed=args.seed, lockstep=args.lockstep, lockstep_tiles=args.lockstep_tiles)
+                           seed=args.seed, lockstep=args.lockstep, lockstep_tiles=args.lockstep_tiles, labels=args.labels)
 
 
 if __name__ == "__main__":

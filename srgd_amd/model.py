@@ -165,9 +165,10 @@ class _ShuffleUp(_Params):                              # PixelShuffleUpsample: 
 
 
 def _single_class_id(class_label) -> int:
-    """The samplers condition every tile on ONE class (the reference passes a ``[1]`` label that broadcasts over the
-    tile batch, model.py:694).  A ``[B]`` label with differing entries (legal for the reference's un-tiled ``sample``)
-    is refused rather than silently collapsed to its first element."""
+    """The un-tiled ``sample()`` loops condition every tile on ONE class (the reference passes a ``[1]`` label that
+    broadcasts over the batch, model.py:694).  A ``[B]`` label with differing entries (legal for the reference's un-tiled
+    ``sample``) is refused there rather than silently collapsed to its first element: un-tiled ``sample()`` is the
+    remaining gap.  ``forward`` and the lock-step forms of ``tiled_sample`` take one label per image (``_image_class_ids``)."""
     if class_label is None:
         return -1
     flat = class_label.reshape(-1)
@@ -175,6 +176,27 @@ def _single_class_id(class_label) -> int:
         raise NotImplementedError("per-image class labels: this engine conditions one run on one class "
                                   "(pass a [1] label, or equal labels)")
     return int(flat[0])
+
+
+def _image_class_ids(class_label, n_images):
+    """``class_label`` of a call on ``n_images`` images as one id per image: ``None`` stays ``None``, a ``[1]`` label
+    broadcasts (the reference's form), a ``[n_images]`` label gives every image its own; any other count is a ``ValueError``."""
+    if class_label is None:
+        return None
+    flat = [int(v) for v in torch.as_tensor(class_label).reshape(-1).tolist()]
+    if len(flat) == 1:
+        return flat * n_images
+    if len(flat) != n_images:
+        raise ValueError(f"class_label holds {len(flat)} labels for {n_images} images (pass one label, or one per image)")
+    return flat
+
+
+def _run_labels(ids):
+    """(class_id for the begin entry, per-image ids or None) of a run: labels that differ are set after the begin
+    (srgd_sampler_image_labels); equal ones run as the one-label run they are."""
+    if ids is None:
+        return -1, None
+    return ids[0], (ids if len(set(ids)) > 1 else None)
 
 
 def _as_tuple(v, n):
@@ -297,14 +319,17 @@ class ConditionalSRUnet(nn.Module):
         f = self.downsample_factor
         assert all(d % f == 0 for d in x.shape[-2:]), \
             f"your input dimensions {x.shape[-2:]} need to be divisible by {f}, given the unet"
-        class_id = -1
+        class_id, per_sample = -1, None
         if class_label is not None:
-            if class_label.numel() != 1:
-                raise NotImplementedError("per-sample class labels (the reference passes one label of shape [1])")
-            class_id = int(class_label.reshape(-1)[0])
+            if class_label.numel() == 1:
+                class_id = int(class_label.reshape(-1)[0])
+            else:                                   # one label per sample (model.py:692-694 embeds a [B] label row by row)
+                per_sample = _image_class_ids(class_label, x.shape[0])
         time = time.reshape(-1)
         if time.numel() == 1 and x.shape[0] > 1:
             time = time.expand(x.shape[0])
+        if per_sample is not None:
+            return self.engine(self.precision).unet_forward_labels(x, time, per_sample, x_self_cond)
         return self.engine(self.precision).unet_forward(x, time, class_id, x_self_cond)
 
 
@@ -409,8 +434,10 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
             raise ValueError("condition_x must be [B,3,H,W] (B=1 in the reference, whose tile gather assumes batch 1)")
         f = self.model.downsample_factor
         assert tile_size % f == 0, f"your input dimensions need to be divisible by {f}, given the unet"
+        class_id, image_ids = _run_labels(_image_class_ids(class_label, batch))
+        if image_ids is not None and self.canvas_group is not None:
+            raise NotImplementedError("per-image class labels on a canvas sharded over ranks (canvas_group)")
         eng = self.model.engine(precision or self.precision)
-        class_id = _single_class_id(class_label)
 
         (left, top, right, bottom), pad = get_coord_and_pad(h, w)
         hp, wp = h + pad[2] + pad[3], w + pad[0] + pad[1]
@@ -431,6 +458,8 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
         cond_canvas = torch.empty(batch, 3, hp, wp, device=dev, dtype=torch.float32)
         eng.sampler_begin(geo, cond01, cond_canvas, [(a, c_) for (a, _, c_, _) in coords0],
                           [(a, c_) for (a, _, c_, _) in coords1], scalars, log_snrs, class_id)
+        if image_ids is not None:
+            eng.sampler_image_labels(image_ids)
 
         host_noise = self.noise_source == "host"
         if generation_start_steps > 0 or not start_white_noise:
@@ -475,6 +504,8 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                     for e_ in more:
                         e_.sampler_begin(geo, cond01, torch.empty_like(cond_canvas), [(a, c_) for (a, _, c_, _) in coords0],
                                          [(a, c_) for (a, _, c_, _) in coords1], scalars, log_snrs, class_id)
+                        if image_ids is not None:
+                            e_.sampler_image_labels(image_ids)
                     lanes = StepLanes([eng] + more, dev)
                 lanes.run(n_step, lambda e_, first, count, ring: e_.sampler_step_tiles(
                     i, first, count, ring, img, cond_canvas, x_start, noise_tiles, noise_canvas, passes, kind, scale, sub_batch,
@@ -516,8 +547,8 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                 raise ValueError("a list condition_x holds [1,3,H,W] tensors")
         plans, classes = plan_mixed_group([(int(c.shape[2]), int(c.shape[3])) for c in conds], tile_size)
         prec = precision or self.precision
+        class_id, image_ids = _run_labels(_image_class_ids(class_label, len(conds)))
         eng = self.model.engine(prec)
-        class_id = _single_class_id(class_label)
         images = [_lib.SamplerImage(H=p.H, W=p.W, Hp=p.Hp, Wp=p.Wp, left=p.box[0], top=p.box[1], inner_l=p.inner[0],
                                     inner_t=p.inner[1], inner_r=p.inner[2], inner_b=p.inner[3], n_even=len(p.coords0),
                                     n_odd=len(p.coords1), noise_class=p.noise_class) for p in plans]
@@ -529,6 +560,8 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
 
         def begin(e_, canvas):
             e_.sampler_begin_images(tile_size, images, cond01, canvas, tiles_even, tiles_odd, scalars, log_snrs, class_id)
+            if image_ids is not None:
+                e_.sampler_image_labels(image_ids)
         begin(eng, cond_canvas)
 
         first_of_class = [next(p for p in plans if p.noise_class == k) for k in range(len(classes))]
@@ -813,8 +846,10 @@ class ConditionalElucidatedDiffusionSR(nn.Module):
         if batch < 1 or c != 3:
             raise ValueError("condition_x must be [B,3,H,W] (B=1 in the reference; B>1 = same-sized images in lock-step, "
                              "each sampled as it would be alone with the same seed)")
+        class_id, image_ids = _run_labels(_image_class_ids(class_label, batch))
+        if image_ids is not None and self.canvas_group is not None:
+            raise NotImplementedError("per-image class labels on a canvas sharded over ranks (canvas_group)")
         eng = self.net.engine(precision or self.precision)
-        class_id = _single_class_id(class_label)
         (left, top, right, bottom), (hp, wp), coords0, coords1, (sl, st_, sr, sb) = _tiling(h, w, tile_size, tile_stride)
         geo = SamplerGeometry(H=h, W=w, Hp=hp, Wp=wp, left=left, top=top, inner_l=sl, inner_t=st_, inner_r=sr,
                               inner_b=sb, tile=tile_size, n_even=len(coords0), n_odd=len(coords1), n_images=batch)
@@ -823,6 +858,8 @@ class ConditionalElucidatedDiffusionSR(nn.Module):
         cond_canvas = torch.empty(batch, 3, hp, wp, device=dev, dtype=torch.float32)
         eng.edm_begin(geo, cond01, cond_canvas, [(a, c_) for (a, _, c_, _) in coords0],
                       [(a, c_) for (a, _, c_, _) in coords1], scalars, c_noise, class_id)
+        if image_ids is not None:
+            eng.sampler_image_labels(image_ids)
         host_noise = self.noise_source == "host"
         seed = self.device_noise_seed
 
@@ -868,6 +905,8 @@ class ConditionalElucidatedDiffusionSR(nn.Module):
                     for e_ in more:
                         e_.edm_begin(geo, cond01, torch.empty_like(cond_canvas), [(a, c_) for (a, _, c_, _) in coords0],
                                      [(a, c_) for (a, _, c_, _) in coords1], scalars, c_noise, class_id)
+                        if image_ids is not None:
+                            e_.sampler_image_labels(image_ids)
                     lanes = StepLanes([eng] + more, dev)
                 lanes.run(n_step, lambda e_, first, count, do_ring: e_.edm_step_tiles(
                     i, first, count, do_ring, img, cond_canvas, x_start, work, z, ring, passes, kind, scale, sub_batch, seed))

@@ -5,7 +5,9 @@ dim-128 seeded weights, 50 steps, device noise, bf16 and f16x3.
 Arms: "solo" = one tiled_sample call per image (what the command line does with such a folder, --lockstep included: its groups
 close at every size change) and "mixed" = plan_lockstep_groups at a budget of 125 tiles, one call per group.  Arms alternate,
 --repeats rounds each; prints one JSON line per (precision, workload, arm) with images/s and tile-forwards/s.
-    python tools/mixed_lockstep_throughput.py [--repeats 3] [--precisions bf16,f16x3] [--steps 50]"""
+--alternating_labels gives image i the class label i % 2 (per-image labels: the solo arm passes each image's own [1] label, the
+mixed arm one label per image of the group); without it every image carries label 0.
+    python tools/mixed_lockstep_throughput.py [--repeats 3] [--precisions bf16,f16x3] [--steps 50] [--alternating_labels]"""
 import argparse
 import json
 import logging
@@ -33,6 +35,7 @@ ap.add_argument("--repeats", type=int, default=3)
 ap.add_argument("--precisions", default="bf16,f16x3")
 ap.add_argument("--steps", type=int, default=50)
 ap.add_argument("--workloads", default=",".join(WORKLOADS))
+ap.add_argument("--alternating_labels", action="store_true")
 args = ap.parse_args()
 
 schema = {k: tuple(v) for k, v in json.load(open(os.path.join(ROOT, "tests", "golden", "schema_dim128.json"))).items()}
@@ -43,7 +46,7 @@ sampler.load_state_dict(synth_state_dict(schema, seed=0), strict=True)
 sampler = sampler.eval().to(torch.device("cuda", 0))
 sampler.noise_source = "device"
 sampler.device_noise_seed = 71
-label = torch.tensor([0]).cuda()
+label_of = (lambda i: i % 2) if args.alternating_labels else (lambda i: 0)
 g = torch.Generator().manual_seed(0)
 
 for prec in args.precisions.split(","):
@@ -57,12 +60,13 @@ for prec in args.precisions.split(","):
         groups = plan_lockstep_groups(hr, BUDGET)
 
         def solo():
-            for c in conds:
-                sampler.tiled_sample(batch_size=BUDGET, condition_x=c, class_label=label, precision=prec)
+            for i, c in enumerate(conds):
+                sampler.tiled_sample(batch_size=BUDGET, condition_x=c, class_label=torch.tensor([label_of(i)]).cuda(), precision=prec)
 
         def mixed():
             for grp in groups:
-                sampler.tiled_sample(batch_size=BUDGET, condition_x=[conds[i] for i in grp], class_label=label, precision=prec)
+                labels = torch.tensor([label_of(i) for i in grp] if args.alternating_labels else [0]).cuda()
+                sampler.tiled_sample(batch_size=BUDGET, condition_x=[conds[i] for i in grp], class_label=labels, precision=prec)
         arms = {"solo": solo, "mixed": mixed}
         for fn in arms.values():                         # warm-up: engines, lane engines, graphs, pool
             fn()
@@ -77,7 +81,7 @@ for prec in args.precisions.split(","):
                 times[k].append(time.perf_counter() - t0)
         for k, ts in times.items():
             best, worst = min(ts), max(ts)
-            print(json.dumps(dict(precision=prec, workload=wl, arm=k, images=len(lr), calls=len(lr) if k == "solo" else len(groups),
+            print(json.dumps(dict(precision=prec, workload=wl, labels="alternating" if args.alternating_labels else "one", arm=k, images=len(lr), calls=len(lr) if k == "solo" else len(groups),
                                   group_sizes=None if k == "solo" else [len(x) for x in groups], steps=args.steps,
                                   tile_forwards=tile_fwd, seconds=[round(t, 3) for t in ts],
                                   images_per_s=round(len(lr) / (sum(ts) / len(ts)), 3),
