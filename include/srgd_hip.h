@@ -180,6 +180,21 @@ int srgd_sampler_begin_images(srgd_engine* e, int tile, int n_images, const srgd
  * ("class label out of range"); a U-Net without a class embedding; a call after the first step. */
 int srgd_sampler_image_labels(srgd_engine* e, const int32_t* class_ids_host, int n_images, void* stream);
 
+/* Gives the noise classes of a begun DDPM run their own seeds (per-image noise seeds in lock-step; an engine extension, absent
+ * upstream): seeds_host is host [n_classes], one seed per noise class of the run in class order (srgd_sampler_begin: one class;
+ * srgd_sampler_begin_images: srgd_sampler_image::noise_class, where two classes may share a canvas size - a noise stream is the
+ * pair (canvas size, seed)).  Valid after srgd_sampler_begin or srgd_sampler_begin_images, before the run's first step and before
+ * srgd_sampler_q_start; the next begin clears the seeds.  From then on every draw the engine makes on the device is per class:
+ *   - a step's tile noise: class k's n_k tiles from seeds_host[k] with the counter starting at 0, the classes' draws
+ *     concatenated in class order (the layout host noise_tiles of a mixed run has);
+ *   - the odd-step ring and srgd_sampler_q_start's canvas draw: class k's [3,Hp_k,Wp_k] from seeds_host[k];
+ * all streams of one use in ONE launch (srgd_randn_streams' kernel), so every image comes out bit-identical to a run of its own
+ * whose `seed` is its class's seed.  The `seed` argument of srgd_sampler_step / _step_tiles / srgd_sampler_q_start is then
+ * ignored for noise.  Host noise pointers, where given, are used as before.
+ * Errors (< 0, nothing launched): no begun run; an EDM run (its step kernels address one shared noise canvas); n_classes
+ * different from the run's; a call after the first step. */
+int srgd_sampler_noise_seeds(srgd_engine* e, const uint64_t* seeds_host, int n_classes, void* stream);
+
 /* One denoising step over every tile of grid (step % 2), `sub_batch` tiles per U-Net launch
  * (the reference's --batch_size; results do not depend on it).
  *   passes = 1: eps = unet(label, cond).                       (model.py:3155-3156)

@@ -112,6 +112,14 @@ int srgd_k_conv1x1_split_rms(const void* x, int Cin, int B, int N, const float* 
                              const float* pre_norm_g_host, const float* post_norm_g_host, const void* residual, void* out,
                              void* stream);
 
+/* Counter-based Gaussian noise (Philox4x32-10 + Box-Muller) for n_streams noise streams in ONE launch: the batched counterpart of
+ * srgd_randn (srgd_hip.h).  Stream k writes counts_host[k] floats at dst + offsets_host[k] from seeds_host[k], with its counter
+ * starting at 0: bit for bit what srgd_randn writes for (counts_host[k], seeds_host[k], stream_id).  Offsets and counts need not be
+ * multiples of 4; the slices must not overlap.  The three arrays are on the HOST (uploaded inside; synchronises).  A seeded
+ * lock-step run (srgd_sampler_noise_seeds) draws its tile, ring and q-start noise through this kernel. */
+int srgd_randn_streams(float* dst, const int64_t* offsets_host, const int64_t* counts_host, const uint64_t* seeds_host,
+                       int n_streams, uint64_t stream_id, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

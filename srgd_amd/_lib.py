@@ -71,6 +71,7 @@ PROTOTYPES = {
     "srgd_unet_forward_labels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int32),
                                            C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "srgd_sampler_image_labels": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_void_p]),
+    "srgd_sampler_noise_seeds": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int, C.c_void_p]),
     "srgd_sampler_begin": (C.c_int, [C.c_void_p, C.POINTER(SamplerGeometry), C.c_void_p, C.c_void_p,
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.POINTER(StepScalars),
                                      C.POINTER(C.c_float), C.c_int, C.c_void_p]),
@@ -110,6 +111,8 @@ PROTOTYPES = {
     "srgd_profile_family_name": (C.c_char_p, [C.c_int]),
     "srgd_device_bytes_in_use": (C.c_int64, [C.c_void_p]),
     # include/srgd_hip_kernels.h
+    "srgd_randn_streams": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.c_int,
+                                     C.c_uint64, C.c_void_p]),
     "srgd_k_conv2d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                 C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_int, C.c_int, C.c_void_p]),

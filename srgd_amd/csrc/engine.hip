@@ -344,6 +344,14 @@ struct srgd_engine {
   struct NoiseClass { int Hp, Wp; long long cnoise_off; };
   std::vector<NoiseClass> classes;        // in order of first appearance; canvas noise of class k at cnoise_off
   size_t class_canvas_elems = 0;          // sum of the classes' 3*Hp*Wp
+  std::vector<int> class_n[2];            // tiles of one image of class k in the even / odd grid
+  // per-class noise seeds (srgd_sampler_noise_seeds): every device draw is then one batched launch over the classes' streams;
+  // d_streams holds three tables of n_classes records: even-step tiles | odd-step tiles | canvas (ring, q_start)
+  bool run_seeded = false;
+  PhiloxStream* d_streams = nullptr; size_t streams_cap = 0;
+  std::vector<PhiloxStream> streams_host;
+  size_t stream_max_n[3] = {0, 0, 0};     // largest stream of each table, elements
+  int class_tiles[2] = {0, 0};            // sum of class_n: tiles of a seeded step's concatenated draw
 
   // device-side step counter + per-run hipGraph cache: a DDPM step is one graph per (grid parity, guidance mode);
   // step-dependent values (conditioning row, schedule scalars, RNG stream) are read through d_step, so one captured
@@ -1328,7 +1336,7 @@ int srgd_destroy(srgd_engine* e) {
   e->pool.release_all();
   for (void* p : {(void*)e->gn_partial, (void*)e->coefA, (void*)e->la_ws, (void*)e->d_rows,
                   (void*)e->d_tiles_even, (void*)e->d_tiles_odd, (void*)e->d_sc, (void*)e->d_edm, (void*)e->rng_tiles,
-                  (void*)e->rng_canvas, (void*)e->d_images, (void*)e->d_slots, (void*)e->d_slots_api})
+                  (void*)e->rng_canvas, (void*)e->d_images, (void*)e->d_slots, (void*)e->d_slots_api, (void*)e->d_streams})
     if (p) hipFree(p);
   for (CondTable* ct : {&e->ct_sampler, &e->ct_api})
     for (float* q : {ct->table, ct->ls, ct->feat, ct->h1, ct->t1, ct->trows, ct->c1, ct->c2})
@@ -1626,12 +1634,13 @@ static int sampler_begin_common(srgd_engine* e, int tile, const std::vector<Imag
   e->n_steps = n_steps;
   e->run_class = class_id;
   e->n_labels = 1;
-  e->run_labels = e->run_stepped = false;
+  e->run_labels = e->run_stepped = e->run_seeded = false;
   e->run_times.assign(times_host, times_host + n_times);
   e->images = recs;
   e->classes = classes;
   e->class_canvas_elems = (size_t)cnoise_off;
   for (int par = 0; par < 2; ++par) {
+    e->class_n[par] = class_n[par];
     e->n_grid[par] = (int)(tl[par].size() / 3);
     e->max_local[par] = max_local[par];
   }
@@ -1760,6 +1769,38 @@ int srgd_sampler_image_labels(srgd_engine* e, const int32_t* class_ids_host, int
   e->run_labels = true;
   e->run_class = labels[0];
   SRGD_HIP(hipStreamSynchronize(st));
+  return 0;
+}
+
+int srgd_sampler_noise_seeds(srgd_engine* e, const uint64_t* seeds_host, int n_classes, void* stream) {
+  if (!e || !e->run_active) SRGD_FAIL("srgd_sampler_noise_seeds: call srgd_sampler_begin or srgd_sampler_begin_images first");
+  if (!seeds_host) SRGD_FAIL("srgd_sampler_noise_seeds: null argument");
+  if (e->run_is_edm) SRGD_FAIL("srgd_sampler_noise_seeds: not available on an EDM run (its step kernels address one shared noise canvas)");
+  if (n_classes != (int)e->classes.size()) SRGD_FAIL("srgd_sampler_noise_seeds: one seed per noise class of the run");
+  if (e->run_stepped) SRGD_FAIL("srgd_sampler_noise_seeds: the run has taken a step (seeds are set before the first)");
+  hipStream_t st = (hipStream_t)stream;
+  SRGD_HIP(hipSetDevice(e->cfg.device));
+  drop_step_graphs(e);                       // graphs bake in which draws a step launches
+  const size_t K = (size_t)n_classes, tile_elems = (size_t)3 * e->geo.tile * e->geo.tile;
+  e->streams_host.assign(3 * K, PhiloxStream{});
+  for (int use = 0; use < 3; ++use) {
+    long long off = 0;
+    e->stream_max_n[use] = 0;
+    for (size_t k = 0; k < K; ++k) {
+      const long long n = use < 2 ? (long long)e->class_n[use][k] * (long long)tile_elems : 3LL * e->classes[k].Hp * e->classes[k].Wp;
+      e->streams_host[use * K + k] = PhiloxStream{use < 2 ? off : e->classes[k].cnoise_off, n, (unsigned long long)seeds_host[k]};
+      off += n;
+      e->stream_max_n[use] = std::max(e->stream_max_n[use], (size_t)n);
+    }
+    if (use < 2) e->class_tiles[use] = (int)(off / (long long)tile_elems);
+  }
+  // every buffer a seeded step or q_start draws into, before any capture
+  SRGD_TRY(ensure(e, &e->d_streams, &e->streams_cap, 3 * K));
+  SRGD_TRY(ensure(e, &e->rng_tiles, &e->rng_tiles_cap, (size_t)std::max(e->class_tiles[0], e->class_tiles[1]) * tile_elems));
+  SRGD_TRY(ensure(e, &e->rng_canvas, &e->rng_canvas_cap, e->class_canvas_elems));
+  SRGD_HIP(hipMemcpyAsync(e->d_streams, e->streams_host.data(), 3 * K * sizeof(PhiloxStream), hipMemcpyHostToDevice, st));
+  SRGD_HIP(hipStreamSynchronize(st));
+  e->run_seeded = true;
   return 0;
 }
 
@@ -1963,7 +2004,11 @@ static int sampler_step_launch(srgd_engine* e, bool last, int parity, int tile_f
     if (!nz) {   // the largest image's worth of tile noise, shared by every image (counter-based: a prefix of it is what a
                  // smaller image draws alone) and independent of sub_batch
       Prof p(e, KC_CANVAS, st);
-      SRGD_TRY(philox_normal(e->rng_tiles, (size_t)e->max_local[parity] * tile_elems, seed, 1ull << 32, e->d_step, st));
+      if (e->run_seeded)   // per-class seeds: each class's own tiles from its own seed, concatenated in class order, one launch
+        SRGD_TRY(philox_normal_streams(e->rng_tiles, e->d_streams + (size_t)parity * e->classes.size(), (int)e->classes.size(),
+                                       e->stream_max_n[parity], 1ull << 32, e->d_step, st));
+      else
+        SRGD_TRY(philox_normal(e->rng_tiles, (size_t)e->max_local[parity] * tile_elems, seed, 1ull << 32, e->d_step, st));
       nz = e->rng_tiles;
     }
   }
@@ -1992,7 +2037,7 @@ static int sampler_step_launch(srgd_engine* e, bool last, int parity, int tile_f
     FinalStepArgs fa;
     fa.act = act; fa.C = e->dim; fa.passes = passes; fa.guidance = guidance_scale;
     fa.w = e->final_w; fa.bias = e->final_b; fa.img = img; fa.x_start = x_start; fa.noise = nz;
-    fa.noise_per_class = noise_tiles ? 1 : 0;
+    fa.noise_per_class = (noise_tiles || e->run_seeded) ? 1 : 0;
     fa.sc = e->d_sc; fa.step_ptr = e->d_step;
     fa.eps4 = x.eps4_done ? eps4 : nullptr;
     { Prof p(e, KC_FINAL, st);
@@ -2009,9 +2054,13 @@ static int sampler_step_launch(srgd_engine* e, bool last, int parity, int tile_f
     Prof p(e, KC_CANVAS, st);
     const float* nc = noise_canvas;
     if (!nc) {   // one draw per noise class (canvas size): what each of its images draws alone
-      for (const auto& k : e->classes)
-        SRGD_TRY(philox_normal(e->rng_canvas + k.cnoise_off, (size_t)3 * k.Hp * k.Wp, seed, (1ull << 32) | 0x80000000ull,
-                               e->d_step, st));
+      if (e->run_seeded)
+        SRGD_TRY(philox_normal_streams(e->rng_canvas, e->d_streams + 2 * e->classes.size(), (int)e->classes.size(),
+                                       e->stream_max_n[2], (1ull << 32) | 0x80000000ull, e->d_step, st));
+      else
+        for (const auto& k : e->classes)
+          SRGD_TRY(philox_normal(e->rng_canvas + k.cnoise_off, (size_t)3 * k.Hp * k.Wp, seed, (1ull << 32) | 0x80000000ull,
+                                 e->d_step, st));
       nc = e->rng_canvas;
     }
     SRGD_TRY(canvas_ring_renoise(img, e->d_images, (int)e->images.size(), e->max_canvas, nc, &e->d_sc[0].sigma_next,
@@ -2063,7 +2112,9 @@ int srgd_sampler_step_tiles(srgd_engine* e, int step, int tile_first, int tile_c
   e->pool.reset_busy();
   // every allocation happens here, before any capture
   SRGD_TRY(ensure_scratch(e, sub_batch * passes, g.tile, g.tile));
-  if (!noise_tiles) SRGD_TRY(ensure(e, &e->rng_tiles, &e->rng_tiles_cap, (size_t)e->max_local[parity] * 3 * g.tile * g.tile));
+  if (!noise_tiles)    // a seeded run draws every class's tiles (sized by srgd_sampler_noise_seeds already; a no-op then)
+    SRGD_TRY(ensure(e, &e->rng_tiles, &e->rng_tiles_cap,
+                    (size_t)(e->run_seeded ? e->class_tiles[parity] : e->max_local[parity]) * 3 * g.tile * g.tile));
   if (!noise_canvas && ring) SRGD_TRY(ensure(e, &e->rng_canvas, &e->rng_canvas_cap, e->class_canvas_elems));
   if (!e->d_step) SRGD_HIP(hipMalloc((void**)&e->d_step, sizeof(int)));
   hipLaunchKernelGGL(set_step_kernel, dim3(1), dim3(1), 0, st, e->d_step, step);
@@ -2119,8 +2170,12 @@ int srgd_sampler_q_start(srgd_engine* e, const float* cond01, const float* noise
   const float* nz = noise_canvas;
   if (!nz) {   // one draw per noise class, as in the ring re-noise
     SRGD_TRY(ensure(e, &e->rng_canvas, &e->rng_canvas_cap, e->class_canvas_elems));
-    for (const auto& k : e->classes)
-      SRGD_TRY(philox_normal(e->rng_canvas + k.cnoise_off, (size_t)3 * k.Hp * k.Wp, seed, 0, nullptr, st));
+    if (e->run_seeded)
+      SRGD_TRY(philox_normal_streams(e->rng_canvas, e->d_streams + 2 * e->classes.size(), (int)e->classes.size(), e->stream_max_n[2],
+                                     0, nullptr, st));
+    else
+      for (const auto& k : e->classes)
+        SRGD_TRY(philox_normal(e->rng_canvas + k.cnoise_off, (size_t)3 * k.Hp * k.Wp, seed, 0, nullptr, st));
     nz = e->rng_canvas;
   }
   return canvas_q_start(cond01, e->d_images, (int)e->images.size(), e->max_canvas, nz, alpha, sigma, img, st);

@@ -322,4 +322,24 @@ int srgd_k_full_attention(const void* qkv, void* out, int B, int N, int heads, i
   return full_attention(qkv, out, B, N, heads, 32, is_bf16 != 0, (hipStream_t)stream);
 }
 
+int srgd_randn_streams(float* dst, const int64_t* offsets_host, const int64_t* counts_host, const uint64_t* seeds_host,
+                       int n_streams, uint64_t stream_id, void* stream) {
+  if (!dst || !offsets_host || !counts_host || !seeds_host) SRGD_FAIL("srgd_randn_streams: null argument");
+  if (n_streams < 1 || n_streams > 65535) SRGD_FAIL("srgd_randn_streams: 1 to 65535 streams per call");
+  hipStream_t st = (hipStream_t)stream;
+  std::vector<PhiloxStream> table((size_t)n_streams);
+  size_t max_n = 0;
+  for (int k = 0; k < n_streams; ++k) {
+    if (offsets_host[k] < 0 || counts_host[k] < 0) SRGD_FAIL("srgd_randn_streams: negative offset or count");
+    table[k] = PhiloxStream{(long long)offsets_host[k], (long long)counts_host[k], (unsigned long long)seeds_host[k]};
+    max_n = std::max(max_n, (size_t)counts_host[k]);
+  }
+  DevBuf dt;
+  SRGD_TRY(dt.alloc(table.size() * sizeof(PhiloxStream)));
+  SRGD_HIP(hipMemcpy(dt.p, table.data(), table.size() * sizeof(PhiloxStream), hipMemcpyHostToDevice));
+  SRGD_TRY(philox_normal_streams(dst, (const PhiloxStream*)dt.p, n_streams, max_n, stream_id, nullptr, st));
+  SRGD_HIP(hipStreamSynchronize(st));        // the table is freed on return
+  return 0;
+}
+
 }  // extern "C"

@@ -293,5 +293,15 @@ int canvas_unpack_gathered(float* canvas, const float* gathered, const TileBatch
 int canvas_exchange_tiles(float* canvas, float* tiles, const TileBatch& tb, bool to_canvas, hipStream_t st);
 // counter-based Gaussian noise (Philox4x32-10 + Box-Muller), throughput mode only
 int philox_normal(float* dst, size_t n, uint64_t seed, uint64_t stream_id, const int* step_ptr, hipStream_t st);
+// the same generator for many noise streams in ONE launch (per-image seeds): stream k writes dst[off_k, off_k + n_k) from seed_k
+// with its counter starting at 0, i.e. exactly philox_normal(dst + off_k, n_k, seed_k, stream_id, step_ptr).  `streams` is a
+// device table; max_n = the largest n_k (sizes the grid).  Offsets and counts need not be multiples of 4.
+struct PhiloxStream {
+  long long off;             // first element of the stream's slice in dst
+  long long n;               // elements
+  unsigned long long seed;
+};
+int philox_normal_streams(float* dst, const PhiloxStream* streams, int n_streams, size_t max_n, uint64_t stream_id,
+                          const int* step_ptr, hipStream_t st);
 
 }  // namespace srgd

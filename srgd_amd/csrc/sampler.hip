@@ -468,6 +468,42 @@ __global__ void philox_normal_kernel(float* __restrict__ dst, size_t n, uint64_t
   }
 }
 
+// One launch for many noise streams (per-image seeds, kernels.hpp PhiloxStream): grid row blockIdx.y = stream, the x blocks stride
+// over that stream's quads.  The counter is local to the stream (q = 0 at its first element) and stream_id / step are mixed in as
+// philox_normal_kernel mixes them, so stream k's slice is bit for bit what philox_normal_kernel writes for (n_k, seed_k,
+// stream_id, step) - tested exactly.  Offsets and counts need not be multiples of 4: every store is a guarded scalar one.
+__global__ void philox_normal_streams_kernel(float* __restrict__ dst, const PhiloxStream* __restrict__ streams, uint64_t stream_id,
+                                             const int* __restrict__ step_ptr) {
+  const PhiloxStream s = streams[blockIdx.y];
+  const uint32_t step = step_ptr ? (uint32_t)*step_ptr : 0u;
+  const size_t n = (size_t)s.n, nq = (n + 3) / 4;
+  float* __restrict__ out = dst + s.off;
+  for (size_t q = (size_t)blockIdx.x * 256 + threadIdx.x; q < nq; q += (size_t)gridDim.x * 256) {
+    uint32_t c[4] = {(uint32_t)q, (uint32_t)(q >> 32), (uint32_t)stream_id, (uint32_t)(stream_id >> 32) ^ (step << 8)};
+    uint32_t k0 = (uint32_t)s.seed, k1 = (uint32_t)(s.seed >> 32);
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+      philox_round(c, k0, k1);
+      k0 += 0x9E3779B9u;
+      k1 += 0xBB67AE85u;
+    }
+    float z[4];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const float u1 = ((float)c[2 * h] + 1.0f) * 2.3283064365386963e-10f;      // (0, 1]
+      const float u2 = (float)c[2 * h + 1] * 2.3283064365386963e-10f;
+      const float rad = sqrtf(-2.0f * __logf(u1));
+      float sn, cs;
+      __sincosf(6.283185307179586f * u2, &sn, &cs);
+      z[2 * h] = rad * cs;
+      z[2 * h + 1] = rad * sn;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (q * 4 + j < n) out[q * 4 + j] = z[j];
+  }
+}
+
 int grid_for(long n) { return (int)std::min<long>((n + 255) / 256, 256L * 16); }
 // canvas kernels: one grid row per image, the same total block budget as grid_for
 dim3 grid_per_image(long max_elems, int n_images) {
@@ -599,6 +635,18 @@ int canvas_exchange_tiles(float* canvas, float* tiles, const TileBatch& tb, bool
 
 int philox_normal(float* dst, size_t n, uint64_t seed, uint64_t stream_id, const int* step_ptr, hipStream_t st) {
   hipLaunchKernelGGL(philox_normal_kernel, dim3(grid_for((long)((n + 3) / 4))), dim3(256), 0, st, dst, n, seed,
+                     stream_id, step_ptr);
+  SRGD_HIP(hipGetLastError());
+  return 0;
+}
+
+int philox_normal_streams(float* dst, const PhiloxStream* streams, int n_streams, size_t max_n, uint64_t stream_id,
+                          const int* step_ptr, hipStream_t st) {
+  if (!dst || !streams) SRGD_FAIL("philox_normal_streams: null argument");
+  if (n_streams < 1 || n_streams > 65535) SRGD_FAIL("philox_normal_streams: 1 to 65535 streams per launch");
+  // the x extent follows the largest stream, under the block budget the canvas kernels share; shorter streams' spare blocks fall
+  // through their loop at once
+  hipLaunchKernelGGL(philox_normal_streams_kernel, grid_per_image((long)((max_n + 3) / 4), n_streams), dim3(256), 0, st, dst, streams,
                      stream_id, step_ptr);
   SRGD_HIP(hipGetLastError());
   return 0;

@@ -162,6 +162,14 @@ class HipEngine:
             check(self._L.srgd_sampler_image_labels(self._h, ids, len(class_ids), _stream_ptr(self.device)),
                   "srgd_sampler_image_labels")
 
+    def sampler_noise_seeds(self, class_seeds: Sequence[int]) -> None:
+        """One noise seed per noise class of the begun DDPM run (srgd_sampler_noise_seeds), before its first step and before
+        ``sampler_q_start``; the ``seed`` of the step and q-start calls is then ignored for noise."""
+        seeds = (C.c_uint64 * len(class_seeds))(*[int(v) & (2 ** 64 - 1) for v in class_seeds])
+        with torch.cuda.device(self.device):
+            check(self._L.srgd_sampler_noise_seeds(self._h, seeds, len(class_seeds), _stream_ptr(self.device)),
+                  "srgd_sampler_noise_seeds")
+
     def sampler_step(self, step: int, img: torch.Tensor, cond_canvas: torch.Tensor, x_start: Optional[torch.Tensor],
                      noise_tiles: Optional[torch.Tensor], noise_canvas: Optional[torch.Tensor], passes: int,
                      guidance_kind: int, guidance_scale: float, sub_batch: int, seed: int = 0) -> None:
@@ -261,6 +269,21 @@ class HipEngine:
         with torch.cuda.device(self.device):
             check(self._L.srgd_randn(self._h, _dev_ptr(dst), dst.numel(), int(seed) & (2 ** 64 - 1), int(stream_id),
                                      _stream_ptr(self.device)), "srgd_randn")
+        return dst
+
+    def randn_streams_(self, dst: torch.Tensor, offsets: Sequence[int], counts: Sequence[int], seeds: Sequence[int],
+                       stream_id: int) -> torch.Tensor:
+        """``randn_`` for several noise streams in one launch (srgd_randn_streams): stream k fills
+        ``dst.view(-1)[offsets[k]:offsets[k] + counts[k]]`` from ``seeds[k]``, its counter starting at 0."""
+        n = len(seeds)
+        assert len(offsets) == n and len(counts) == n and n >= 1
+        assert all(o >= 0 and c >= 0 and o + c <= dst.numel() for o, c in zip(offsets, counts)), "stream outside dst"
+        off = (C.c_int64 * n)(*[int(v) for v in offsets])
+        cnt = (C.c_int64 * n)(*[int(v) for v in counts])
+        sd = (C.c_uint64 * n)(*[int(v) & (2 ** 64 - 1) for v in seeds])
+        with torch.cuda.device(self.device):
+            check(self._L.srgd_randn_streams(_dev_ptr(dst), off, cnt, sd, n, int(stream_id), _stream_ptr(self.device)),
+                  "srgd_randn_streams")
         return dst
 
     # ---------------------------------------------------------------- measurement

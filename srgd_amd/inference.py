@@ -66,7 +66,15 @@ def parse_args(argv=None):
     p.add_argument("--label_file", type=str, default=None, metavar="PATH",
                    help="text file of `file_name label` lines: the images of --input_dir named there are sampled with that class "
                         "label, the others with --test_label; lock-step groups may mix labels (engine extension)")
+    p.add_argument("--samples", type=int, default=1, metavar="K",
+                   help="sample every input image K times in lock-step with the noise seeds --seed, --seed+1, ..., --seed+K-1: sample 0 "
+                        "goes to <name>_out.png (the file a run without --samples writes), sample k >= 1 to <name>_out_s<k>.png, each "
+                        "bit-identical to a solo run with that seed (engine extension, DDPM configs only)")
     args = p.parse_args(argv)
+    if args.samples < 1:
+        raise SystemExit(f"--samples: K must be >= 1, got {args.samples}")
+    if args.seed < 0 and args.samples > 1:
+        raise SystemExit("--samples: noise seeds are non-negative, --seed must be >= 0")
     args.labels = None
     if args.label_file is not None:
         args.labels = parse_label_file(args.label_file, args.input_dir, load_config(args.conf).num_classes)
@@ -116,6 +124,12 @@ def _label_tensor(test_label, n_images, device):
     else:
         ids = [test_label]
     return torch.LongTensor(ids).to(device)
+
+
+def sample_output_name(file_name, k):
+    """``--samples``: output file name of sample k of an input file: sample 0 keeps the reference's ``<name>_out.png``, sample
+    k >= 1 is ``<name>_out_s<k>.png``."""
+    return os.path.basename(file_name).replace(".png", "_out.png" if k == 0 else f"_out_s{k}.png")
 
 
 def seed_everything(seed):
@@ -246,6 +260,46 @@ def sr_target_images_mixed(images, sr_model, scale=4, batch_size=8, test_label=2
     return outs
 
 
+def sr_target_images_seeded(images, seeds, sr_model, scale=4, batch_size=8, test_label=2, cond_scale=1.0, guidance_start_steps=0,
+                            class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0,
+                            num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71):
+    """``sr_target_images_mixed`` with one noise seed per image (engine extension, ``tiled_sample(seeds=...)``): image i comes out
+    bit-identical to its own ``sr_target_image`` run with ``seed=seeds[i]``; an image may appear several times with different
+    seeds (each PIL image is upsampled once).  ``seed`` seeds the process as the other entry points do and is not a noise seed."""
+    conds = {}
+    for im in images:
+        if id(im) not in conds:
+            conds[id(im)] = upsample_bicubic_on_device(im, scale, sr_model.device)
+    label = _label_tensor(test_label, len(images), sr_model.device)
+    seed_everything(seed)
+    sr_model.device_noise_seed = seed
+    with torch.inference_mode():
+        output = sr_model.tiled_sample(batch_size=batch_size * len(images), condition_x=[conds[id(im)] for im in images],
+                                       class_label=label, cond_scale=cond_scale, guidance_start_steps=guidance_start_steps,
+                                       class_cond_scale=class_cond_scale,
+                                       class_guidance_start_steps=class_guidance_start_steps,
+                                       generation_start_steps=generation_start_steps,
+                                       num_sample_steps=num_sample_steps, amp=enable_amp, seeds=list(seeds))
+    outs = [unit_tensor_to_pil_on_device(o[0]) for o in output]
+    assert all(o.size == (im.size[0] * 4, im.size[1] * 4) for o, im in zip(outs, images))
+    return outs
+
+
+def plan_sample_entries(file_names, output_dir, samples, seed):
+    """``--samples K``: the grouping loop's entries ``(file name, save path, noise seed)`` in order - the K samples of a file are
+    consecutive, sample k with seed ``seed + k``; an entry whose output file exists is left out (skip-if-exists per output file,
+    so only the missing samples are drawn)."""
+    entries = []
+    for filename in file_names:
+        for k in range(samples):
+            save_path = os.path.join(output_dir, sample_output_name(filename, k))
+            if os.path.exists(save_path):
+                print("skip")
+                continue
+            entries.append((filename, save_path, seed + k))
+    return entries
+
+
 def try_open_image(image_path):
     try:
         return Image.open(image_path).convert("RGB")
@@ -256,62 +310,73 @@ def try_open_image(image_path):
 def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=8, test_label=2, cond_scale=1.0,
                            guidance_start_steps=0, class_cond_scale=1.0, class_guidance_start_steps=0,
                            generation_start_steps=0, num_sample_steps=250, start_index=0, end_index=None,
-                           enable_amp=False, interpolation="bicubic", seed=71, lockstep=1, lockstep_tiles=None, labels=None):
+                           enable_amp=False, interpolation="bicubic", seed=71, lockstep=1, lockstep_tiles=None, labels=None,
+                           samples=1):
     """``lockstep``: groups of up to N consecutive same-sized images; ``lockstep_tiles``: groups of consecutive images of any
     size up to that many tiles per even step (srgd_amd.lockstep.plan_lockstep_groups).  ``labels``: ``{file name: label}``
-    (``--label_file``) for the images that do not take ``test_label``; a group may mix labels."""
+    (``--label_file``) for the images that do not take ``test_label``; a group may mix labels.  ``samples``: every image is
+    sampled that many times with the noise seeds ``seed, seed + 1, ...`` (``--samples``); the samples of an image are consecutive
+    entries of the grouping, each counts as an image of its group, and with neither lock-step argument they group as
+    ``lockstep=samples``."""
     from .lockstep import even_step_tiles, plan_lockstep_groups
     print(f"save images at: {output_dir}")
     os.makedirs(output_dir, exist_ok=True)
     labels = labels or {}
+    if samples > 1 and lockstep_tiles is None and lockstep <= 1:
+        lockstep = samples
     kw = dict(scale=scale, batch_size=batch_size, cond_scale=cond_scale,
               guidance_start_steps=guidance_start_steps, class_cond_scale=class_cond_scale,
               class_guidance_start_steps=class_guidance_start_steps, generation_start_steps=generation_start_steps,
               num_sample_steps=num_sample_steps, enable_amp=enable_amp, interpolation=interpolation, seed=seed)
     from concurrent.futures import ThreadPoolExecutor
-    pending, saves = [], []                              # (image, save_path, label) of the current lock-step group; PNG writers
+    pending, saves = [], []                              # (image, save_path, label, noise seed) of the current lock-step group; PNG writers
 
     with ThreadPoolExecutor(max_workers=2) as pool:      # PNG encoding overlaps the next group's sampling
         def flush():
             if not pending:
                 return
             if lockstep_tiles is not None:
-                sizes = [im.size for im, _, _ in pending]
+                sizes = [e[0].size for e in pending]
                 tiles = sum(even_step_tiles(h * scale, w * scale) for (w, h) in sizes)
                 print(f"lock-step group: {len(pending)} images, {tiles} tiles per even step")
-            group_labels = [lb for _, _, lb in pending]
+            group_labels = [e[2] for e in pending]
+            group_seeds = [e[3] for e in pending]
             one_label = group_labels[0] if len(set(group_labels)) == 1 else group_labels
-            if len(pending) == 1:
-                outs = [sr_target_image(pending[0][0], sr_model, test_label=group_labels[0], **kw)]
+            group_images = [e[0] for e in pending]
+            if len(pending) == 1:                        # a solo run with that seed: what every sample of a group is identical to
+                outs = [sr_target_image(pending[0][0], sr_model, test_label=group_labels[0], **dict(kw, seed=group_seeds[0]))]
+            elif len(set(group_seeds)) > 1:
+                outs = sr_target_images_seeded(group_images, group_seeds, sr_model, test_label=one_label, **kw)
             elif lockstep_tiles is not None:
-                outs = sr_target_images_mixed([im for im, _, _ in pending], sr_model, test_label=one_label, **kw)
+                outs = sr_target_images_mixed(group_images, sr_model, test_label=one_label, **dict(kw, seed=group_seeds[0]))
             else:
-                outs = sr_target_images([im for im, _, _ in pending], sr_model, test_label=one_label, **kw)
-            for (_, path, _), sr in zip(pending, outs):
-                saves.append(pool.submit(sr.save, path))
+                outs = sr_target_images(group_images, sr_model, test_label=one_label, **dict(kw, seed=group_seeds[0]))
+            for e, sr in zip(pending, outs):
+                saves.append(pool.submit(sr.save, e[1]))
             pending.clear()
 
-        for filename in sorted(glob.glob(f"{input_dir}/*"))[start_index:end_index]:
-            save_path = os.path.join(output_dir, os.path.basename(filename).replace(".png", "_out.png"))
-            if os.path.exists(save_path):
-                print("skip")
-                continue
-            image = try_open_image(filename)
+        opened = (None, None)                            # the K samples of a file share one decoded image
+        for filename, save_path, noise_seed in plan_sample_entries(sorted(glob.glob(f"{input_dir}/*"))[start_index:end_index],
+                                                                   output_dir, samples, seed):
+            if opened[0] != filename:
+                opened = (filename, try_open_image(filename))
+                if opened[1] is None:
+                    print("Invalid image or unable to open image:", filename)
+            image = opened[1]
             if image is None:
-                print("Invalid image or unable to open image:", filename)
                 continue
             label = labels.get(os.path.basename(filename), test_label)
             if pending and (label is None) != (pending[0][2] is None):     # an unlabelled image does not join a labelled group
                 flush()
             if lockstep_tiles is not None:
-                hr = [(h * scale, w * scale) for (w, h) in [im.size for im, _, _ in pending] + [image.size]]
+                hr = [(h * scale, w * scale) for (w, h) in [e[0].size for e in pending] + [image.size]]
                 if len(plan_lockstep_groups(hr, lockstep_tiles)) > 1:      # the image would push the group over the budget
                     flush()
-                pending.append((image, save_path, label))
+                pending.append((image, save_path, label, noise_seed))
                 continue
             if pending and (len(pending) >= max(1, lockstep) or pending[0][0].size != image.size):
                 flush()
-            pending.append((image, save_path, label))
+            pending.append((image, save_path, label, noise_seed))
             if len(pending) >= max(1, lockstep):
                 flush()
         flush()
@@ -350,6 +415,9 @@ def main(argv=None):
     if args.lockstep_tiles is not None and isinstance(sr_model, ConditionalElucidatedDiffusionSR):
         raise SystemExit("--lockstep_tiles: mixed-size lock-step is built for the DDPM sampler (model: conditional_continuous) only; "
                          "this config samples with EDM - use --lockstep N for same-sized images")
+    if args.samples > 1 and isinstance(sr_model, ConditionalElucidatedDiffusionSR):
+        raise SystemExit("--samples: per-image noise seeds are built for the DDPM sampler (model: conditional_continuous) only; "
+                         "this config samples with EDM - run once per --seed instead")
     sr_model.noise_source = "device" if args.device_noise else "host"
     sr_model.precision = args.precision
     print(f"engine precision: {args.precision} (noise: {sr_model.noise_source})")
@@ -376,7 +444,8 @@ def main(argv=None):
                            generation_start_steps=args.generation_start_steps,
                            num_sample_steps=args.num_sample_steps, start_index=args.start_index,
                            end_index=args.end_index, enable_amp=args.amp, interpolation=args.interpolation,
-                           seed=args.seed, lockstep=args.lockstep, lockstep_tiles=args.lockstep_tiles, labels=args.labels)
+                           seed=args.seed, lockstep=args.lockstep, lockstep_tiles=args.lockstep_tiles, labels=args.labels,
+                           samples=args.samples)
 
 
 if __name__ == "__main__":

@@ -5,11 +5,13 @@ A mixed group samples images of different sizes together: every image keeps its 
 box and tile grids (reference model.py:3296-3342, exactly what a run of that image alone uses), and a step's tiles of all
 images share the U-Net launches.  The reference reseeds before every image (inference.py:73) and its draw sequence depends
 only on the canvas size, so images with the same canvas ``(Hp, Wp)`` form one *noise class* and share their noise, as
-same-sized images in lock-step always have (480x320 and 320x480 both pad to 768x768: one class).
+same-sized images in lock-step always have (480x320 and 320x480 both pad to 768x768: one class).  With per-image noise seeds
+(``tiled_sample(seeds=...)``) a class is a noise stream, the pair (canvas size, seed): K copies of one image with K seeds
+are K streams and come out as K different samples.
 """
 from __future__ import annotations
 
-from typing import List, NamedTuple, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 
 class ImagePlan(NamedTuple):
@@ -32,17 +34,27 @@ def image_plan(h: int, w: int, tile_size: int = 256, noise_class: int = 0) -> Im
     return ImagePlan(h, w, hp, wp, tuple(box), tuple(inner), coords0, coords1, noise_class)
 
 
-def plan_mixed_group(sizes: Sequence[Tuple[int, int]], tile_size: int = 256):
+def plan_mixed_group(sizes: Sequence[Tuple[int, int]], tile_size: int = 256, seeds: Optional[Sequence[int]] = None):
     """Per-image plans of a group and its noise classes: ``(plans, classes)`` with ``classes`` the canvas sizes ``(Hp, Wp)``
-    in order of first appearance and ``plans[i].noise_class`` the index of image i's class."""
-    plans, classes = [], []
-    for (h, w) in sizes:
+    in order of first appearance and ``plans[i].noise_class`` the index of image i's class.
+
+    With ``seeds`` (one noise seed per image) a class is a *noise stream*, the pair (canvas size, seed): images that agree in
+    both share one, images that differ in either get their own, numbered in order of first appearance.  The return value is
+    then ``(plans, classes, class_seeds)``: ``classes[k]`` still the canvas size of stream k (sizes may repeat) and
+    ``class_seeds[k]`` its seed."""
+    if seeds is not None and len(seeds) != len(sizes):
+        raise ValueError(f"seeds: {len(seeds)} seeds for {len(sizes)} images (one per image)")
+    plans, classes, keys = [], [], []
+    for i, (h, w) in enumerate(sizes):
         p = image_plan(int(h), int(w), tile_size)
-        key = (p.Hp, p.Wp)
-        if key not in classes:
-            classes.append(key)
-        plans.append(p._replace(noise_class=classes.index(key)))
-    return plans, classes
+        key = (p.Hp, p.Wp) if seeds is None else (p.Hp, p.Wp, int(seeds[i]))
+        if key not in keys:
+            keys.append(key)
+            classes.append((p.Hp, p.Wp))
+        plans.append(p._replace(noise_class=keys.index(key)))
+    if seeds is None:
+        return plans, classes
+    return plans, classes, [k[2] for k in keys]
 
 
 def even_step_tiles(h: int, w: int, tile_size: int = 256) -> int:

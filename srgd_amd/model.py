@@ -199,6 +199,29 @@ def _run_labels(ids):
     return ids[0], (ids if len(set(ids)) > 1 else None)
 
 
+def _noise_seeds(seeds, n_images):
+    """``tiled_sample(seeds=...)``: a list of one non-negative int per image (ValueError otherwise)."""
+    import operator
+    if torch.is_tensor(seeds):
+        seeds = seeds.tolist()
+    try:
+        seeds = list(seeds)
+    except TypeError:
+        raise ValueError("seeds must be a sequence of one non-negative int per image")
+    if len(seeds) != n_images:
+        raise ValueError(f"seeds: {len(seeds)} seeds for {n_images} images (one per image)")
+    out = []
+    for v in seeds:
+        try:
+            v = operator.index(v)
+        except TypeError:
+            raise ValueError(f"seeds: {v!r} is not an integer")
+        if v < 0 or v >= 2 ** 64:
+            raise ValueError(f"seeds: {v} is outside [0, 2**64) (a noise seed is a non-negative integer)")
+        out.append(v)
+    return out
+
+
 def _as_tuple(v, n):
     return tuple(v) if isinstance(v, (tuple, list)) else (v,) * n
 
@@ -393,7 +416,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
     def tiled_sample(self, batch_size=4, tile_size=256, tile_stride=256, condition_x=None, class_label=None,
                      cond_scale=1.0, guidance_start_steps=0, class_cond_scale=1.0, class_guidance_start_steps=0,
                      generation_start_steps=0, num_sample_steps=None, with_images=False, with_x0_images=False,
-                     start_white_noise=True, amp=False, precision=None):
+                     start_white_noise=True, amp=False, precision=None, seeds=None):
         """Tiled CFG-DDPM sampling (reference model.py:3288-3413).
 
         ``amp`` is accepted and ignored exactly as in the reference (which always computes fp32); the engine
@@ -406,8 +429,37 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
 
         ``condition_x`` may also be a list or tuple of ``[1,3,H_i,W_i]`` tensors of different sizes: they are sampled in
         lock-step the same way (mixed-size lock-step, ``_tiled_sample_images``) and a list of ``[1,3,H_i,W_i]`` outputs is
-        returned, each bit-identical to a call with that image alone."""
+        returned, each bit-identical to a call with that image alone.
+
+        ``seeds`` (engine-only keyword, absent upstream): a sequence of non-negative ints, one noise seed per image of either
+        group form.  Image i then comes out bit-identical to a call on that image alone after ``torch.manual_seed(seeds[i])``
+        (host noise) or with ``device_noise_seed = seeds[i]`` (device noise), every other argument the same - K copies of one
+        image with K seeds are K different samples in one run.  Images that agree in canvas size and seed share one noise
+        stream.  In host-noise mode each stream draws from a private ``torch.Generator().manual_seed(seed)`` in the reference's
+        draw order, and the caller's generator (``host_generator`` or torch's global one) is neither read nor advanced.  A
+        seeded run takes the mixed-size path for both condition forms; ``seeds=None`` is the unseeded call unchanged.  Not
+        available together with ``with_images`` / ``with_x0_images`` or a canvas sharded over ranks."""
         num_sample_steps = self.num_sample_steps if num_sample_steps is None else num_sample_steps
+        if seeds is not None:
+            as_list = isinstance(condition_x, (list, tuple))
+            seeds = _noise_seeds(seeds, len(condition_x) if as_list else int(condition_x.shape[0]))
+            if with_images or with_x0_images:
+                raise NotImplementedError("seeds together with with_images / with_x0_images (trajectories of a seeded group)")
+            if self.canvas_group is not None:
+                raise NotImplementedError("seeds on a canvas sharded over ranks (canvas_group)")
+            if not as_list:
+                if condition_x.dim() != 4 or condition_x.shape[1] != 3:
+                    raise ValueError("condition_x must be [B,3,H,W] (B=1 in the reference, whose tile gather assumes batch 1)")
+                condition_x = [condition_x[i:i + 1] for i in range(condition_x.shape[0])]
+            if cond_scale != 1.0 and class_cond_scale != 1.0:
+                raise NotImplementedError("Currently, you cannot specify both cond_scale and class_cond_scale at the same time.")
+            if tile_size != 256 or tile_stride != 256:
+                raise NotImplementedError("tile_size/tile_stride other than 256 are unusable in the reference too "
+                                          "(get_coord_and_pad is called without them, model.py:3301)")
+            outs = self._tiled_sample_images(batch_size, tile_size, list(condition_x), class_label, cond_scale,
+                                             guidance_start_steps, class_cond_scale, class_guidance_start_steps,
+                                             generation_start_steps, num_sample_steps, start_white_noise, precision, seeds=seeds)
+            return outs if as_list else torch.cat(outs, 0)
         if isinstance(condition_x, (list, tuple)):
             if with_images or with_x0_images:
                 raise NotImplementedError("with_images / with_x0_images of a mixed-size group (trajectories of different shapes)")
@@ -530,12 +582,17 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
 
     def _tiled_sample_images(self, batch_size, tile_size, conds, class_label, cond_scale, guidance_start_steps,
                              class_cond_scale, class_guidance_start_steps, generation_start_steps, num_sample_steps,
-                             start_white_noise, precision):
+                             start_white_noise, precision, seeds=None):
         """Mixed-size lock-step (srgd_sampler_begin_images): every image keeps its own canvas, crop box, padding, inner box and
         tile grids; a step's tiles of all images share the U-Net launches.  Noise: the images of one noise class (canvas size)
         see the draw sequence a run of one of them alone sees.  Host noise: the generator state is taken once at entry and
         each class draws from its own generator started at that state, in the reference's order; on return the caller's
-        generator (``host_generator`` or torch's global one) holds the state a run of the FIRST image alone would leave."""
+        generator (``host_generator`` or torch's global one) holds the state a run of the FIRST image alone would leave.
+
+        ``seeds`` (one per image, validated by the caller): a noise class is a noise stream (canvas size, seed).  Host noise:
+        stream k draws from a private ``torch.Generator().manual_seed(seed_k)`` - the stream of the global generator after
+        ``torch.manual_seed(seed_k)`` - and the caller's generator is left alone.  Device noise: every engine of the run gets
+        the streams' seeds (srgd_sampler_noise_seeds) and draws all of them in one launch per use."""
         from .lockstep import plan_mixed_group
         dev = self.device
         if dev.type != "cuda":
@@ -545,7 +602,12 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
         for c in conds:
             if not torch.is_tensor(c) or c.dim() != 4 or c.shape[0] != 1 or c.shape[1] != 3:
                 raise ValueError("a list condition_x holds [1,3,H,W] tensors")
-        plans, classes = plan_mixed_group([(int(c.shape[2]), int(c.shape[3])) for c in conds], tile_size)
+        sizes = [(int(c.shape[2]), int(c.shape[3])) for c in conds]
+        class_seeds = None
+        if seeds is None:
+            plans, classes = plan_mixed_group(sizes, tile_size)
+        else:
+            plans, classes, class_seeds = plan_mixed_group(sizes, tile_size, seeds=seeds)
         prec = precision or self.precision
         class_id, image_ids = _run_labels(_image_class_ids(class_label, len(conds)))
         eng = self.model.engine(prec)
@@ -558,22 +620,28 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
         cond01 = torch.cat([c.to(dev, torch.float32).reshape(-1) for c in conds])
         cond_canvas = torch.empty(sum(3 * p.Hp * p.Wp for p in plans), device=dev, dtype=torch.float32)
 
+        host_noise = self.noise_source == "host"
+
         def begin(e_, canvas):
             e_.sampler_begin_images(tile_size, images, cond01, canvas, tiles_even, tiles_odd, scalars, log_snrs, class_id)
             if image_ids is not None:
                 e_.sampler_image_labels(image_ids)
+            if class_seeds is not None and not host_noise:   # host noise arrives drawn: the engine makes no draw of its own
+                e_.sampler_noise_seeds(class_seeds)
         begin(eng, cond_canvas)
 
         first_of_class = [next(p for p in plans if p.noise_class == k) for k in range(len(classes))]
-        host_noise = self.noise_source == "host"
         if host_noise:
-            caller_gen = self.host_generator if self.host_generator is not None else torch.default_generator
-            state = caller_gen.get_state()
-            gens = []
-            for _ in classes:
-                g_ = torch.Generator()
-                g_.set_state(state)
-                gens.append(g_)
+            if class_seeds is not None:     # a private generator per stream; the caller's is neither read nor advanced
+                gens = [torch.Generator().manual_seed(s_) for s_ in class_seeds]
+            else:
+                caller_gen = self.host_generator if self.host_generator is not None else torch.default_generator
+                state = caller_gen.get_state()
+                gens = []
+                for _ in classes:
+                    g_ = torch.Generator()
+                    g_.set_state(state)
+                    gens.append(g_)
 
             def draw(shape_of_class):       # per-class draws in class order, concatenated (the engine's noise layout)
                 return torch.cat([_host_randn(g_, *shape_of_class(k)).reshape(-1) for k, g_ in enumerate(gens)]).to(dev)
@@ -588,14 +656,17 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
             eng.sampler_q_start(cond01, canvas_draw() if host_noise else None, float(ls0.sigmoid().sqrt()),
                                 float((-ls0).sigmoid().sqrt()), img, self.device_noise_seed)
         else:
-            if host_noise:
-                start = canvas_draw()
-            else:                           # the counter-based draw of each class's canvas, as a run alone draws it
-                start = torch.cat([eng.randn_(torch.empty(3 * hp * wp, device=dev), self.device_noise_seed, 0)
-                                   for (hp, wp) in classes])
             offs = [0]
             for (hp, wp) in classes:
                 offs.append(offs[-1] + 3 * hp * wp)
+            if host_noise:
+                start = canvas_draw()
+            elif class_seeds is not None:   # every stream's canvas from its own seed, one launch
+                start = eng.randn_streams_(torch.empty(offs[-1], device=dev), offs[:-1],
+                                           [b_ - a_ for a_, b_ in zip(offs, offs[1:])], class_seeds, 0)
+            else:                           # the counter-based draw of each class's canvas, as a run alone draws it
+                start = torch.cat([eng.randn_(torch.empty(3 * hp * wp, device=dev), self.device_noise_seed, 0)
+                                   for (hp, wp) in classes])
             img = torch.cat([start[offs[p.noise_class]:offs[p.noise_class + 1]] for p in plans])
 
         sub_batch = self.max_tiles_per_launch or batch_size
@@ -631,7 +702,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
 
         out = torch.empty(sum(3 * p.H * p.W for p in plans), device=dev, dtype=torch.float32)
         eng.sampler_end(img, out)
-        if host_noise:
+        if host_noise and class_seeds is None:
             caller_gen.set_state(gens[plans[0].noise_class].get_state())
         outs, off = [], 0
         for p in plans:
@@ -827,13 +898,17 @@ class ConditionalElucidatedDiffusionSR(nn.Module):
     def tiled_sample(self, batch_size=4, tile_size=256, tile_stride=256, condition_x=None, class_label=None,
                      cond_scale=1.0, guidance_start_steps=0, class_cond_scale=1.0, class_guidance_start_steps=0,
                      generation_start_steps=0, num_sample_steps=None, clamp=True, zero_init=False, with_images=False,
-                     with_x0_images=False, start_white_noise=True, amp=False, precision=None):
+                     with_x0_images=False, start_white_noise=True, amp=False, precision=None, seeds=None):
         """Reference model.py:2309-2475 (``start_white_noise`` and ``amp`` are accepted and unused there too; ``precision``
-        is the engine-only override of ``self.precision``)."""
+        is the engine-only override of ``self.precision``).  ``seeds`` (per-image noise seeds) is a DDPM-sampler feature and is
+        refused here."""
         n = self.num_sample_steps if num_sample_steps is None else num_sample_steps
         if isinstance(condition_x, (list, tuple)):
             raise NotImplementedError("mixed-size lock-step (a list condition_x) is built for the DDPM sampler only; "
                                       "sample EDM images one size at a time")
+        if seeds is not None:
+            raise NotImplementedError("seeds (per-image noise seeds) are built for the DDPM sampler only: the EDM step kernels "
+                                      "address one noise canvas shared by all images")
         if cond_scale != 1.0 and class_cond_scale != 1.0:
             raise NotImplementedError("Currently, you cannot specify both cond_scale and class_cond_scale at the same time.")
         if tile_size != 256 or tile_stride != 256:
