@@ -306,6 +306,33 @@ int srgd_image_resize_bicubic_u8(const uint8_t* src_hwc, int h, int w, int out_h
  * trunc(img * 255) (torchvision: pic.mul(255).byte()).  Asynchronous on `stream`. */
 int srgd_image_unit_to_u8(const float* img01_chw, int h, int w, uint8_t* dst_hwc, void* stream);
 
+/* Colour correction of a sampler output against its condition (engine extension, absent upstream; the arithmetic of StableSR's
+ * wavelet_reconstruction / adaptive_instance_normalization): out01 = the [0,1] output of srgd_sampler_end, cond01 = the [0,1] x4
+ * bicubic input of the same size, both device fp32 planar [3][h][w]; dst01 likewise (written).
+ *   mode 1, wavelet: dst = clamp(high5(out) + low5(cond)), five a-trous levels (radius 1, 2, 4, 8, 16) of the 3x3 kernel
+ *     [1,2,1]^T [1,2,1] / 16 with replicate padding, computed as out + B16(B8(B4(B2(B1(cond - out))))) in ten separable passes
+ *     (the clamped blur is linear; every level clamps its own indices).
+ *   mode 2, adain: per channel dst = clamp((out - mean_out) / std_out * std_cond + mean_cond), std = sqrt(unbiased variance + 1e-5),
+ *     the statistics summed in float64 over fixed 4096-pixel chunks of a channel plane and then over the chunks in a fixed order
+ *     (no atomics).
+ * The clamp to [0,1] keeps a NaN; a NaN of out01 or cond01 is a NaN at that pixel of dst01 (wavelet: over the footprint of the
+ * five-level chain and nowhere else; adain: the whole channel).  dst01 may alias out01 (in place), not cond01.
+ * scratch: device memory owned by the caller, 16-byte aligned for the 16-byte access path (8-byte at least for adain), of
+ *   wavelet: 2 * E fp32 elements, E = 3*h*w rounded up to a multiple of 4 (two ping-pong planes sets);
+ *   adain:   96 * (1 + ceil(h*w / 4096)) bytes (the channel statistics and the float64 partial sums, carved from the same buffer).
+ * An image has at most 2^31 - 256 elements (3*h*w).  Asynchronous on `stream`; no allocation, no synchronisation. */
+int srgd_image_color_fix(const float* out01, const float* cond01, int h, int w, int mode, float* dst01, float* scratch,
+                         void* stream);
+/* srgd_image_color_fix for n_images images held in flat buffers (the layout of a mixed lock-step run): image i's [3][h_i][w_i]
+ * planes start at element offsets_host[i] of out01, cond01, dst01 and (wavelet) scratch alike; hw_host = h_0, w_0, h_1, w_1, ...
+ * Offsets need not be multiples of 4.  One launch sequence covers up to 128 images (the grid's y index is the image; a larger group
+ * runs as consecutive sequences of 128), so a group costs the launches of one image: 10 (wavelet) or 3 (adain).  Each image comes out
+ * bit-identical to srgd_image_color_fix on that image alone.
+ * scratch: wavelet: 2 * E fp32 elements, E = max_i(offsets_host[i] + 3*h_i*w_i) rounded up to a multiple of 4;
+ *          adain:   sum_i 96 * (1 + ceil(h_i*w_i / 4096)) bytes. */
+int srgd_image_color_fix_images(const float* out01, const float* cond01, const int64_t* offsets_host, const int32_t* hw_host,
+                                int n_images, int mode, float* dst01, float* scratch, void* stream);
+
 /* Fills dst[n] with N(0,1) draws of the engine's counter-based generator (initial canvas noise
  * in throughput mode; the parity mode uploads torch's CPU stream instead). */
 int srgd_randn(srgd_engine* e, float* dst, size_t n, uint64_t seed, uint64_t stream_id, void* stream);

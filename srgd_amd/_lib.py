@@ -102,6 +102,9 @@ PROTOTYPES = {
     "srgd_quantize_e4m3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float]),
     "srgd_image_resize_bicubic_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "srgd_image_unit_to_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "srgd_image_color_fix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "srgd_image_color_fix_images": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int, C.c_int,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]),
     "srgd_randn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_void_p]),
     "srgd_profile_begin": (C.c_int, [C.c_void_p]),
     "srgd_profile_end": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double),

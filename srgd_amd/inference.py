@@ -21,6 +21,7 @@ import numpy as np
 import torch
 from PIL import Image
 
+from .colorfix import color_fix_on_device  # noqa: F401  (public: srgd_amd.inference.color_fix_on_device)
 from .config import load_config
 from .model import ConditionalElucidatedDiffusionSR, get_model
 
@@ -70,6 +71,10 @@ def parse_args(argv=None):
                    help="sample every input image K times in lock-step with the noise seeds --seed, --seed+1, ..., --seed+K-1: sample 0 "
                         "goes to <name>_out.png (the file a run without --samples writes), sample k >= 1 to <name>_out_s<k>.png, each "
                         "bit-identical to a solo run with that seed (engine extension, DDPM configs only)")
+    p.add_argument("--color_fix", choices=["none", "wavelet", "adain"], default="none",
+                   help="colour-correct every output against its x4 bicubic input on the GPU (engine extension): wavelet = the input's "
+                        "low frequencies (five a-trous levels) under the output's high frequencies, adain = the input's per-channel "
+                        "mean and standard deviation; with --samples every sample is corrected against the same input")
     args = p.parse_args(argv)
     if args.samples < 1:
         raise SystemExit(f"--samples: K must be >= 1, got {args.samples}")
@@ -124,6 +129,11 @@ def _label_tensor(test_label, n_images, device):
     else:
         ids = [test_label]
     return torch.LongTensor(ids).to(device)
+
+
+def _color_fix_kw(color_fix):
+    """``tiled_sample``'s ``color_fix`` keyword for a set mode; nothing for None / "none" (the call a run without the flag makes)."""
+    return {} if color_fix in (None, "none") else {"color_fix": color_fix}
 
 
 def sample_output_name(file_name, k):
@@ -194,7 +204,7 @@ def unit_tensor_to_pil_on_device(t: torch.Tensor) -> Image.Image:
 
 def sr_target_image(image, sr_model, scale=4, batch_size=8, test_label=2, cond_scale=1.0, guidance_start_steps=0,
                     class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0,
-                    num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71):
+                    num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None):
     width, height = image.size
     # the reference maps 'lanczos' to bicubic too (inference.py:66-69)
     condition_x = upsample_bicubic_on_device(image, scale, sr_model.device)
@@ -207,7 +217,7 @@ def sr_target_image(image, sr_model, scale=4, batch_size=8, test_label=2, cond_s
                                        class_cond_scale=class_cond_scale,
                                        class_guidance_start_steps=class_guidance_start_steps,
                                        generation_start_steps=generation_start_steps,
-                                       num_sample_steps=num_sample_steps, amp=enable_amp)
+                                       num_sample_steps=num_sample_steps, amp=enable_amp, **_color_fix_kw(color_fix))
     sr_img = unit_tensor_to_pil_on_device(output[0])
     assert sr_img.size == (width * 4, height * 4)
     return sr_img
@@ -215,7 +225,7 @@ def sr_target_image(image, sr_model, scale=4, batch_size=8, test_label=2, cond_s
 
 def sr_target_images(images, sr_model, scale=4, batch_size=8, test_label=2, cond_scale=1.0, guidance_start_steps=0,
                      class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0,
-                     num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71):
+                     num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None):
     """``sr_target_image`` for several same-sized images in lock-step (engine extension): one ``tiled_sample`` call on a
     ``[B,3,H,W]`` condition.  Each image is sampled exactly as it would be alone after the reference's per-image
     ``seed_everything(seed)`` (inference.py:73) - bit-identical outputs - while their tiles fill the U-Net launches.
@@ -232,7 +242,7 @@ def sr_target_images(images, sr_model, scale=4, batch_size=8, test_label=2, cond
                                        class_cond_scale=class_cond_scale,
                                        class_guidance_start_steps=class_guidance_start_steps,
                                        generation_start_steps=generation_start_steps,
-                                       num_sample_steps=num_sample_steps, amp=enable_amp)
+                                       num_sample_steps=num_sample_steps, amp=enable_amp, **_color_fix_kw(color_fix))
     outs = [unit_tensor_to_pil_on_device(o) for o in output]
     assert all(o.size == (width * 4, height * 4) for o in outs)
     return outs
@@ -240,7 +250,7 @@ def sr_target_images(images, sr_model, scale=4, batch_size=8, test_label=2, cond
 
 def sr_target_images_mixed(images, sr_model, scale=4, batch_size=8, test_label=2, cond_scale=1.0, guidance_start_steps=0,
                            class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0,
-                           num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71):
+                           num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None):
     """``sr_target_image`` for several images of any sizes in lock-step (engine extension): one ``tiled_sample`` call on a list
     of conditions.  Each image comes out bit-identical to its own ``sr_target_image`` run (with its own label where
     ``test_label`` is a sequence of one label per image)."""
@@ -254,7 +264,7 @@ def sr_target_images_mixed(images, sr_model, scale=4, batch_size=8, test_label=2
                                        class_cond_scale=class_cond_scale,
                                        class_guidance_start_steps=class_guidance_start_steps,
                                        generation_start_steps=generation_start_steps,
-                                       num_sample_steps=num_sample_steps, amp=enable_amp)
+                                       num_sample_steps=num_sample_steps, amp=enable_amp, **_color_fix_kw(color_fix))
     outs = [unit_tensor_to_pil_on_device(o[0]) for o in output]
     assert all(o.size == (im.size[0] * 4, im.size[1] * 4) for o, im in zip(outs, images))
     return outs
@@ -262,7 +272,7 @@ def sr_target_images_mixed(images, sr_model, scale=4, batch_size=8, test_label=2
 
 def sr_target_images_seeded(images, seeds, sr_model, scale=4, batch_size=8, test_label=2, cond_scale=1.0, guidance_start_steps=0,
                             class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0,
-                            num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71):
+                            num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None):
     """``sr_target_images_mixed`` with one noise seed per image (engine extension, ``tiled_sample(seeds=...)``): image i comes out
     bit-identical to its own ``sr_target_image`` run with ``seed=seeds[i]``; an image may appear several times with different
     seeds (each PIL image is upsampled once).  ``seed`` seeds the process as the other entry points do and is not a noise seed."""
@@ -279,7 +289,8 @@ def sr_target_images_seeded(images, seeds, sr_model, scale=4, batch_size=8, test
                                        class_cond_scale=class_cond_scale,
                                        class_guidance_start_steps=class_guidance_start_steps,
                                        generation_start_steps=generation_start_steps,
-                                       num_sample_steps=num_sample_steps, amp=enable_amp, seeds=list(seeds))
+                                       num_sample_steps=num_sample_steps, amp=enable_amp, seeds=list(seeds),
+                                       **_color_fix_kw(color_fix))
     outs = [unit_tensor_to_pil_on_device(o[0]) for o in output]
     assert all(o.size == (im.size[0] * 4, im.size[1] * 4) for o, im in zip(outs, images))
     return outs
@@ -311,8 +322,9 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
                            guidance_start_steps=0, class_cond_scale=1.0, class_guidance_start_steps=0,
                            generation_start_steps=0, num_sample_steps=250, start_index=0, end_index=None,
                            enable_amp=False, interpolation="bicubic", seed=71, lockstep=1, lockstep_tiles=None, labels=None,
-                           samples=1):
-    """``lockstep``: groups of up to N consecutive same-sized images; ``lockstep_tiles``: groups of consecutive images of any
+                           samples=1, color_fix=None):
+    """``color_fix``: ``--color_fix`` (None / "none", "wavelet", "adain"), handed by keyword to whichever ``sr_target_image*``
+    function samples a group.  ``lockstep``: groups of up to N consecutive same-sized images; ``lockstep_tiles``: groups of consecutive images of any
     size up to that many tiles per even step (srgd_amd.lockstep.plan_lockstep_groups).  ``labels``: ``{file name: label}``
     (``--label_file``) for the images that do not take ``test_label``; a group may mix labels.  ``samples``: every image is
     sampled that many times with the noise seeds ``seed, seed + 1, ...`` (``--samples``); the samples of an image are consecutive
@@ -327,7 +339,8 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
     kw = dict(scale=scale, batch_size=batch_size, cond_scale=cond_scale,
               guidance_start_steps=guidance_start_steps, class_cond_scale=class_cond_scale,
               class_guidance_start_steps=class_guidance_start_steps, generation_start_steps=generation_start_steps,
-              num_sample_steps=num_sample_steps, enable_amp=enable_amp, interpolation=interpolation, seed=seed)
+              num_sample_steps=num_sample_steps, enable_amp=enable_amp, interpolation=interpolation, seed=seed,
+              color_fix=None if color_fix in (None, "none") else color_fix)
     from concurrent.futures import ThreadPoolExecutor
     pending, saves = [], []                              # (image, save_path, label, noise seed) of the current lock-step group; PNG writers
 
@@ -445,7 +458,7 @@ def main(argv=None):
                            num_sample_steps=args.num_sample_steps, start_index=args.start_index,
                            end_index=args.end_index, enable_amp=args.amp, interpolation=args.interpolation,
                            seed=args.seed, lockstep=args.lockstep, lockstep_tiles=args.lockstep_tiles, labels=args.labels,
-                           samples=args.samples)
+                           samples=args.samples, color_fix=args.color_fix)
 
 
 if __name__ == "__main__":

@@ -23,6 +23,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import SamplerGeometry, StepScalars
+from .colorfix import check_mode, color_fix_flat
 from .engine import HipEngine
 from .lanes import StepLanes, lanes_setting_from_env, lanes_wanted
 
@@ -416,7 +417,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
     def tiled_sample(self, batch_size=4, tile_size=256, tile_stride=256, condition_x=None, class_label=None,
                      cond_scale=1.0, guidance_start_steps=0, class_cond_scale=1.0, class_guidance_start_steps=0,
                      generation_start_steps=0, num_sample_steps=None, with_images=False, with_x0_images=False,
-                     start_white_noise=True, amp=False, precision=None, seeds=None):
+                     start_white_noise=True, amp=False, precision=None, seeds=None, color_fix=None):
         """Tiled CFG-DDPM sampling (reference model.py:3288-3413).
 
         ``amp`` is accepted and ignored exactly as in the reference (which always computes fp32); the engine
@@ -438,7 +439,14 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
         stream.  In host-noise mode each stream draws from a private ``torch.Generator().manual_seed(seed)`` in the reference's
         draw order, and the caller's generator (``host_generator`` or torch's global one) is neither read nor advanced.  A
         seeded run takes the mixed-size path for both condition forms; ``seeds=None`` is the unseeded call unchanged.  Not
-        available together with ``with_images`` / ``with_x0_images`` or a canvas sharded over ranks."""
+        available together with ``with_images`` / ``with_x0_images`` or a canvas sharded over ranks.
+
+        ``color_fix`` (engine-only keyword, absent upstream): ``None`` / ``"none"`` (default: nothing is launched), ``"wavelet"`` or
+        ``"adain"`` - the final [0,1] image of every image of the run is colour-corrected against its own ``condition_x`` on the
+        GPU (srgd_amd.colorfix, one batched call per run) and equals ``color_fix_on_device(uncorrected result, condition_x, mode)``
+        bit for bit.  Trajectories (``with_images`` / ``with_x0_images``) stay raw; on a canvas sharded over ranks every rank
+        corrects its own copy of the whole output."""
+        color_fix = check_mode(color_fix)
         num_sample_steps = self.num_sample_steps if num_sample_steps is None else num_sample_steps
         if seeds is not None:
             as_list = isinstance(condition_x, (list, tuple))
@@ -458,7 +466,8 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                                           "(get_coord_and_pad is called without them, model.py:3301)")
             outs = self._tiled_sample_images(batch_size, tile_size, list(condition_x), class_label, cond_scale,
                                              guidance_start_steps, class_cond_scale, class_guidance_start_steps,
-                                             generation_start_steps, num_sample_steps, start_white_noise, precision, seeds=seeds)
+                                             generation_start_steps, num_sample_steps, start_white_noise, precision, seeds=seeds,
+                                             color_fix=color_fix)
             return outs if as_list else torch.cat(outs, 0)
         if isinstance(condition_x, (list, tuple)):
             if with_images or with_x0_images:
@@ -472,7 +481,8 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                                           "(get_coord_and_pad is called without them, model.py:3301)")
             return self._tiled_sample_images(batch_size, tile_size, list(condition_x), class_label, cond_scale,
                                              guidance_start_steps, class_cond_scale, class_guidance_start_steps,
-                                             generation_start_steps, num_sample_steps, start_white_noise, precision)
+                                             generation_start_steps, num_sample_steps, start_white_noise, precision,
+                                             color_fix=color_fix)
         if cond_scale != 1.0 and class_cond_scale != 1.0:
             raise NotImplementedError("Currently, you cannot specify both cond_scale and class_cond_scale at the same time.")
         if tile_size != 256 or tile_stride != 256:
@@ -576,13 +586,15 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
 
         out = torch.empty(batch, 3, h, w, device=dev, dtype=torch.float32)
         eng.sampler_end(img, out)
+        if color_fix is not None:           # in place on the [B,3,H,W] result; the trajectories above stay raw
+            color_fix_flat(out, cond01, [b * 3 * h * w for b in range(batch)], [(h, w)] * batch, color_fix)
         if with_images:
             return (out, image_list, x0_image_list) if with_x0_images else (out, image_list)
         return out
 
     def _tiled_sample_images(self, batch_size, tile_size, conds, class_label, cond_scale, guidance_start_steps,
                              class_cond_scale, class_guidance_start_steps, generation_start_steps, num_sample_steps,
-                             start_white_noise, precision, seeds=None):
+                             start_white_noise, precision, seeds=None, color_fix=None):
         """Mixed-size lock-step (srgd_sampler_begin_images): every image keeps its own canvas, crop box, padding, inner box and
         tile grids; a step's tiles of all images share the U-Net launches.  Noise: the images of one noise class (canvas size)
         see the draw sequence a run of one of them alone sees.  Host noise: the generator state is taken once at entry and
@@ -702,6 +714,11 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
 
         out = torch.empty(sum(3 * p.H * p.W for p in plans), device=dev, dtype=torch.float32)
         eng.sampler_end(img, out)
+        if color_fix is not None:           # on the run's flat buffers: out and cond01 share the per-image layout
+            starts = [0]
+            for p in plans:
+                starts.append(starts[-1] + 3 * p.H * p.W)
+            color_fix_flat(out, cond01, starts[:-1], [(p.H, p.W) for p in plans], color_fix)
         if host_noise and class_seeds is None:
             caller_gen.set_state(gens[plans[0].noise_class].get_state())
         outs, off = [], 0
@@ -898,10 +915,12 @@ class ConditionalElucidatedDiffusionSR(nn.Module):
     def tiled_sample(self, batch_size=4, tile_size=256, tile_stride=256, condition_x=None, class_label=None,
                      cond_scale=1.0, guidance_start_steps=0, class_cond_scale=1.0, class_guidance_start_steps=0,
                      generation_start_steps=0, num_sample_steps=None, clamp=True, zero_init=False, with_images=False,
-                     with_x0_images=False, start_white_noise=True, amp=False, precision=None, seeds=None):
+                     with_x0_images=False, start_white_noise=True, amp=False, precision=None, seeds=None, color_fix=None):
         """Reference model.py:2309-2475 (``start_white_noise`` and ``amp`` are accepted and unused there too; ``precision``
         is the engine-only override of ``self.precision``).  ``seeds`` (per-image noise seeds) is a DDPM-sampler feature and is
-        refused here."""
+        refused here.  ``color_fix``: as in the DDPM wrapper's ``tiled_sample`` - the final image of every image of the batch
+        colour-corrected against its condition, trajectories raw."""
+        color_fix = check_mode(color_fix)
         n = self.num_sample_steps if num_sample_steps is None else num_sample_steps
         if isinstance(condition_x, (list, tuple)):
             raise NotImplementedError("mixed-size lock-step (a list condition_x) is built for the DDPM sampler only; "
@@ -998,6 +1017,8 @@ class ConditionalElucidatedDiffusionSR(nn.Module):
                 x0_image_list.append(x_start.clone().cpu())
         out = torch.empty(batch, 3, h, w, device=dev, dtype=torch.float32)
         eng.sampler_end(img, out)
+        if color_fix is not None:
+            color_fix_flat(out, cond01, [b * 3 * h * w for b in range(batch)], [(h, w)] * batch, color_fix)
         if with_images:
             return (out, image_list, x0_image_list) if with_x0_images else (out, image_list)
         return out
