@@ -26,18 +26,6 @@ constexpr int RING1 = 3;
 constexpr int LDS1_BYTES = RING1 * STAGE1;         // 73,728 >= EPI_LDS_BYTES = 69,632 (epilogue staging)
 static_assert(LDS1_BYTES >= EPI_LDS_BYTES && BM1 == EPI_BM && BN1 == EPI_BN && NT1 == EPI_NT, "conv1x1_epilogue.hpp tile shape");
 
-typedef __attribute__((address_space(3))) void* lds_ptr1;
-// voffset: per-lane byte offset (VGPR); soffset: wave-uniform byte offset (SGPR)
-__device__ __forceinline__ void dma16_1(__amdgpu_buffer_rsrc_t rsrc, char* lds_wave_base, int voffset, int soffset) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr1)lds_wave_base, 16, voffset, soffset, 0, 0);
-}
-#define WAIT_VM1(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
-#define BARRIER1()                       \
-  do {                                   \
-    __builtin_amdgcn_s_barrier();        \
-    __builtin_amdgcn_sched_barrier(0);   \
-  } while (0)
-
 struct Conv1Args {
   const bf16* in0; const bf16* in1; int C0, C1;
   int B, Hin, Win;        // input image grid
@@ -55,8 +43,6 @@ struct Conv1Args {
   float* eps4; const float* fin_w; const float* fin_b;   // EPI_GNTAIL_FINAL (ConvArgs::eps4)
 };
 
-__device__ __forceinline__ int row_swz1(int row) { return (row >> 1) & 3; }
-
 template <int EPI>
 __global__ __launch_bounds__(NT1, 4) void conv1x1_bf16_kernel(Conv1Args p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -70,8 +56,7 @@ __global__ __launch_bounds__(NT1, 4) void conv1x1_bf16_kernel(Conv1Args p) {
   const int HWo = p.Hout * p.Wout;
   int wg = blockIdx.x;
   {
-    const int nwg = gridDim.x, q = nwg >> 3, rem = nwg & 7, x = wg & 7, k = wg >> 3;
-    wg = (x < rem ? x * (q + 1) : rem * (q + 1) + (x - rem) * q) + k;
+    wg = xcd_band_remap(wg, gridDim.x);
   }
   const int nt = wg % n_tiles;
   const int mt = wg / n_tiles;
@@ -95,7 +80,7 @@ __global__ __launch_bounds__(NT1, 4) void conv1x1_bf16_kernel(Conv1Args p) {
     const int op = p0 + P;                                                   \
     const int oy = op / p.Wout, ox = op - oy * p.Wout;                       \
     const int pix = oy * p.stride * p.Win + ox * p.stride;                   \
-    const int sub = (g & 3) ^ row_swz1(P);                                   \
+    const int sub = (g & 3) ^ row_swz(P);                                   \
     a_b0##J = (pix * p.ps0 + sub * 8) * 2;                                   \
     a_b1##J = (pix * p.ps1 + sub * 8) * 2;                                   \
   }
@@ -122,13 +107,13 @@ __global__ __launch_bounds__(NT1, 4) void conv1x1_bf16_kernel(Conv1Args p) {
     // ADDRESSES of the two candidates and parks those in scratch - a flat load behind s_waitcnt vmcnt(0) in every K-step)
     const int vo0 = first ? a_b00 : a_b10, vo1 = first ? a_b01 : a_b11;
     if (first) {
-      dma16_1(rs0, st + wave * 1024, vo0, soff);
-      dma16_1(rs0, st + (wave + 8) * 1024, vo1, soff);
+      dma16(rs0, st + wave * 1024, vo0, soff);
+      dma16(rs0, st + (wave + 8) * 1024, vo1, soff);
     } else {
-      dma16_1(rs1, st + wave * 1024, vo0, soff);
-      dma16_1(rs1, st + (wave + 8) * 1024, vo1, soff);
+      dma16(rs1, st + wave * 1024, vo0, soff);
+      dma16(rs1, st + (wave + 8) * 1024, vo1, soff);
     }
-    dma16_1(rsw, st + A1_BYTES + wave * 1024, tid16, i_w);
+    dma16(rsw, st + A1_BYTES + wave * 1024, tid16, i_w);
     i_w += (int)w_tile_stride;
     i_slot = i_slot == RING1 - 1 ? 0 : i_slot + 1;
     if (++i_cc == CC) {
@@ -141,11 +126,11 @@ __global__ __launch_bounds__(NT1, 4) void conv1x1_bf16_kernel(Conv1Args p) {
         c20 = 0, c21 = 0, c22 = 0, c23 = 0, c30 = 0, c31 = 0, c32 = 0, c33 = 0;
   auto a_addr = [&](int i) {
     const int P = wm * 64 + i * 16 + r16;
-    return P * 64 + ((q16 ^ row_swz1(P)) << 4);
+    return P * 64 + ((q16 ^ row_swz(P)) << 4);
   };
   auto b_addr = [&](int j) {
     const int n = wn * 64 + j * 16 + r16;
-    return A1_BYTES + n * 64 + ((q16 ^ row_swz1(n)) << 4);
+    return A1_BYTES + n * 64 + ((q16 ^ row_swz(n)) << 4);
   };
   const int aa0 = a_addr(0), aa1 = a_addr(1), aa2 = a_addr(2), aa3 = a_addr(3);
   const int ba0 = b_addr(0), ba1 = b_addr(1), ba2 = b_addr(2), ba3 = b_addr(3);
@@ -172,13 +157,13 @@ __global__ __launch_bounds__(NT1, 4) void conv1x1_bf16_kernel(Conv1Args p) {
   // ---- pipeline: stages s+1 and s+2 in flight while stage s is consumed (3 DMA instructions per wave and stage)
   issue();
   if (S > 1) issue();
-  if (S > 1) WAIT_VM1(3); else WAIT_VM1(0);
-  BARRIER1();
+  if (S > 1) WAIT_VM(3); else WAIT_VM(0);
+  BARRIER();
   for (int s = 0; s < S; ++s) {
     if (s + 2 < S) issue();
     compute();
-    if (s + 2 < S) WAIT_VM1(3); else WAIT_VM1(0);   // stage s+1 has landed (this wave's part; the barrier covers the rest)
-    BARRIER1();
+    if (s + 2 < S) WAIT_VM(3); else WAIT_VM(0);   // stage s+1 has landed (this wave's part; the barrier covers the rest)
+    BARRIER();
   }
 
   // ---- epilogue (conv1x1_epilogue.hpp): transpose through LDS, then 16-byte channel-contiguous traffic only

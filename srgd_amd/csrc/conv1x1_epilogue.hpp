@@ -4,7 +4,7 @@
 // stores, residual add, the ResnetBlock's GroupNorm2 + SiLU tail (reference model.py:250-259, :285), PixelShuffle scatter + SiLU
 // (:70-98), the fused 1x1 output convolution (:776-777), the optional MX-fp8 twin - is written once.
 #pragma once
-#include "kernels.hpp"
+#include "conv_common.hpp"
 
 namespace srgd {
 namespace {

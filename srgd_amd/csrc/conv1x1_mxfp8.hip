@@ -46,10 +46,6 @@ template <int BM> struct QShape {
   static_assert(LDS >= BM * EPI_ROW && LDS <= 160 * 1024, "conv1x1_mxfp8: LDS budget");
 };
 
-typedef __attribute__((address_space(3))) void* lds_ptrq;
-typedef int v8iq __attribute__((ext_vector_type(8)));
-typedef int v4iq __attribute__((ext_vector_type(4)));
-
 struct Conv1QArgs {
   const unsigned char* q0; const unsigned char* s0; int C0;     // MX-fp8 source 0: e4m3 [B,Hin,Win,C0], E8M0 [B,Hin,Win,C0/32]
   const unsigned char* q1; const unsigned char* s1; int C1;     // optional source 1 (channel concat; 1x1 taps only)
@@ -64,13 +60,6 @@ struct Conv1QArgs {
   unsigned char* oq; unsigned char* os;
   float* eps4; const float* fin_w; const float* fin_b;
 };
-
-#define WAIT_VMQ(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
-#define BARRIERQ()                       \
-  do {                                   \
-    __builtin_amdgcn_s_barrier();        \
-    __builtin_amdgcn_sched_barrier(0);   \
-  } while (0)
 
 template <int EPI, int BM>
 __global__ __launch_bounds__(BM * 2, 2) void conv1x1_mxfp8_kernel(Conv1QArgs p) {
@@ -87,8 +76,7 @@ __global__ __launch_bounds__(BM * 2, 2) void conv1x1_mxfp8_kernel(Conv1QArgs p) 
   const int HWo = p.Hout * p.Wout;
   int wg = blockIdx.x;
   {
-    const int nwg = gridDim.x, q = nwg >> 3, rem = nwg & 7, x = wg & 7, k = wg >> 3;
-    wg = (x < rem ? x * (q + 1) : rem * (q + 1) + (x - rem) * q) + k;
+    wg = xcd_band_remap(wg, gridDim.x);
   }
   const int nt = wg % n_tiles;
   const int mt = wg / n_tiles;
@@ -142,7 +130,7 @@ __global__ __launch_bounds__(BM * 2, 2) void conv1x1_mxfp8_kernel(Conv1QArgs p) 
     char* st = smem + i_slot * STAGEQ;
     const int m1 = first ? 0 : -1;
     const int v0 = a00 + (d10 & m1), v1 = a01 + (d11 & m1), v2 = a02 + (d12 & m1), v3 = a03 + (d13 & m1), vs = as0 + (ds1 & m1);
-#define K_DMAQ(RS_, DST_, VO_, SO_, SZ_) __builtin_amdgcn_raw_ptr_buffer_load_lds(RS_, (lds_ptrq)(DST_), SZ_, VO_, SO_, 0, 0)
+#define K_DMAQ(RS_, DST_, VO_, SO_, SZ_) __builtin_amdgcn_raw_ptr_buffer_load_lds(RS_, (lds_ptr)(DST_), SZ_, VO_, SO_, 0, 0)
     const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void*)(first ? qb0 : qb1), 0, first ? qn0 : qn1, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(first ? sb0 : sb1), 0, (first ? qn0 : qn1) >> 5, 0x00020000);
     K_DMAQ(rq, st + wave * 1024, v0, soff, 16);
@@ -176,13 +164,13 @@ __global__ __launch_bounds__(BM * 2, 2) void conv1x1_mxfp8_kernel(Conv1QArgs p) 
   auto compute = [&]() __attribute__((always_inline)) {
     const char* st = smem + c_slot * STAGEQ;
     c_slot = c_slot == RINGQ - 1 ? 0 : c_slot + 1;
-    v8iq a0, a1, a2, a3, b0, b1, b2, b3;
+    v8i a0, a1, a2, a3, b0, b1, b2, b3;
     int sa0, sa1, sa2, sa3;
 #define K_LOADQ(DST_, BASE_, I_)                                                     \
     {                                                                                   \
-      const v4iq lo = *reinterpret_cast<const v4iq*>(st + BASE_ + I_ * 2048);           \
-      const v4iq hi = *reinterpret_cast<const v4iq*>(st + (BASE_ ^ 64) + I_ * 2048);    \
-      DST_ = v8iq{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};              \
+      const v4i lo = *reinterpret_cast<const v4i*>(st + BASE_ + I_ * 2048);           \
+      const v4i hi = *reinterpret_cast<const v4i*>(st + (BASE_ ^ 64) + I_ * 2048);    \
+      DST_ = v8i{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};              \
     }
     K_LOADQ(b0, bb, 0) K_LOADQ(b1, bb, 1) K_LOADQ(b2, bb, 2) K_LOADQ(b3, bb, 3)
     const int sbw = *reinterpret_cast<const int*>(st + bsb);
@@ -216,13 +204,13 @@ __global__ __launch_bounds__(BM * 2, 2) void conv1x1_mxfp8_kernel(Conv1QArgs p) 
     static_assert(Q::DMA_PER_STAGE == 8 || RINGQ != 3, "counted wait below");
     issue();
     if (S > 1) issue();
-    if (S > 1) WAIT_VMQ(8); else WAIT_VMQ(0);
-    BARRIERQ();
+    if (S > 1) WAIT_VM(8); else WAIT_VM(0);
+    BARRIER();
     for (int s = 0; s < S; ++s) {
       if (s + 2 < S) issue();
       compute();
-      if (s + 2 < S) WAIT_VMQ(8); else WAIT_VMQ(0);   // stage s+1 has landed (this wave's part; the barrier covers the rest)
-      BARRIERQ();
+      if (s + 2 < S) WAIT_VM(8); else WAIT_VM(0);   // stage s+1 has landed (this wave's part; the barrier covers the rest)
+      BARRIER();
     }
   } else {
     // ---- 2-deep ring: both slots are requested up front (the streaming layers have S = 2: nothing else ever is), afterwards
@@ -230,12 +218,12 @@ __global__ __launch_bounds__(BM * 2, 2) void conv1x1_mxfp8_kernel(Conv1QArgs p) 
     static_assert(Q::DMA_PER_STAGE == 10 || RINGQ != 2, "counted wait below");
     issue();
     if (S > 1) issue();
-    if (S > 1) WAIT_VMQ(10); else WAIT_VMQ(0);
-    BARRIERQ();
+    if (S > 1) WAIT_VM(10); else WAIT_VM(0);
+    BARRIER();
     for (int s = 0; s < S; ++s) {
       compute();
-      WAIT_VMQ(0);                                   // stage s+1 (the only one in flight) has landed
-      BARRIERQ();                                    // ... for every wave, and every wave is done reading stage s
+      WAIT_VM(0);                                   // stage s+1 (the only one in flight) has landed
+      BARRIER();                                    // ... for every wave, and every wave is done reading stage s
       if (s + 2 < S) issue();
     }
   }

@@ -30,7 +30,7 @@
 #include <cmath>
 #include <cstdlib>
 
-#include "kernels.hpp"
+#include "conv_common.hpp"
 
 namespace srgd {
 namespace {
@@ -44,10 +44,6 @@ constexpr int RING = 3;
 constexpr int STG_BYTES = 2048;                // per-wave staging area of the store transposition (epilogue)
 constexpr int LDS_BYTES = RING * STAGE + (NT / 64) * STG_BYTES;   // 147,456 + 16,384 = 163,840: all of a CU's LDS, one workgroup per CU
 enum { SEPI_PLAIN = 0, SEPI_RESIDUAL = 1, SEPI_PS_SILU = 2, SEPI_RMS_RESIDUAL = 3, SEPI_GNTAIL = 4 };
-
-typedef __attribute__((address_space(3))) void* lds_ptr;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 struct Split1Args {
   const float* in0; const float* in1; int C0, C1;
@@ -65,28 +61,7 @@ struct Split1Args {
   const float* rms_g;     // SEPI_RMS_RESIDUAL: [Cout] gain of the RMSNorm applied to the result, already times sqrt(Cout)
 };
 
-#define WAIT_VM(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
-#define BARRIER()                        \
-  do {                                   \
-    __builtin_amdgcn_s_barrier();        \
-    __builtin_amdgcn_sched_barrier(0);   \
-  } while (0)
-
-// 8 fp32 (two 16-byte loads) -> the hi and lo f16 fragments (finite values saturate, non-finite ones become NaN, as conv3x3_split.hip)
-__device__ __forceinline__ void split8(const u32x4& r0, const u32x4& r1, u32x4& hi, u32x4& lo) {
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const unsigned ua = k < 2 ? r0[2 * k] : r1[2 * k - 4], ub = k < 2 ? r0[2 * k + 1] : r1[2 * k - 3];
-    const float a = sat_f16_keep_nonfinite(__uint_as_float(ua));
-    const float b = sat_f16_keep_nonfinite(__uint_as_float(ub));
-    const f16x2 h = __builtin_convertvector(f32x2{a, b}, f16x2);
-    const f32x2 hf = __builtin_convertvector(h, f32x2);
-    const f16x2 l = __builtin_convertvector(f32x2{a - hf[0], b - hf[1]}, f16x2);
-    hi[k] = __builtin_bit_cast(unsigned, h);
-    lo[k] = __builtin_bit_cast(unsigned, l);
-  }
-}
-
+// (fragments are split with split8<true>, conv_common.hpp: finite values saturate, non-finite ones become NaN)
 // RMS_IN: the convolution reads RMSNorm(x) (reference RMSNorm.forward model.py:206-207 ahead of to_qkv, :312 / :349): the gain and
 // sqrt(C) are folded into the weights on the host, and the per-pixel 1 / max(||x||, 1e-12) - a wave sees every channel of its 32
 // pixels on their way through the K loop - multiplies the accumulators in the epilogue.  SEPI_RMS_RESIDUAL (one n-tile: Cout ==
@@ -110,8 +85,7 @@ __global__ __launch_bounds__(NT, 2) void conv1x1_split_kernel(Split1Args p) {
   // tiles of one workgroup stay on its XCD's band.
   const int T = p.n_wg_tiles;
   auto tile_of = [&](int v, int& nt_, int& b_, int& p0_) {
-    const int q = T >> 3, rem = T & 7, x = v & 7, k = v >> 3;
-    const int wg = (x < rem ? x * (q + 1) : rem * (q + 1) + (x - rem) * q) + k;
+    const int wg = xcd_band_remap(v, T);
     nt_ = wg % n_tiles;
     const int mt = wg / n_tiles, tpi = HWo / BM;     // HWo % 256 == 0: a tile lies in one image (32-bit arithmetic throughout)
     b_ = mt / tpi;
@@ -218,8 +192,8 @@ __global__ __launch_bounds__(NT, 2) void conv1x1_split_kernel(Split1Args p) {
     const u32x4 x00 = *reinterpret_cast<const u32x4*>(st + a_row0 + a_c0), x01 = *reinterpret_cast<const u32x4*>(st + a_row0 + a_c1);
     const u32x4 x10 = *reinterpret_cast<const u32x4*>(st + a_row1 + a_c0), x11 = *reinterpret_cast<const u32x4*>(st + a_row1 + a_c1);
     if constexpr (RMS_IN) { ss0 = sumsq8(x00, x01, ss0); ss1 = sumsq8(x10, x11, ss1); }
-    split8(x00, x01, ah0, al0);
-    split8(x10, x11, ah1, al1);
+    split8<true>(x00, x01, ah0, al0);
+    split8<true>(x10, x11, ah1, al1);
 #define K_COL(J, C0_, C1_)                                                                         \
   {                                                                                                \
     const u32x4 bh = *reinterpret_cast<const u32x4*>(st + b_base + J * 1024);                      \
@@ -326,8 +300,9 @@ __global__ __launch_bounds__(NT, 2) void conv1x1_split_kernel(Split1Args p) {
   }
   if (EPI == SEPI_GNTAIL) {
     // out = conv(x) + silu(a[b][c] * h + b[b][c]): the second GroupNorm + SiLU of a ResnetBlock and its residual add folded into the
-    // 1x1 res_conv (reference model.py:250-259, :283-285); h may alias out (a lane reads exactly the addresses it writes)
-    // (block 0's tail operand, then block 1's in the same registers: all of it ahead of the first store, which comes at the very end)
+    // 1x1 res_conv (reference model.py:250-259, :283-285); h may alias out: a wave reads and writes only its own 32 pixel rows of the
+    // tile (the store transposition below is wave-private), and all of its loads of h - block 0's tail operand, then block 1's in
+    // the same registers - are consumed ahead of its first store, which comes at the very end
     f32x4 r_[8], a_[8], b_[8];
     const float* ga = p.gn_a + (size_t)b * p.Cout + n0 + q16 * 32;
     const float* gb = p.gn_b + (size_t)b * p.Cout + n0 + q16 * 32;

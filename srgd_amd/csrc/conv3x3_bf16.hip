@@ -33,7 +33,7 @@
 // power-limited 1.7 GHz.  Diagnostic builds (tools/build_variant.py only): -DSRGD_CONV3_STAMPS=1 adds per-phase s_memtime stamps.
 #include <cstdlib>
 
-#include "kernels.hpp"
+#include "conv_common.hpp"
 
 #ifndef SRGD_CONV3_STAMPS
 #define SRGD_CONV3_STAMPS 0
@@ -56,13 +56,6 @@ constexpr int COEF_BYTES = 2 * 256;            // GNIN: 32 scales | 32 shifts (f
 constexpr bool STAMPS = SRGD_CONV3_STAMPS != 0;
 static_assert(8 * 16 * 144 <= A_BYTES, "store staging fits the idle A buffer");
 
-typedef __attribute__((address_space(3))) void* lds_ptr;
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, char* lds_wave_base, int voffset, int soffset = 0) {
-  // LDS destination = wave-uniform base + lane * 16; voffset per lane (VGPR), soffset wave-uniform (SGPR)
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr)lds_wave_base, 16, voffset, soffset, 0, 0);
-}
-
 struct Conv3Args {
   const bf16* in0; const bf16* in1; int C0, C1;
   int B, H, W;
@@ -79,20 +72,6 @@ struct Conv3Args {
 __device__ unsigned long long g_conv3_timeline[(size_t)STAMP_REC * STAMP_MAX_WAVES];       // stamps.hpp
 #endif
 
-#define WAIT_VM(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
-// Raw barrier (no vmcnt drain: LDS-DMA prefetches stay in flight) fenced for the instruction scheduler:
-// s_barrier is IntrNoMem to LLVM, so without sched_barrier(0) the machine scheduler hoists the next step's
-// ds_reads above it - a read of a buffer whose DMA other waves have not yet waited for.
-#define BARRIER()                        \
-  do {                                   \
-    __builtin_amdgcn_s_barrier();        \
-    __builtin_amdgcn_sched_barrier(0);   \
-  } while (0)
-
-// Row swizzle: chunk ^= (row >> 1) & 3 for the 16x16x32 operand pattern (16 rows x 4 chunks per ds_read_b128) - conflict-free
-// for its lane groups at every tap shift (checked exhaustively on the bank model).
-__device__ __forceinline__ int row_swz(int row) { return (row >> 1) & 3; }
-
 template <bool STATS, bool GNIN>
 __global__ __launch_bounds__(NT3, 4) void conv3x3_bf16_kernel(Conv3Args p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -102,26 +81,10 @@ __global__ __launch_bounds__(NT3, 4) void conv3x3_bf16_kernel(Conv3Args p) {
   const int wm = wave >> 1, wn = wave & 1;
   const int r16 = lane & 15, q16 = lane >> 4;        // fragment row / 8-channel chunk
 
-  // ---- tile coordinates (XCD-aware remap: blocks b, b+8, ... share an XCD -> give each XCD a contiguous band)
-  const int n_tiles = p.Cout / BN3;
-  const int tiles_x = p.W / PW, tiles_y = p.H / PH;
-  const int m_tiles = p.B * tiles_y * tiles_x;
-  const int nwg = m_tiles * n_tiles;
-  int wg = blockIdx.x;
-  // Tile map, measured with the L2's own counters (round 5, profiles/r5/conv3x3_bf16_tcc_*.txt; 1024 -> 1024 @32^2, 125 tiles):
-  // this map - n-tiles fastest inside an XCD's band, so the 64 workgroups an XCD runs at a time are 8 m-tiles x 8 n-tiles - reads
-  // 112.7 M 128-byte lines per launch with an 81 % L2 hit rate (23.4 M misses = 3.0 GB from the Infinity Cache).  Pinning one
-  // n-tile per XCD makes the weight stream L2-resident and every XCD read every halo patch: 21.4 M misses, the same clock and
-  // throughput.  Blocks of 32 m-tiles x 2 n-tiles cut the misses to 17.1 M (-27 %): clock 1.653 vs 1.648 GHz, +0.4 % (noise).
-  // Non-temporal halo DMAs and output stores: 29-36 M misses, 1.55-1.59 GHz, -4 ... -12 %.  The kernel's clock does not follow
-  // its traffic beyond L2 within what a tile map can change, so the simplest map stays.
-  const int q = nwg >> 3, rem = nwg & 7, x = wg & 7, k = wg >> 3;
-  wg = (x < rem ? x * (q + 1) : rem * (q + 1) + (x - rem) * q) + k;
-  const int nt = wg % n_tiles, mt = wg / n_tiles;
-  const int b = mt / (tiles_y * tiles_x);
-  const int trem = mt - b * tiles_y * tiles_x;
-  const int ty = trem / tiles_x, tx = trem - ty * tiles_x;
-  const int y0 = ty * PH, x0 = tx * PW;
+  // ---- tile coordinates (conv_common.hpp: XCD-aware remap - each XCD a contiguous band of tiles -, n-tiles fastest)
+  int n_tiles, tiles_x, tiles_y, nt, b, trem, y0, x0;
+  static_assert(PH == 8 && BN3 == 128, "patch_tile_decode: 8-row patches, 128-channel tiles");
+  patch_tile_decode<PW>(blockIdx.x, p.Cout, p.W, p.H, p.B, n_tiles, tiles_x, tiles_y, nt, b, trem, y0, x0);
   const int Cin = p.C0 + p.C1;
   const int CC = Cin / KC;
 
@@ -464,7 +427,7 @@ __global__ __launch_bounds__(NT3, 4) void conv3x3_bf16_kernel(Conv3Args p) {
     float a2 = row16_sum((s2v[0] + s2v[1]) + (s2v[2] + s2v[3]));
     if (cpg >= 32) { a1 = xor16_sum(a1); a2 = xor16_sum(a2); }
     if (cpg >= 64) { a1 = xor32_sum(a1); a2 = xor32_sum(a2); }
-    const int rows_per_group = cpg >= 64 ? 4 : cpg >> 4;  // lane rows (16 channels each) that share a group: 1, 2 or 4
+    const int rows_per_group = cpg >= 64 ? 4 : cpg >> 4;    // (a copy of gn_partial_store<BN3, 4>, conv_common.hpp: the call changed 36 instructions here)
     if (r16E == 0 && (q16E & (rows_per_group - 1)) == 0) {
       const int tpg = cpg >= BN3 ? cpg / BN3 : 1;         // 128-channel tiles per group
       const int wpt = cpg >= BN3 ? 8 : 4;                 // contributing waves per tile
@@ -487,7 +450,9 @@ __global__ __launch_bounds__(NT3, 4) void conv3x3_bf16_kernel(Conv3Args p) {
 
 }  // namespace
 
-bool conv3x3_bf16_eligible(const ConvArgs& a) {
+// The 8 x 32-patch 3x3 kernels (this one, conv3x3_split, conv3x3_mx2) take the same shapes; they differ in the bytes of a tensor
+// element and of a weight unit (one (tap, chunk, n-tile) step of the weight stream).
+bool conv3x3_patch_eligible(const ConvArgs& a, int elem_bytes, int weight_unit_bytes) {
   if (a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1 || a.mode != CONV_PLAIN || a.residual || a.gn_res_src) return false;
   if (a.ps0 != a.C0 || (a.C1 && a.ps1 != a.C1)) return false;
   if (a.C0 % KC || a.C1 % KC || a.Cout % BN3 || a.Cout != a.CoutPad) return false;
@@ -498,40 +463,23 @@ bool conv3x3_bf16_eligible(const ConvArgs& a) {
     if (!(cpg == 16 || cpg == 32 || cpg == 64 || cpg % BN3 == 0)) return false;
   }
   // per-image byte offsets must fit the 32-bit buffer offset
-  if ((size_t)a.Hin * a.Win * (size_t)std::max(a.C0, a.C1) * 2 >= (1ull << 31)) return false;
-  if ((size_t)a.Hin * a.Win * (size_t)a.Cout * 2 >= (1ull << 31)) return false;
-  if ((size_t)9 * ((a.C0 + a.C1) / KC) * (a.Cout / BN3) * B_BYTES >= (1ull << 31)) return false;
+  if ((size_t)a.Hin * a.Win * (size_t)std::max(a.C0, a.C1) * elem_bytes >= (1ull << 31)) return false;
+  if ((size_t)a.Hin * a.Win * (size_t)a.Cout * elem_bytes >= (1ull << 31)) return false;
+  if ((size_t)9 * ((a.C0 + a.C1) / KC) * (a.Cout / BN3) * weight_unit_bytes >= (1ull << 31)) return false;
   return true;
 }
+bool conv3x3_bf16_eligible(const ConvArgs& a) { return conv3x3_patch_eligible(a, 2, B_BYTES); }
 
-// GroupNorm partial slots per (sample, group): one per contributing wave (see the kernel's epilogue)
-int conv3x3_bf16_stats_slots(const ConvArgs& a) {
-  if (a.groups <= 0) return 0;
-  const int cpg = a.Cout / a.groups;
-  return (a.Hin / PH) * (a.Win / PW) * (cpg >= BN3 ? (cpg / BN3) * 8 : 4);
-}
+// GroupNorm partial slots per (sample, group): one per contributing wave (gn_partial_store, conv_common.hpp)
+static_assert(PH == 8 && PW == 32 && BN3 == 128, "conv3x3_stats_slots counts 8 x 32 pixel patches and 128-channel tiles");
+int conv3x3_bf16_stats_slots(const ConvArgs& a) { return conv3x3_stats_slots(a, 4); }
 
 // Host-side packing: OIHW fp32 -> [tap][cc][ntile][128 rows][64 B swizzled] bf16 (the LDS image of each K-step tile).
 // Row order inside a tile: regepi_row_channel (common.hpp) - the accumulator registers of a lane are 16 consecutive channels.
-
 void pack_conv3x3_bf16(const float* src_oihw, int Cin, int Cout, std::vector<unsigned short>& out,
                        unsigned short (*to_bf16)(float)) {
-  const int CC = Cin / KC, NTL = Cout / BN3;
-  out.assign((size_t)9 * CC * NTL * BN3 * KC, 0);
-  for (int tap = 0; tap < 9; ++tap)
-    for (int cc = 0; cc < CC; ++cc)
-      for (int nt = 0; nt < NTL; ++nt) {
-        unsigned short* tile = out.data() + ((size_t)(tap * CC + cc) * NTL + nt) * BN3 * KC;
-        for (int n = 0; n < BN3; ++n)
-          for (int c = 0; c < 4; ++c) {
-            const int cs = c ^ ((n >> 1) & 3);  // stored chunk position (row_swz of the kernel)
-            for (int e = 0; e < 8; ++e) {
-              const int ci = cc * KC + c * 8 + e, o = nt * BN3 + regepi_row_channel(n);
-              const float v = src_oihw[(((size_t)o * Cin + ci) * 3 + tap / 3) * 3 + tap % 3];
-              tile[n * KC + cs * 8 + e] = to_bf16(v);
-            }
-          }
-      }
+  out.assign((size_t)9 * (Cin / KC) * (Cout / BN3) * BN3 * KC, 0);
+  conv3x3_weight_walk(src_oihw, Cin, Cout, [&](size_t tile, int, int, int pos, float v) { out[tile * BN3 * KC + pos] = to_bf16(v); });
 }
 
 int conv3x3_bf16(const ConvArgs& a, const void* packed_w, const float* gn_in_a, const float* gn_in_b,

@@ -36,7 +36,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "kernels.hpp"
+#include "conv_common.hpp"
 
 namespace srgd {
 namespace {
@@ -60,11 +60,6 @@ constexpr int B_RING = 4;                      // two tap pairs: the one being c
 constexpr int LDS_BYTES = 2 * A_BUF + B_RING * B_UNIT;   // 161,792
 constexpr int COEF_BYTES = 2 * 256;            // GNIN: 32 scales | 32 shifts (fp32) of a channel chunk, double-buffered
 
-typedef __attribute__((address_space(3))) void* lds_ptr;
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef int v4i __attribute__((ext_vector_type(4)));
-
 struct Mx2Args {
   const float* in0; const float* in1; int C0, C1;
   int B, H, W;
@@ -78,26 +73,15 @@ struct Mx2Args {
   int gn_in_b_off;        // byte offset of the shift array from gn_in_a (one allocation)
 };
 
-#define WAIT_VM(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
-#define BARRIER()                        \
-  do {                                   \
-    __builtin_amdgcn_s_barrier();        \
-    __builtin_amdgcn_sched_barrier(0);   \
-  } while (0)
-
-__device__ __forceinline__ int row_swz(int row) { return (row >> 1) & 3; }
-
 // 8 fp32 -> f16 hi (packed, for the 16-bit image) and the hi / lo VALUES as floats for the e4m3 quantisation; lo = x - hi in fp32
 // (not rounded to f16 first: at e4m3's 4 significand bits that rounding is invisible, and it costs three conversions per pair)
 __device__ __forceinline__ void split8f(const u32x4& r0, const u32x4& r1, u32x4& hi, float (&yh)[8], float (&yl)[8]) {
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const unsigned ua = k < 2 ? r0[2 * k] : r1[2 * k - 4], ub = k < 2 ? r0[2 * k + 1] : r1[2 * k - 3];
-    const float a = sat_f16_keep_nonfinite(__uint_as_float(ua));
-    const float b = sat_f16_keep_nonfinite(__uint_as_float(ub));
-    const f16x2 h = __builtin_convertvector(f32x2{a, b}, f16x2);
-    const f32x2 hf = __builtin_convertvector(h, f32x2);
-    hi[k] = __builtin_bit_cast(unsigned, h);
+    float a = __uint_as_float(ua), b = __uint_as_float(ub);
+    f32x2 hf;
+    hi[k] = split_hi_f16(a, b, hf);
     yh[2 * k] = hf[0]; yh[2 * k + 1] = hf[1];
     yl[2 * k] = a - hf[0]; yl[2 * k + 1] = b - hf[1];
   }
@@ -134,21 +118,10 @@ __global__ __launch_bounds__(NT3, 2) void conv3x3_mx2_kernel(Mx2Args p) {
   const int wm = wave >> 1, wn = wave & 1;
   const int r16 = lane & 15, q16 = lane >> 4;
 
-  // ---- tile coordinates (conv3x3_split.hip)
-  const int n_tiles = p.Cout / BN3;
-  const int tiles_x = p.W / PW, tiles_y = p.H / PH;
-  const int m_tiles = p.B * tiles_y * tiles_x;
-  const int nwg = m_tiles * n_tiles;
-  int wg = blockIdx.x;
-  {
-    const int q = nwg >> 3, rem = nwg & 7, x = wg & 7, k = wg >> 3;
-    wg = (x < rem ? x * (q + 1) : rem * (q + 1) + (x - rem) * q) + k;
-  }
-  const int nt = wg % n_tiles, mt = wg / n_tiles;
-  const int b = mt / (tiles_y * tiles_x);
-  const int trem = mt - b * tiles_y * tiles_x;
-  const int ty = trem / tiles_x, tx = trem - ty * tiles_x;
-  const int y0 = ty * PH, x0 = tx * PW;
+  // ---- tile coordinates (conv_common.hpp: XCD-aware remap - each XCD a contiguous band of tiles -, n-tiles fastest)
+  int n_tiles, tiles_x, tiles_y, nt, b, trem, y0, x0;
+  static_assert(PH == 8 && BN3 == 128, "patch_tile_decode: 8-row patches, 128-channel tiles");
+  patch_tile_decode<PW>(blockIdx.x, p.Cout, p.W, p.H, p.B, n_tiles, tiles_x, tiles_y, nt, b, trem, y0, x0);
   const int Cin = p.C0 + p.C1;
   const int CC = Cin / KC;
 
@@ -219,7 +192,7 @@ __global__ __launch_bounds__(NT3, 2) void conv3x3_mx2_kernel(Mx2Args p) {
     const f32x4 gb0 = *reinterpret_cast<const f32x4*>(sc + 128), gb1 = *reinterpret_cast<const f32x4*>(sc + 144);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const unsigned u0 = r0[k], u1 = r1[k];       // (element copied out first: conv3x3_split.hip)
+      const unsigned u0 = r0[k], u1 = r1[k];       // (elements copied out first: the note in conv_common.hpp; act4 there is the same arithmetic, one vector at a time)
       const float t0 = __builtin_fmaf(ga0[k], __uint_as_float(u0), gb0[k]), t1 = __builtin_fmaf(ga1[k], __uint_as_float(u1), gb1[k]);
       r0[k] = __float_as_uint(t0 * __builtin_amdgcn_rcpf(1.0f + __expf(-t0)));
       r1[k] = __float_as_uint(t1 * __builtin_amdgcn_rcpf(1.0f + __expf(-t1)));
@@ -475,7 +448,7 @@ __global__ __launch_bounds__(NT3, 2) void conv3x3_mx2_kernel(Mx2Args p) {
     float a2 = row16_sum((s2v[0] + s2v[1]) + (s2v[2] + s2v[3]));
     if (cpg >= 32) { a1 = xor16_sum(a1); a2 = xor16_sum(a2); }
     if (cpg >= 64) { a1 = xor32_sum(a1); a2 = xor32_sum(a2); }
-    const int rows_per_group = cpg >= 64 ? 4 : cpg >> 4;
+    const int rows_per_group = cpg >= 64 ? 4 : cpg >> 4;    // (a copy of gn_partial_store<BN3, 4>, conv_common.hpp: the call changed 16 instructions here)
     if (r16E == 0 && (q16E & (rows_per_group - 1)) == 0) {
       const int tpg = cpg >= BN3 ? cpg / BN3 : 1;
       const int wpt = cpg >= BN3 ? 8 : 4;
@@ -488,21 +461,6 @@ __global__ __launch_bounds__(NT3, 2) void conv3x3_mx2_kernel(Mx2Args p) {
   }
 }
 
-float f16_bits_to_f32_mx2(unsigned short h) {
-  const uint32_t sign = (uint32_t)(h & 0x8000u) << 16;
-  const int e = (h >> 10) & 31;
-  const uint32_t m = h & 0x3ffu;
-  float v;
-  if (e == 0) v = std::ldexp((float)m, -24);
-  else if (e == 31) v = m ? NAN : INFINITY;
-  else v = std::ldexp((float)(m | 0x400u), e - 25);
-  uint32_t u;
-  std::memcpy(&u, &v, 4);
-  u |= sign;
-  std::memcpy(&v, &u, 4);
-  return v;
-}
-
 }  // namespace
 
 static size_t conv3x3_mx2_packed_bytes(int Cin, int Cout) { return (size_t)9 * (Cin / KC) * (Cout / BN3) * B_UNIT; }
@@ -511,37 +469,27 @@ static size_t conv3x3_mx2_packed_bytes(int Cin, int Cout) { return (size_t)9 * (
 // and Q(w_lo) (p = 1), 16 bytes per row and plane | scale bytes [p][wn][r16][J] (row n = 64 wn + 16 J + r16); blocks = the 32 input
 // channels of the chunk, the engine's scale rule (mx_block_exponent)
 void pack_conv3x3_mx2(const float* src_oihw, int Cin, int Cout, float scale, std::vector<unsigned char>& out) {
-  const int CC = Cin / KC, NTL = Cout / BN3;
   out.assign(conv3x3_mx2_packed_bytes(Cin, Cout), 0);
-  for (int tap = 0; tap < 9; ++tap)
-    for (int cc = 0; cc < CC; ++cc)
-      for (int nt = 0; nt < NTL; ++nt) {
-        unsigned char* u = out.data() + ((size_t)(tap * CC + cc) * NTL + nt) * B_UNIT;
-        unsigned short* hi_t = reinterpret_cast<unsigned short*>(u);
-        for (int n = 0; n < BN3; ++n) {
-          const int o = nt * BN3 + regepi_row_channel(n);
-          float vh[KC], vl[KC];
-          for (int k = 0; k < KC; ++k) {
-            const float v = src_oihw[(((size_t)o * Cin + cc * KC + k) * 3 + tap / 3) * 3 + tap % 3] * scale;
-            unsigned short hb, lb;
-            split_halves_host(v, true, &hb, &lb);
-            const int c = k >> 3, e = k & 7, cs = c ^ ((n >> 1) & 3);
-            hi_t[n * KC + cs * 8 + e] = hb;
-            vh[k] = f16_bits_to_f32_mx2(hb);
-            vl[k] = f16_bits_to_f32_mx2(lb);
-          }
-          for (int pr = 0; pr < 2; ++pr) {
-            const float* v = pr == 0 ? vh : vl;
-            float amax = 0.f;
-            for (int k = 0; k < KC; ++k) amax = std::max(amax, std::fabs(v[k]));
-            const int ex = mx_block_exponent(amax);
-            const float inv = std::ldexp(1.0f, -ex);
-            for (int k = 0; k < KC; ++k)
-              u[B_Q + (pr * 2 + (k >> 4)) * B_PLANE + n * 16 + (k & 15)] = e4m3_encode(v[k] * inv);
-            u[B_SC + pr * 256 + ((n >> 6) * 16 + (n & 15)) * 4 + ((n >> 4) & 3)] = (unsigned char)(ex + 127);
-          }
-        }
-      }
+  float vh[KC], vl[KC];                                   // the hi / lo halves of the row being walked
+  conv3x3_weight_walk(src_oihw, Cin, Cout, [&](size_t tile, int n, int k, int pos, float w) {
+    unsigned char* u = out.data() + tile * B_UNIT;
+    unsigned short hb, lb;
+    split_halves_host(w * scale, true, &hb, &lb);
+    reinterpret_cast<unsigned short*>(u)[pos] = hb;
+    vh[k] = f16_bits_to_f32(hb);
+    vl[k] = f16_bits_to_f32(lb);
+    if (k < KC - 1) return;
+    for (int pr = 0; pr < 2; ++pr) {                      // the row is complete: its two e4m3 blocks and scale bytes
+      const float* v = pr == 0 ? vh : vl;
+      float amax = 0.f;
+      for (int i = 0; i < KC; ++i) amax = std::max(amax, std::fabs(v[i]));
+      const int ex = mx_block_exponent(amax);
+      const float inv = std::ldexp(1.0f, -ex);
+      for (int i = 0; i < KC; ++i)
+        u[B_Q + (pr * 2 + (i >> 4)) * B_PLANE + n * 16 + (i & 15)] = e4m3_encode(v[i] * inv);
+      u[B_SC + pr * 256 + ((n >> 6) * 16 + (n & 15)) * 4 + ((n >> 4) & 3)] = (unsigned char)(ex + 127);
+    }
+  });
 }
 
 int conv3x3_mx2(const ConvArgs& a, const void* packed_w, float w_inv_scale, hipStream_t st, const float* gn_in_a, const float* gn_in_b) {

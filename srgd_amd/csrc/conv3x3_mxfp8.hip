@@ -34,7 +34,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "kernels.hpp"
+#include "conv_common.hpp"
 #if SRGD_MXFP8_STAMPS
 #include "stamps.hpp"
 #endif
@@ -62,14 +62,7 @@ constexpr int QB_BYTES = QB_TILE + 512;          // + 512 scale bytes ([wn][r16]
 constexpr int QRING = 2;
 constexpr int QLDS = QA_BYTES + QAS_BYTES + QRING * QB_BYTES;   // 80,896 B: two workgroups per CU (<= 81,920)
 
-typedef __attribute__((address_space(3))) void* lds_ptr;
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef int v4i __attribute__((ext_vector_type(4)));
-
-// voffset: per-lane byte offset (VGPR); soffset: wave-uniform byte offset (SGPR) - keeping the uniform part out of the VGPRs
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, char* lds_wave_base, int voffset, int soffset = 0) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr)lds_wave_base, 16, voffset, soffset, 0, 0);
-}
+// (dma16: conv_common.hpp) the 4-byte-per-lane form, for the scale bytes
 __device__ __forceinline__ void dma4(__amdgpu_buffer_rsrc_t rsrc, char* lds_wave_base, int voffset, int soffset = 0) {
   __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr)lds_wave_base, 4, voffset, soffset, 0, 0);
 }
@@ -97,13 +90,6 @@ __device__ __forceinline__ int lane_id_opaque() {
   return l;
 }
 
-#define QWAIT_VM(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
-#define QBARRIER()                       \
-  do {                                   \
-    __builtin_amdgcn_s_barrier();        \
-    __builtin_amdgcn_sched_barrier(0);   \
-  } while (0)
-
 // 2 x 2 waves, wave tile 128 pixels x 64 channels (128 accumulators, <= 256 VGPRs), two waves per SIMD, two workgroups per CU.
 template <bool STATS>
 __global__ __launch_bounds__(NW * 64, NW / 2) void conv3x3_mxfp8_kernel(ConvQArgs p) {
@@ -123,22 +109,10 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void conv3x3_mxfp8_kernel(ConvQArg
   const int wm = wave >> 1, wn = wave & 1;
   const int r16 = lane & 15, g = lane >> 4;
 
-  // ---- tile coordinates (XCD-aware remap as in conv3x3_bf16.hip)
-  const int n_tiles = p.Cout / QBN;
-  const int tiles_x = p.W / QPW, tiles_y = p.H / QPH;
-  const int m_tiles = p.B * tiles_y * tiles_x;
-  const int nwg = m_tiles * n_tiles;
-  int wg = blockIdx.x;
-  {
-    const int q = nwg >> 3, rem = nwg & 7, x = wg & 7, k = wg >> 3;
-    wg = (x < rem ? x * (q + 1) : rem * (q + 1) + (x - rem) * q) + k;
-  }
-  const int nt = wg % n_tiles;
-  const int mt = wg / n_tiles;
-  const int b = mt / (tiles_y * tiles_x);
-  const int trem = mt - b * tiles_y * tiles_x;
-  const int ty = trem / tiles_x, tx = trem - ty * tiles_x;
-  const int y0 = ty * QPH, x0 = tx * QPW;
+  // ---- tile coordinates (conv_common.hpp: XCD-aware remap - each XCD a contiguous band of tiles -, n-tiles fastest)
+  int n_tiles, tiles_x, tiles_y, nt, b, trem, y0, x0;
+  static_assert(QPH == 8 && QBN == 128, "patch_tile_decode and gn_partial_store: 8-row patches, 128-channel tiles");
+  patch_tile_decode<QPW>(blockIdx.x, p.Cout, p.W, p.H, p.B, n_tiles, tiles_x, tiles_y, nt, b, trem, y0, x0);
   const int CC0 = p.C0 / QKC, CC = (p.C0 + p.C1) / QKC;
 
   // ---- A staging: 44 pieces of 1 KiB per chunk, wave w issues pieces w, w+4, ..., w+40; 16-byte chunk index in the LDS image
@@ -344,8 +318,8 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void conv3x3_mxfp8_kernel(ConvQArg
   // ---- prologue: A(0), B[0]
   issue_a(0);
   issue_b(0, 0, 0);
-  QWAIT_VM(0);
-  QBARRIER();
+  WAIT_VM(0);
+  BARRIER();
 
   if constexpr (QSTAMPS) t1 = __builtin_amdgcn_s_memtime();
   // ---- main loop.  Per K-step: issue B[s+1] into the other ring slot; compute(s) (32 MFMAs per wave, ~2,000 cycles with the
@@ -361,13 +335,13 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void conv3x3_mxfp8_kernel(ConvQArg
       if (tap < 8) issue_b(cc, tap + 1, slot ^ 1);
       else issue_b(min(cc + 1, CC - 1), cc + 1 < CC ? 0 : 8, slot ^ 1);   // (the last step re-fetches its own unit into the idle slot)
       compute(tap, slot);
-      QWAIT_VM(0);
-      QBARRIER();
+      WAIT_VM(0);
+      BARRIER();
     }
     if (cc + 1 < CC) {
       issue_a(cc + 1);                             // every wave passed the barrier above: the old patch is dead
-      QWAIT_VM(0);
-      QBARRIER();
+      WAIT_VM(0);
+      BARRIER();
     }
   }
   if constexpr (QSTAMPS) t2 = __builtin_amdgcn_s_memtime();
@@ -452,25 +426,7 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void conv3x3_mxfp8_kernel(ConvQArg
   } while (0)
   { K_QEMIT(0); K_QEMIT(1); K_QEMIT(2); K_QEMIT(3); K_QEMIT(4); K_QEMIT(5); K_QEMIT(6); K_QEMIT(7); }
 #undef K_QEMIT
-  if (STATS) {
-    // per-(sample, group) sums of this wave's 128 pixels x 64 channels (conv3x3_bf16.hip): cpg 16 -> one group per lane row,
-    // 32 -> row pairs, >= 64 -> the wave; one slot per contributing wave: the 2 waves (wm) of the group's column half, or all 4
-    const int cpg = p.Cout / p.groups;                    // 16, 32, 64 or a multiple of 128
-    float a1 = row16_sum((s1v[0] + s1v[1]) + (s1v[2] + s1v[3]));
-    float a2 = row16_sum((s2v[0] + s2v[1]) + (s2v[2] + s2v[3]));
-    if (cpg >= 32) { a1 = xor16_sum(a1); a2 = xor16_sum(a2); }
-    if (cpg >= 64) { a1 = xor32_sum(a1); a2 = xor32_sum(a2); }
-    const int rows_per_group = cpg >= 64 ? 4 : cpg >> 4;
-    if (r16E == 0 && (gE & (rows_per_group - 1)) == 0) {
-      const int tpg = cpg >= QBN ? cpg / QBN : 1;
-      const int wpt = cpg >= QBN ? NW : NWM;
-      const int nslots = tiles_y * tiles_x * tpg * wpt;
-      const int slot = (trem * tpg + (cpg >= QBN ? nt % tpg : 0)) * wpt + (cpg >= QBN ? wave : wm);
-      const int grp = cpg >= QBN ? chw / cpg : (chw + chl) >> __builtin_ctz(cpg);
-      float* dst = p.gn_partial + ((size_t)(b * p.groups + grp) * nslots + slot) * 2;
-      *reinterpret_cast<f32x2*>(dst) = f32x2{a1, a2};
-    }
-  }
+  if (STATS) gn_partial_store<QBN, NWM>(s1v, s2v, p.Cout, p.groups, p.gn_partial, r16E, gE, wave, wm, tiles_y, tiles_x, trem, nt, b, chw, chl);
   if constexpr (QSTAMPS) {
     t3 = __builtin_amdgcn_s_memtime();
 #if SRGD_MXFP8_STAMPS
@@ -507,6 +463,7 @@ int mx_block_exponent(float amax) {
   return e < -127 ? -127 : (e > 127 ? 127 : e);
 }
 
+// (not conv3x3_patch_eligible: 128-channel chunks, one-byte inputs beside two-byte outputs, and no pixel-stride condition)
 bool conv3x3_mxfp8_eligible(const ConvArgs& a) {
   if (a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1 || a.mode != CONV_PLAIN || a.residual || a.gn_res_src) return false;
   if (a.C0 % QKC || a.C1 % QKC || a.Cout % QBN || a.Cout != a.CoutPad) return false;
@@ -522,11 +479,8 @@ bool conv3x3_mxfp8_eligible(const ConvArgs& a) {
   return true;
 }
 
-int conv3x3_mxfp8_stats_slots(const ConvArgs& a) {
-  if (a.groups <= 0) return 0;
-  const int cpg = a.Cout / a.groups;
-  return (a.Hin / QPH) * (a.Win / QPW) * (cpg >= QBN ? (cpg / QBN) * NW : NW / 2);      // one slot per contributing wave
-}
+static_assert(QPH == 8 && QPW == 32 && QBN == 128, "conv3x3_stats_slots counts 8 x 32 pixel patches and 128-channel tiles");
+int conv3x3_mxfp8_stats_slots(const ConvArgs& a) { return conv3x3_stats_slots(a, NW / 2); }      // one slot per contributing wave
 
 // OIHW fp32 -> [tap][cc][ntile][16.5 KiB]: 128 rows x 128 B of e4m3 (swizzled LDS image) + 512 E8M0 bytes [wn][r16][blk][J].
 // Tile row n holds output channel regepi_row_channel(n) (common.hpp: the register-direct epilogue's row order).

@@ -27,7 +27,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "kernels.hpp"
+#include "conv_common.hpp"
 
 namespace srgd {
 namespace {
@@ -43,11 +43,6 @@ constexpr int B_TILE = BN3 * KC * 2;           // 8 KiB: one 16-bit weight tile
 constexpr int B_SLOT = 2 * B_TILE;             // hi | lo
 constexpr int LDS_BYTES = 2 * A_BUF + 3 * B_SLOT;   // 147,456: one workgroup per CU
 
-typedef __attribute__((address_space(3))) void* lds_ptr;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
 struct Split3Args {
   const float* in0; const float* in1; int C0, C1;
   int B, H, W;
@@ -61,43 +56,31 @@ struct Split3Args {
   const float* gn_in_b;
 };
 
-#define WAIT_VM(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
-#define BARRIER()                        \
-  do {                                   \
-    __builtin_amdgcn_s_barrier();        \
-    __builtin_amdgcn_sched_barrier(0);   \
-  } while (0)
+// One K-row of a K-step, for both kernels below: the wave's pixel block I (16 pixels) of tap `tap` against its four 16-channel weight
+// fragments - twelve MFMAs, x_lo * w_hi, then x_hi * w_lo, then x_hi * w_hi into the same four accumulators.  A = the hi halo image
+// in LDS, the lo image IMG bytes behind it; a_addr, mma, tap and the weight fragments bh0..3 / bl0..3 are the caller's.
+#define SPLIT_K_ROW(A, IMG, I, C0_, C1_, C2_, C3_)                                             \
+  {                                                                                            \
+    const frag ah = *reinterpret_cast<const frag*>((A) + a_addr(tap, I));                      \
+    const frag al = *reinterpret_cast<const frag*>((A) + (IMG) + a_addr(tap, I));              \
+    mma(C0_, bh0, al); mma(C1_, bh1, al); mma(C2_, bh2, al); mma(C3_, bh3, al);                \
+    mma(C0_, bl0, ah); mma(C1_, bl1, ah); mma(C2_, bl2, ah); mma(C3_, bl3, ah);                \
+    mma(C0_, bh0, ah); mma(C1_, bh1, ah); mma(C2_, bh2, ah); mma(C3_, bh3, ah);                \
+  }
 
-__device__ __forceinline__ int row_swz(int row) { return (row >> 1) & 3; }
-
-// 8 fp32 -> 8 hi + 8 lo 16-bit values (each a 16-byte vector).  F16: a FINITE value beyond f16's range saturates at +-65504 (finite
-// garbage instead of inf - inf = NaN; activations on this path are O(1..100)); a NaN or an infinity leaves as NaN in both halves
-// and so reaches every output it contributes to (sat_f16_keep_nonfinite, common.hpp).  bf16 halves share fp32's range: no clamp.
-template <bool F16>
-__device__ __forceinline__ void split8(const u32x4& r0, const u32x4& r1, u32x4& hi, u32x4& lo) {
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const unsigned ua = k < 2 ? r0[2 * k] : r1[2 * k - 4], ub = k < 2 ? r0[2 * k + 1] : r1[2 * k - 3];
-    float a = __uint_as_float(ua), b = __uint_as_float(ub);
-    if constexpr (F16) {
-      a = sat_f16_keep_nonfinite(a);
-      b = sat_f16_keep_nonfinite(b);
-      const f16x2 h = __builtin_convertvector(f32x2{a, b}, f16x2);
-      const f32x2 hf = __builtin_convertvector(h, f32x2);
-      const f16x2 l = __builtin_convertvector(f32x2{a - hf[0], b - hf[1]}, f16x2);
-      hi[k] = __builtin_bit_cast(unsigned, h);
-      lo[k] = __builtin_bit_cast(unsigned, l);
-    } else {
-      const bf16x2 h = __builtin_convertvector(f32x2{a, b}, bf16x2);
-      const unsigned hb = __builtin_bit_cast(unsigned, h);
-      const float h0 = __uint_as_float(hb << 16), h1 = __uint_as_float(hb & 0xffff0000u);
-      const bf16x2 l = __builtin_convertvector(f32x2{a - h0, b - h1}, bf16x2);
-      hi[k] = hb;
-      lo[k] = __builtin_bit_cast(unsigned, l);
-    }
+// The lane's sixteen bias values (both kernels below): channels chw + chl .. + 15 (16-byte aligned: launcher), zero without a bias.
+__device__ __forceinline__ void split_load_bias(const float* bias, int chw, int chl, f32x4& bs0, f32x4& bs1, f32x4& bs2, f32x4& bs3) {
+  bs0 = bs1 = bs2 = bs3 = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (bias) {
+    const float* bp = bias + chw + chl;
+    bs0 = *reinterpret_cast<const f32x4*>(bp);
+    bs1 = *reinterpret_cast<const f32x4*>(bp + 4);
+    bs2 = *reinterpret_cast<const f32x4*>(bp + 8);
+    bs3 = *reinterpret_cast<const f32x4*>(bp + 12);
   }
 }
 
+// (the (hi, lo) operand split split8<F16> and the GNIN transform act4: conv_common.hpp)
 // GNIN instances: the PRODUCER's GroupNorm-apply + SiLU (reference Block.forward model.py:250-259 between two convolutions) is applied
 // to the fp32 halo pieces in registers, ahead of the split - the separate gn_apply pass over that tensor (4 B read + 4 B written per
 // element) disappears.  Out-of-image halo pixels stay zero (the convolution pads the ACTIVATED tensor).  v_exp_f32 / v_rcp_f32
@@ -111,21 +94,10 @@ __global__ __launch_bounds__(NT3, 2) void conv3x3_split_kernel(Split3Args p) {
   const int wm = wave >> 1, wn = wave & 1;
   const int r16 = lane & 15, q16 = lane >> 4;
 
-  // ---- tile coordinates: the bf16 kernel's XCD-aware map (each XCD a contiguous band of tiles, n-tiles fastest)
-  const int n_tiles = p.Cout / BN3;
-  const int tiles_x = p.W / PW, tiles_y = p.H / PH;
-  const int m_tiles = p.B * tiles_y * tiles_x;
-  const int nwg = m_tiles * n_tiles;
-  int wg = blockIdx.x;
-  {
-    const int q = nwg >> 3, rem = nwg & 7, x = wg & 7, k = wg >> 3;
-    wg = (x < rem ? x * (q + 1) : rem * (q + 1) + (x - rem) * q) + k;
-  }
-  const int nt = wg % n_tiles, mt = wg / n_tiles;
-  const int b = mt / (tiles_y * tiles_x);
-  const int trem = mt - b * tiles_y * tiles_x;
-  const int ty = trem / tiles_x, tx = trem - ty * tiles_x;
-  const int y0 = ty * PH, x0 = tx * PW;
+  // ---- tile coordinates (conv_common.hpp: XCD-aware remap - each XCD a contiguous band of tiles -, n-tiles fastest)
+  int n_tiles, tiles_x, tiles_y, nt, b, trem, y0, x0;
+  static_assert(PH == 8 && BN3 == 128, "patch_tile_decode and gn_partial_store: 8-row patches, 128-channel tiles");
+  patch_tile_decode<PW>(blockIdx.x, p.Cout, p.W, p.H, p.B, n_tiles, tiles_x, tiles_y, nt, b, trem, y0, x0);
   const int Cin = p.C0 + p.C1;
   const int CC = Cin / KC;
 
@@ -186,16 +158,6 @@ __global__ __launch_bounds__(NT3, 2) void conv3x3_split_kernel(Split3Args p) {
       gb0 = *reinterpret_cast<const f32x4*>(cb); gb1 = *reinterpret_cast<const f32x4*>(cb + 4);
     }
   };
-  auto act4 = [&](u32x4& r, const f32x4& ga, const f32x4& gb) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      // (element copied out first: __builtin_bit_cast applied directly to the vector-element lvalue r[k] read element 0 for every
-      // k with this toolchain - hipcc 7.2 - which the kernel test caught)
-      const unsigned u = r[k];
-      const float t = __builtin_fmaf(ga[k], __uint_as_float(u), gb[k]);
-      r[k] = __float_as_uint(t * __builtin_amdgcn_rcpf(1.0f + __expf(-t)));
-    }
-  };
   auto store_piece = [&](int cc, int j, u32x4 r0, u32x4 r1) {
     if constexpr (GNIN) {
       if ((j == 0 ? a_pix0 : (j == 1 ? a_pix1 : a_pix2)) >= 0) { act4(r0, ga0, gb0); act4(r1, ga1, gb1); }
@@ -241,19 +203,10 @@ __global__ __launch_bounds__(NT3, 2) void conv3x3_split_kernel(Split3Args p) {
                bh2 = *reinterpret_cast<const frag*>(Bt + b_base + 2048), bh3 = *reinterpret_cast<const frag*>(Bt + b_base + 3072);
     const frag bl0 = *reinterpret_cast<const frag*>(Bt + B_TILE + b_base), bl1 = *reinterpret_cast<const frag*>(Bt + B_TILE + b_base + 1024),
                bl2 = *reinterpret_cast<const frag*>(Bt + B_TILE + b_base + 2048), bl3 = *reinterpret_cast<const frag*>(Bt + B_TILE + b_base + 3072);
-#define K_ROW(I, C0_, C1_, C2_, C3_)                                                          \
-  {                                                                                            \
-    const frag ah = *reinterpret_cast<const frag*>(A + a_addr(tap, I));                        \
-    const frag al = *reinterpret_cast<const frag*>(A + A_IMG + a_addr(tap, I));                \
-    mma(C0_, bh0, al); mma(C1_, bh1, al); mma(C2_, bh2, al); mma(C3_, bh3, al);                \
-    mma(C0_, bl0, ah); mma(C1_, bl1, ah); mma(C2_, bl2, ah); mma(C3_, bl3, ah);                \
-    mma(C0_, bh0, ah); mma(C1_, bh1, ah); mma(C2_, bh2, ah); mma(C3_, bh3, ah);                \
-  }
-    K_ROW(0, c00, c01, c02, c03)
-    K_ROW(1, c10, c11, c12, c13)
-    K_ROW(2, c20, c21, c22, c23)
-    K_ROW(3, c30, c31, c32, c33)
-#undef K_ROW
+    SPLIT_K_ROW(A, A_IMG, 0, c00, c01, c02, c03)
+    SPLIT_K_ROW(A, A_IMG, 1, c10, c11, c12, c13)
+    SPLIT_K_ROW(A, A_IMG, 2, c20, c21, c22, c23)
+    SPLIT_K_ROW(A, A_IMG, 3, c30, c31, c32, c33)
   };
 
   // ---- prologue: A(0) through registers, B[0], B[1]
@@ -308,14 +261,8 @@ __global__ __launch_bounds__(NT3, 2) void conv3x3_split_kernel(Split3Args p) {
   // 64 wn + 16 g + 4 J + e (regepi_row_channel): a lane's sixteen registers of a pixel block are 16 consecutive channels = 64 bytes.
   const int chw = nt * BN3 + wn * 64;
   const int chl = q16 * 16;
-  f32x4 bs0 = {0.f, 0.f, 0.f, 0.f}, bs1 = bs0, bs2 = bs0, bs3 = bs0;
-  if (p.bias) {
-    const float* bp = p.bias + chw + chl;
-    bs0 = *reinterpret_cast<const f32x4*>(bp);
-    bs1 = *reinterpret_cast<const f32x4*>(bp + 4);
-    bs2 = *reinterpret_cast<const f32x4*>(bp + 8);
-    bs3 = *reinterpret_cast<const f32x4*>(bp + 12);
-  }
+  f32x4 bs0, bs1, bs2, bs3;
+  split_load_bias(p.bias, chw, chl, bs0, bs1, bs2, bs3);
   const u32x4 rso = make_raw_rsrc(p.out + ((size_t)(b * p.H + y0 + 2 * wm) * p.W + x0) * p.Cout + chw, (unsigned)(2 * p.W * p.Cout * 4));
   const int o_voff = (r16 * p.Cout + chl) * 4;
   // Stores leave as full lines (the wave's 64 fp32 channels of a pixel = 256 bytes): each 16-pixel block goes through 16 staging rows
@@ -363,24 +310,7 @@ __global__ __launch_bounds__(NT3, 2) void conv3x3_split_kernel(Split3Args p) {
   K_EMIT(2, c20, c21, c22, c23);
   K_EMIT(3, c30, c31, c32, c33);
 #undef K_EMIT
-  if (STATS) {
-    // same slot layout and reduction order as conv3x3_bf16.hip (gn_finalize sums the slots in index order)
-    const int cpg = p.Cout / p.groups;                    // 16, 32, 64 or a multiple of 128
-    float a1 = row16_sum((s1v[0] + s1v[1]) + (s1v[2] + s1v[3]));
-    float a2 = row16_sum((s2v[0] + s2v[1]) + (s2v[2] + s2v[3]));
-    if (cpg >= 32) { a1 = xor16_sum(a1); a2 = xor16_sum(a2); }
-    if (cpg >= 64) { a1 = xor32_sum(a1); a2 = xor32_sum(a2); }
-    const int rows_per_group = cpg >= 64 ? 4 : cpg >> 4;
-    if (r16 == 0 && (q16 & (rows_per_group - 1)) == 0) {
-      const int tpg = cpg >= BN3 ? cpg / BN3 : 1;
-      const int wpt = cpg >= BN3 ? 8 : 4;
-      const int nslots = tiles_y * tiles_x * tpg * wpt;
-      const int slot = (trem * tpg + (cpg >= BN3 ? nt % tpg : 0)) * wpt + (cpg >= BN3 ? wave : wm);
-      const int g = cpg >= BN3 ? chw / cpg : (chw + chl) >> __builtin_ctz(cpg);
-      float* dst = p.gn_partial + ((size_t)(b * p.groups + g) * nslots + slot) * 2;
-      *reinterpret_cast<f32x2*>(dst) = f32x2{a1, a2};
-    }
-  }
+  if (STATS) gn_partial_store<BN3, 4>(s1v, s2v, p.Cout, p.groups, p.gn_partial, r16, q16, wave, wm, tiles_y, tiles_x, trem, nt, b, chw, chl);
 }
 
 
@@ -407,20 +337,10 @@ __global__ __launch_bounds__(NT2, 2) void conv3x3_split2_kernel(Split3Args p) {
   const int wm = wave >> 1, wn = wave & 1;
   const int r16 = lane & 15, q16 = lane >> 4;
 
-  const int n_tiles = p.Cout / BN3;
-  const int tiles_x = p.W / PW2, tiles_y = p.H / PH;
-  const int m_tiles = p.B * tiles_y * tiles_x;
-  const int nwg = m_tiles * n_tiles;
-  int wg = blockIdx.x;
-  {
-    const int q = nwg >> 3, rem = nwg & 7, x = wg & 7, k = wg >> 3;
-    wg = (x < rem ? x * (q + 1) : rem * (q + 1) + (x - rem) * q) + k;
-  }
-  const int nt = wg % n_tiles, mt = wg / n_tiles;
-  const int b = mt / (tiles_y * tiles_x);
-  const int trem = mt - b * tiles_y * tiles_x;
-  const int ty = trem / tiles_x, tx = trem - ty * tiles_x;
-  const int y0 = ty * PH, x0 = tx * PW2;
+  // ---- tile coordinates (conv_common.hpp: XCD-aware remap - each XCD a contiguous band of tiles -, n-tiles fastest)
+  int n_tiles, tiles_x, tiles_y, nt, b, trem, y0, x0;
+  static_assert(PH == 8 && BN3 == 128, "patch_tile_decode and gn_partial_store: 8-row patches, 128-channel tiles");
+  patch_tile_decode<PW2>(blockIdx.x, p.Cout, p.W, p.H, p.B, n_tiles, tiles_x, tiles_y, nt, b, trem, y0, x0);
   const int Cin = p.C0 + p.C1;
   const int CC = Cin / KC;
 
@@ -451,6 +371,8 @@ __global__ __launch_bounds__(NT2, 2) void conv3x3_split2_kernel(Split3Args p) {
   char* const sA = smem;
   char* const sB0 = smem + A_BUF2;
 
+  // (load_piece and load_a repeat conv3x3_split_kernel's: as functions shared by the two kernels they compiled to other instructions
+  // in both - profiles/conv_common_refactor.txt)
   u32x4 ra00, ra01, ra10, ra11, ra20, ra21;
   f32x4 ga0, ga1, gb0, gb1;
   auto load_piece = [&](int cc, int a_pix, u32x4& lo16, u32x4& hi16) {
@@ -476,14 +398,6 @@ __global__ __launch_bounds__(NT2, 2) void conv3x3_split2_kernel(Split3Args p) {
       const float* cb = p.gn_in_b + (size_t)b * Cin + cc * KC + a_sub * 8;
       ga0 = *reinterpret_cast<const f32x4*>(ca); ga1 = *reinterpret_cast<const f32x4*>(ca + 4);
       gb0 = *reinterpret_cast<const f32x4*>(cb); gb1 = *reinterpret_cast<const f32x4*>(cb + 4);
-    }
-  };
-  auto act4 = [&](u32x4& r, const f32x4& ga, const f32x4& gb) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const unsigned u = r[k];                       // (see conv3x3_split_kernel: no bit_cast on the element lvalue)
-      const float t = __builtin_fmaf(ga[k], __uint_as_float(u), gb[k]);
-      r[k] = __float_as_uint(t * __builtin_amdgcn_rcpf(1.0f + __expf(-t)));
     }
   };
   auto store_piece = [&](int j, u32x4 r0, u32x4 r1) {
@@ -529,19 +443,10 @@ __global__ __launch_bounds__(NT2, 2) void conv3x3_split2_kernel(Split3Args p) {
                bh2 = *reinterpret_cast<const frag*>(Bt + b_base + 2048), bh3 = *reinterpret_cast<const frag*>(Bt + b_base + 3072);
     const frag bl0 = *reinterpret_cast<const frag*>(Bt + B_TILE + b_base), bl1 = *reinterpret_cast<const frag*>(Bt + B_TILE + b_base + 1024),
                bl2 = *reinterpret_cast<const frag*>(Bt + B_TILE + b_base + 2048), bl3 = *reinterpret_cast<const frag*>(Bt + B_TILE + b_base + 3072);
-#define K_ROW(I, C0_, C1_, C2_, C3_)                                                          \
-  {                                                                                            \
-    const frag ah = *reinterpret_cast<const frag*>(sA + a_addr(tap, I));                       \
-    const frag al = *reinterpret_cast<const frag*>(sA + A_IMG2 + a_addr(tap, I));              \
-    mma(C0_, bh0, al); mma(C1_, bh1, al); mma(C2_, bh2, al); mma(C3_, bh3, al);                \
-    mma(C0_, bl0, ah); mma(C1_, bl1, ah); mma(C2_, bl2, ah); mma(C3_, bl3, ah);                \
-    mma(C0_, bh0, ah); mma(C1_, bh1, ah); mma(C2_, bh2, ah); mma(C3_, bh3, ah);                \
-  }
-    K_ROW(0, c00, c01, c02, c03)
-    K_ROW(1, c10, c11, c12, c13)
-    K_ROW(2, c20, c21, c22, c23)
-    K_ROW(3, c30, c31, c32, c33)
-#undef K_ROW
+    SPLIT_K_ROW(sA, A_IMG2, 0, c00, c01, c02, c03)
+    SPLIT_K_ROW(sA, A_IMG2, 1, c10, c11, c12, c13)
+    SPLIT_K_ROW(sA, A_IMG2, 2, c20, c21, c22, c23)
+    SPLIT_K_ROW(sA, A_IMG2, 3, c30, c31, c32, c33)
   };
 
   // ---- prologue
@@ -591,14 +496,8 @@ __global__ __launch_bounds__(NT2, 2) void conv3x3_split2_kernel(Split3Args p) {
   // ---- epilogue (register-direct, fp32): block mi = patch row 4 wm + mi, pixel x = r16, channels 64 wn + 16 g + 4 J + e
   const int chw = nt * BN3 + wn * 64;
   const int chl = q16 * 16;
-  f32x4 bs0 = {0.f, 0.f, 0.f, 0.f}, bs1 = bs0, bs2 = bs0, bs3 = bs0;
-  if (p.bias) {
-    const float* bp = p.bias + chw + chl;
-    bs0 = *reinterpret_cast<const f32x4*>(bp);
-    bs1 = *reinterpret_cast<const f32x4*>(bp + 4);
-    bs2 = *reinterpret_cast<const f32x4*>(bp + 8);
-    bs3 = *reinterpret_cast<const f32x4*>(bp + 12);
-  }
+  f32x4 bs0, bs1, bs2, bs3;
+  split_load_bias(p.bias, chw, chl, bs0, bs1, bs2, bs3);
   const u32x4 rso = make_raw_rsrc(p.out + ((size_t)(b * p.H + y0 + 4 * wm) * p.W + x0) * p.Cout + chw, (unsigned)(4 * p.W * p.Cout * 4));
   const int o_voff = (r16 * p.Cout + chl) * 4;
   const float ws = p.w_inv_scale;
@@ -625,48 +524,17 @@ __global__ __launch_bounds__(NT2, 2) void conv3x3_split2_kernel(Split3Args p) {
   K_EMIT(2, c20, c21, c22, c23);
   K_EMIT(3, c30, c31, c32, c33);
 #undef K_EMIT
-  if (STATS) {
-    // slots: per (sample, group) tiles_y * tiles_x * tpg * wpt with wpt = 2 (4 when a group spans whole 128-channel tiles) - twice
-    // the patches of the 512-thread kernel with half the waves each: the same count (conv3x3_bf16_stats_slots)
-    const int cpg = p.Cout / p.groups;
-    float a1 = row16_sum((s1v[0] + s1v[1]) + (s1v[2] + s1v[3]));
-    float a2 = row16_sum((s2v[0] + s2v[1]) + (s2v[2] + s2v[3]));
-    if (cpg >= 32) { a1 = xor16_sum(a1); a2 = xor16_sum(a2); }
-    if (cpg >= 64) { a1 = xor32_sum(a1); a2 = xor32_sum(a2); }
-    const int rows_per_group = cpg >= 64 ? 4 : cpg >> 4;
-    if (r16 == 0 && (q16 & (rows_per_group - 1)) == 0) {
-      const int tpg = cpg >= BN3 ? cpg / BN3 : 1;
-      const int wpt = cpg >= BN3 ? 4 : 2;
-      const int nslots = tiles_y * tiles_x * tpg * wpt;
-      const int slot = (trem * tpg + (cpg >= BN3 ? nt % tpg : 0)) * wpt + (cpg >= BN3 ? wave : wm);
-      const int g = cpg >= BN3 ? chw / cpg : (chw + chl) >> __builtin_ctz(cpg);
-      float* dst = p.gn_partial + ((size_t)(b * p.groups + g) * nslots + slot) * 2;
-      *reinterpret_cast<f32x2*>(dst) = f32x2{a1, a2};
-    }
-  }
+  // twice the patches of the 512-thread kernel with half the waves each: the same slot count (conv3x3_stats_slots)
+  if (STATS) gn_partial_store<BN3, 2>(s1v, s2v, p.Cout, p.groups, p.gn_partial, r16, q16, wave, wm, tiles_y, tiles_x, trem, nt, b, chw, chl);
 }
 
 }  // namespace
 
-bool conv3x3_split_eligible(const ConvArgs& a) {
-  if (a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1 || a.mode != CONV_PLAIN || a.residual || a.gn_res_src) return false;
-  if (a.ps0 != a.C0 || (a.C1 && a.ps1 != a.C1)) return false;
-  if (a.C0 % KC || a.C1 % KC || a.Cout % BN3 || a.Cout != a.CoutPad) return false;
-  if (a.Hin % PH || a.Win % PW) return false;
-  if (a.gn_partial) {
-    const int cpg = a.Cout / a.groups;
-    if (a.Cout % a.groups) return false;
-    if (!(cpg == 16 || cpg == 32 || cpg == 64 || cpg % BN3 == 0)) return false;
-  }
-  if ((size_t)a.Hin * a.Win * (size_t)std::max(a.C0, a.C1) * 4 >= (1ull << 31)) return false;
-  if ((size_t)a.Hin * a.Win * (size_t)a.Cout * 4 >= (1ull << 31)) return false;
-  if ((size_t)9 * ((a.C0 + a.C1) / KC) * (a.Cout / BN3) * B_SLOT >= (1ull << 31)) return false;
-  return true;
-}
+bool conv3x3_split_eligible(const ConvArgs& a) { return conv3x3_patch_eligible(a, 4, B_SLOT); }
 
 // ---- host-side split of the weights ---------------------------------------------------------------------------------------------
 // f16: round-to-nearest-even conversion of a float (finite, |x| < 65520) to IEEE binary16 bits, subnormals kept.
-static unsigned short f32_to_f16_host(float f) {
+unsigned short f32_to_f16_host(float f) {
   uint32_t u;
   std::memcpy(&u, &f, 4);
   const uint32_t sign = (u >> 16) & 0x8000u;
@@ -685,7 +553,7 @@ static unsigned short f32_to_f16_host(float f) {
   if (rem > half || (rem == half && (keep & 1u))) h += 1;                   // carries into the exponent correctly
   return (unsigned short)(sign | h);
 }
-static float f16_bits_to_f32(unsigned short h) {
+float f16_bits_to_f32(unsigned short h) {
   const uint32_t sign = (uint32_t)(h & 0x8000u) << 16;
   const int e = (h >> 10) & 31;
   const uint32_t m = h & 0x3ffu;
@@ -699,7 +567,7 @@ static float f16_bits_to_f32(unsigned short h) {
   std::memcpy(&v, &u, 4);
   return v;
 }
-static float bf16_bits_to_f32(unsigned short h) {
+float bf16_bits_to_f32(unsigned short h) {
   const uint32_t u = (uint32_t)h << 16;
   float v;
   std::memcpy(&v, &u, 4);
@@ -730,23 +598,11 @@ void split_halves_host(float v, bool f16, unsigned short* hi, unsigned short* lo
 
 // OIHW fp32 -> [tap][cc][ntile][hi tile | lo tile], each tile 128 rows x 64 B in conv3x3_bf16's swizzled LDS image and row order
 void pack_conv3x3_split(const float* src_oihw, int Cin, int Cout, bool f16, float scale, std::vector<unsigned short>& out) {
-  const int CC = Cin / KC, NTL = Cout / BN3;
-  out.assign((size_t)9 * CC * NTL * 2 * BN3 * KC, 0);
-  for (int tap = 0; tap < 9; ++tap)
-    for (int cc = 0; cc < CC; ++cc)
-      for (int nt = 0; nt < NTL; ++nt) {
-        unsigned short* hi_t = out.data() + ((size_t)(tap * CC + cc) * NTL + nt) * 2 * BN3 * KC;
-        unsigned short* lo_t = hi_t + BN3 * KC;
-        for (int n = 0; n < BN3; ++n)
-          for (int c = 0; c < 4; ++c) {
-            const int cs = c ^ ((n >> 1) & 3);
-            for (int e = 0; e < 8; ++e) {
-              const int ci = cc * KC + c * 8 + e, o = nt * BN3 + regepi_row_channel(n);
-              const float v = src_oihw[(((size_t)o * Cin + ci) * 3 + tap / 3) * 3 + tap % 3] * scale;
-              split_halves_host(v, f16, &hi_t[n * KC + cs * 8 + e], &lo_t[n * KC + cs * 8 + e]);
-            }
-          }
-      }
+  out.assign((size_t)9 * (Cin / KC) * (Cout / BN3) * 2 * BN3 * KC, 0);
+  conv3x3_weight_walk(src_oihw, Cin, Cout, [&](size_t tile, int, int, int pos, float v) {
+    unsigned short* hi_t = out.data() + tile * 2 * BN3 * KC;
+    split_halves_host(v * scale, f16, &hi_t[pos], &hi_t[BN3 * KC + pos]);
+  });
 }
 
 int conv3x3_split(const ConvArgs& a, const void* packed_w, float w_inv_scale, bool f16, hipStream_t st, const float* gn_in_a,

@@ -13,7 +13,7 @@
 //   bf16: v_mfma_f32_32x32x16_bf16 (fp32 accumulate);  fp32: v_mfma_f32_32x32x2_f32 (exact fp32).
 #include <cstdlib>
 
-#include "kernels.hpp"
+#include "conv_common.hpp"
 
 namespace srgd {
 
@@ -161,6 +161,8 @@ __global__ __launch_bounds__(NT, (sizeof(T) == 4 && BKC == 16) ? 4 : 1) void con
   // XCD-aware order: hardware deals consecutive workgroup ids round-robin to the 8 XCDs (one L2 each); renumber so
   // that each XCD walks a contiguous run of logical tiles - the n-tiles of one m-tile (same A rows) and the
   // neighbouring m-tiles (shared 3x3 halo rows) then hit the same L2 instead of 8 different ones
+  // (the same map as xcd_band_remap, conv_common.hpp, in a second algebraic form; kept: through the shared function this kernel
+  // compiles to a different instruction stream)
   const int nwg = gridDim.x, xq = nwg >> 3, xr = nwg & 7;
   const int xcd = blockIdx.x & 7, xloc = blockIdx.x >> 3;
   const int bid = xcd * xq + (xcd < xr ? xcd : xr) + xloc;
@@ -342,31 +344,12 @@ __global__ __launch_bounds__(NT, (sizeof(T) == 4 && BKC == 16) ? 4 : 1) void con
 // A K-step is one (tap, 32-channel chunk): the fp32 A rows are split in registers on their way to LDS, the weights come pre-split
 // from pack_conv_weights_split ([tap][CoutPad][Cin / 32][hi 32 | lo 32] 16-bit).  LDS rows: [hi 64 B | lo 64 B | 16 B pad].
 constexpr int SP_KC = 32, SP_STRIDE = 144;
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 
+// four fp32 -> two packed hi and two packed lo words (split_pair, conv_common.hpp)
 template <bool F16>
 __device__ __forceinline__ void split4(const f32x4& x, unsigned (&hi)[2], unsigned (&lo)[2]) {
-  typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    float a = x[2 * k], b = x[2 * k + 1];
-    if constexpr (F16) {
-      a = sat_f16_keep_nonfinite(a);        // finite out-of-range saturates, NaN / Inf become NaN (common.hpp)
-      b = sat_f16_keep_nonfinite(b);
-      const f16x2 hh = __builtin_convertvector(f32x2{a, b}, f16x2);
-      const f32x2 hf = __builtin_convertvector(hh, f32x2);
-      const f16x2 ll = __builtin_convertvector(f32x2{a - hf[0], b - hf[1]}, f16x2);
-      hi[k] = __builtin_bit_cast(unsigned, hh);
-      lo[k] = __builtin_bit_cast(unsigned, ll);
-    } else {
-      const bf16x2 hh = __builtin_convertvector(f32x2{a, b}, bf16x2);
-      const unsigned hb = __builtin_bit_cast(unsigned, hh);
-      const bf16x2 ll = __builtin_convertvector(f32x2{a - __uint_as_float(hb << 16), b - __uint_as_float(hb & 0xffff0000u)}, bf16x2);
-      hi[k] = hb;
-      lo[k] = __builtin_bit_cast(unsigned, ll);
-    }
-  }
+  for (int k = 0; k < 2; ++k) split_pair<F16>(x[2 * k], x[2 * k + 1], hi[k], lo[k]);
 }
 
 template <bool F16>
@@ -380,6 +363,8 @@ __global__ __launch_bounds__(NT, 2) void conv_igemm_split_kernel(ConvArgs p, flo
   const int wm = wave >> 1, wn = wave & 1;
   const int r = lane & 31, h = lane >> 5;
   const int n_tiles = p.CoutPad / BN;
+  // (the same map as xcd_band_remap, conv_common.hpp, in a second algebraic form; kept: through the shared function this kernel
+  // compiles to a different instruction stream)
   const int nwg = gridDim.x, xq = nwg >> 3, xr = nwg & 7;
   const int xcd = blockIdx.x & 7, xloc = blockIdx.x >> 3;
   const int bid = xcd * xq + (xcd < xr ? xcd : xr) + xloc;
@@ -446,7 +431,7 @@ __global__ __launch_bounds__(NT, 2) void conv_igemm_split_kernel(ConvArgs p, flo
 
   f32x16 acc00 = 0, acc01 = 0, acc10 = 0, acc11 = 0;
   auto mma = [&](f32x16& c, const u32x4& a, const u32x4& b) {
-    if constexpr (F16) c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
+    if constexpr (F16) c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
     else c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
   };
 

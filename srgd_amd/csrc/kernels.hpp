@@ -74,11 +74,39 @@ bool conv3x3_bf16_eligible(const ConvArgs& a);
 int conv3x3_bf16_stats_slots(const ConvArgs& a);
 void pack_conv3x3_bf16(const float* src_oihw, int Cin, int Cout, std::vector<unsigned short>& out,
                        unsigned short (*to_bf16)(float));
+// the shape test behind conv3x3_bf16_eligible / conv3x3_split_eligible (conv3x3_mx2 asks conv3x3_split_eligible and adds its own
+// 2 GiB check): bytes of a tensor element and of one (tap, chunk, n-tile) unit of the packed weight stream
+bool conv3x3_patch_eligible(const ConvArgs& a, int elem_bytes, int weight_unit_bytes);
+// The order in which pack_conv3x3_bf16 / _split / _mx2 lay out a 3x3 weight tensor: [tap][32-channel chunk][128-channel n-tile], and
+// inside a tile 128 rows x 64 B of 16-bit values - row n holds output channel regepi_row_channel(n) (common.hpp: the accumulator
+// registers of a lane are then 16 consecutive channels), its four 8-channel chunks XOR-swizzled by the row (row_swz of the kernels).
+// f(tile, n, k, pos, v): tile = (tap * CC + cc) * NTL + nt, k = channel inside the chunk (ascending per row), pos = 16-bit position
+// inside the tile's swizzled LDS image, v = the weight.
+template <typename F>
+void conv3x3_weight_walk(const float* src_oihw, int Cin, int Cout, F&& f) {
+  const int CC = Cin / 32, NTL = Cout / 128;
+  for (int tap = 0; tap < 9; ++tap)
+    for (int cc = 0; cc < CC; ++cc)
+      for (int nt = 0; nt < NTL; ++nt)
+        for (int n = 0; n < 128; ++n)
+          for (int c = 0; c < 4; ++c) {
+            const int cs = c ^ ((n >> 1) & 3);  // stored chunk position
+            for (int e = 0; e < 8; ++e) {
+              const int ci = cc * 32 + c * 8 + e, o = nt * 128 + regepi_row_channel(n);
+              f((size_t)(tap * CC + cc) * NTL + nt, n, c * 8 + e, n * 32 + cs * 8 + e,
+                src_oihw[(((size_t)o * Cin + ci) * 3 + tap / 3) * 3 + tap % 3]);
+            }
+          }
+}
 // gn_in_a/gn_in_b (nullable): [B][Cin] fp32 coefficients of y = silu(a*x + b) applied to the INPUT while it is
 // staged (the producer's GroupNorm+SiLU, fused; single source, Cin <= 1024).
 int conv3x3_bf16(const ConvArgs& a, const void* packed_w, const float* gn_in_a, const float* gn_in_b,
                  hipStream_t st);
 unsigned short f32_to_bf16_host(float f);
+// IEEE binary16 / bfloat16 bit patterns on the host (conv3x3_split.hip): round-to-nearest-even, subnormals kept
+unsigned short f32_to_f16_host(float f);
+float f16_bits_to_f32(unsigned short h);
+float bf16_bits_to_f32(unsigned short h);
 
 // ---------------------------------------------------------------- conv3x3_split.hip / conv_igemm.hip (split-operand precision)
 // fp32 tensors in HBM, contraction as three 16-bit MFMAs per product on (hi, lo) operand pairs (f16 halves, or bf16 halves for

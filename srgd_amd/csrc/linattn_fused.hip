@@ -22,7 +22,7 @@
 // The RMSNorm gains g1*sqrt(C) are folded into Wkv'/Wq' on the host.
 #include <cstdlib>
 
-#include "kernels.hpp"
+#include "conv_common.hpp"
 
 namespace srgd {
 namespace {
@@ -38,27 +38,21 @@ constexpr int NTH = 256;                // 4 waves: one per head (la1) / per 32-
 constexpr int RING = 3;                 // x tiles in flight per workgroup (LDS-DMA ring)
 constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 #if SRGD_LA_STAMPS
 __device__ unsigned long long g_la1_stamps[8];   // [norms + sync, k/v GEMM, scale + max + exp, rescale + context MFMAs, DMA wait + barrier, tiles]
 #endif
 
 __device__ __forceinline__ int swz(int row, int chunk16) { return row * 256 + ((chunk16 ^ (row & 15)) << 4); }
 
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, char* lds_wave_base, int voffset) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)lds_wave_base, 16, voffset, 0, 0, 2 /* nt */);
+// (non-temporal: not conv_common.hpp's dma16)
+__device__ __forceinline__ void dma16_nt(__amdgpu_buffer_rsrc_t rsrc, char* lds_wave_base, int voffset) {
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr)lds_wave_base, 16, voffset, 0, 0, 2 /* nt */);
 }
 
-#define LA_WAIT_VM(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
-#define LA_BARRIER()                     \
-  do {                                   \
-    __builtin_amdgcn_s_barrier();        \
-    __builtin_amdgcn_sched_barrier(0);   \
-  } while (0)
 #define LA_SYNC()                                         \
   do {                                                    \
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    \
-    LA_BARRIER();                                         \
+    BARRIER();                                         \
   } while (0)
 
 // stage one 64-pixel x tile (rows px0..px0+63 of the image behind rsrc) into `buf`, XOR-swizzled: 4 LDS-DMA pieces per wave
@@ -69,7 +63,7 @@ __device__ __forceinline__ void stage_tile(__amdgpu_buffer_rsrc_t rsrc, char* bu
     const int g = q * 64 + lane;
     const int row = g >> 4, cs = g & 15;
     const int c = cs ^ (row & 15);
-    dma16(rsrc, buf + q * 1024, ((px0 + row) * 128 + c * 8) * 2);
+    dma16_nt(rsrc, buf + q * 1024, ((px0 + row) * 128 + c * 8) * 2);
   }
 }
 
@@ -159,8 +153,8 @@ __global__ __launch_bounds__(NTH, 2) void la1_kernel(const bf16* __restrict__ x,
 #define LA_MM0(C_, A_, B_) C_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_, B_, f32x16(0), 0, 0, 0)
   // tile 0 has landed once at most the second tile's 4 pieces are outstanding (wherever the compiler put the fragment
   // loads relative to the DMAs, "all but the 4 youngest" covers tile 0)
-  if (T > 1) LA_WAIT_VM(4); else LA_WAIT_VM(0);
-  LA_BARRIER();
+  if (T > 1) WAIT_VM(4); else WAIT_VM(0);
+  BARRIER();
 
 #if SRGD_LA_STAMPS
   unsigned long long ph0 = 0, ph1 = 0, ph2 = 0, ph3 = 0, ph4 = 0, tq = __builtin_amdgcn_s_memtime(), tn;
@@ -256,8 +250,8 @@ __global__ __launch_bounds__(NTH, 2) void la1_kernel(const bf16* __restrict__ x,
 #endif
     LA_STAMP(ph3);
     // tile t+1 must have landed before the next iteration reads it; the DMA of tile t+2 (4 pieces) stays in flight
-    if (t + 2 < T) LA_WAIT_VM(4); else LA_WAIT_VM(0);
-    LA_BARRIER();
+    if (t + 2 < T) WAIT_VM(4); else WAIT_VM(0);
+    BARRIER();
     LA_STAMP(ph4);
   }
 #if SRGD_LA_STAMPS
@@ -316,7 +310,7 @@ __global__ __launch_bounds__(NTH, 2) void la2_kernel(La2Args p) {
       __builtin_amdgcn_make_buffer_rsrc((void*)(p.rinv + (size_t)b * p.N), 0, p.N * 4, 0x00020000);
   auto stage = [&](int slot, int px0) {
     stage_tile(rsx, sA + slot * TILE_BYTES, hd, lane, px0);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsr, (lds_ptr_t)(sRv + (slot * 4 + hd) * TM), 4, (px0 + lane) * 4, 0, 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsr, (lds_ptr)(sRv + (slot * 4 + hd) * TM), 4, (px0 + lane) * 4, 0, 0, 0);
   };
 
   // register-resident operands: rows (hd*32 + r) of Wq' and Wout as MFMA A fragments for the 8 k16 steps
@@ -345,8 +339,8 @@ __global__ __launch_bounds__(NTH, 2) void la2_kernel(La2Args p) {
   }
   stage(0, tile0 * TM);
   if (T > 1) stage(1, (tile0 + 1) * TM);
-  if (T > 1) LA_WAIT_VM(5); else LA_WAIT_VM(0);            // tile 0 (and every operand load) landed; tile 1's 5 pieces may fly
-  LA_BARRIER();
+  if (T > 1) WAIT_VM(5); else WAIT_VM(0);            // tile 0 (and every operand load) landed; tile 1's 5 pieces may fly
+  BARRIER();
 
   for (int t = 0; t < T; ++t) {
     const char* A = sA + (t % RING) * TILE_BYTES;
@@ -468,7 +462,7 @@ __global__ __launch_bounds__(NTH, 2) void la2_kernel(La2Args p) {
     }
     // Tile t+1 (issued one iteration ago) must have landed before the next iteration reads it; this iteration's DMA of
     // tile t+2 (5 pieces) and its 4 stores (younger still) stay in flight.
-    if (t + 2 < T) LA_WAIT_VM(9); else LA_WAIT_VM(4);
+    if (t + 2 < T) WAIT_VM(9); else WAIT_VM(4);
     LA_SYNC();                                             // every wave has read the x / output tiles from LDS
   }
 }

@@ -9,7 +9,7 @@
 //     64 VGPRs); att goes through an 8 KiB LDS tile, bias / RMSNorm gain come from LDS, and y = RMSNorm(o) g + x is formed
 //     IN the staged x tile (each (pixel, channel) element is owned by one lane), which then leaves as whole 512-byte rows.
 // Partials / combine / workspace layout are those of linattn_fused.hip (la_combine_kernel merges the strips).
-#include "kernels.hpp"
+#include "conv_common.hpp"
 
 namespace srgd {
 namespace {
@@ -25,21 +25,14 @@ template <int C> struct LaDims {
 };
 constexpr float LOG2E_ = 1.4426950408889634f, LN2_ = 0.6931471805599453f;
 
-typedef __attribute__((address_space(3))) void* lds_ptr2;
 
 template <int C> __device__ __forceinline__ int swz2(int row, int chunk) { return row * (C * 2) + ((chunk ^ (row & 15)) << 4); }    // x tile
 __device__ __forceinline__ int swza(int row, int chunk16) { return row * 256 + ((chunk16 ^ (row & 15)) << 4); }  // att tile
 
-#define LB_WAIT_VM(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
-#define LB_BARRIER()                     \
-  do {                                   \
-    __builtin_amdgcn_s_barrier();        \
-    __builtin_amdgcn_sched_barrier(0);   \
-  } while (0)
 #define LB_SYNC()                                         \
   do {                                                    \
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    \
-    LB_BARRIER();                                         \
+    BARRIER();                                         \
   } while (0)
 
 // one 32-pixel x tile (rows px0..px0+31) -> `buf`, XOR-swizzled: PPW LDS-DMA pieces of 1 KiB per wave
@@ -52,7 +45,7 @@ __device__ __forceinline__ void stage_tile2(__amdgpu_buffer_rsrc_t rsrc, char* b
     const int g = q * 64 + lane;
     const int row = g / NCH, cs = g % NCH;
     const int c = cs ^ (row & 15);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr2)(buf + q * 1024), 16, ((px0 + row) * C + c * 8) * 2, 0, 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr)(buf + q * 1024), 16, ((px0 + row) * C + c * 8) * 2, 0, 0, 0);
   }
 }
 
@@ -76,11 +69,11 @@ __device__ __forceinline__ void row_rinv2(const char* tile, float* rinv, int tid
 
 // the DMA pieces of the youngest staged tile may stay in flight (PIECES is a template constant: s_waitcnt takes an immediate)
 template <int PIECES> __device__ __forceinline__ void wait_all_but() {
-  if constexpr (PIECES == 2) LB_WAIT_VM(2);
-  else if constexpr (PIECES == 3) LB_WAIT_VM(3);
-  else if constexpr (PIECES == 4) LB_WAIT_VM(4);
-  else if constexpr (PIECES == 5) LB_WAIT_VM(5);
-  else if constexpr (PIECES == 9) LB_WAIT_VM(9);
+  if constexpr (PIECES == 2) WAIT_VM(2);
+  else if constexpr (PIECES == 3) WAIT_VM(3);
+  else if constexpr (PIECES == 4) WAIT_VM(4);
+  else if constexpr (PIECES == 5) WAIT_VM(5);
+  else if constexpr (PIECES == 9) WAIT_VM(9);
   else static_assert(PIECES == 2, "unsupported wait count");
 }
 
@@ -132,8 +125,8 @@ __global__ __launch_bounds__(NTH2, C == 128 ? 3 : 2) void la1_t_kernel(const bf1
   if (T > 1) stage_tile2<C>(rsx, sA + TILE2, head, lane, px_begin + TM2);
   float m = -INFINITY, l = 0.f;
   f32x16 ctx = 0;
-  if (T > 1) wait_all_but<PPW>(); else LB_WAIT_VM(0);
-  LB_BARRIER();
+  if (T > 1) wait_all_but<PPW>(); else WAIT_VM(0);
+  BARRIER();
 
   for (int t = 0; t < T; ++t) {
     const char* A = sA + (t % RING2) * TILE2;
@@ -186,8 +179,8 @@ __global__ __launch_bounds__(NTH2, C == 128 ? 3 : 2) void la1_t_kernel(const bf1
     }
 #pragma unroll
     for (int s = 0; s < 2; ++s) ctx = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pack8_(k0, s), pack8_(v0, s), ctx, 0, 0, 0);
-    if (t + 2 < T) wait_all_but<PPW>(); else LB_WAIT_VM(0);
-    LB_BARRIER();
+    if (t + 2 < T) wait_all_but<PPW>(); else WAIT_VM(0);
+    BARRIER();
   }
   l += __shfl_xor(l, 32, 64);
   const size_t pidx = (size_t)(b * 4 + head) * nstrips + sidx;
@@ -242,7 +235,7 @@ __global__ __launch_bounds__(NTH2, C == 128 ? 3 : 2) void la2_t_kernel(La2Args25
   auto stage = [&](int slot, int px0) {
     stage_tile2<C>(rsx, sA + slot * TILE2, hd, lane, px0);
     // 64 dwords ride along (the tile's 32 + the next 32; out-of-range lanes read 0 through the buffer bounds check)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsr, (lds_ptr2)(sRv + (slot * 4 + hd) * 64), 4, (px0 + lane) * 4, 0, 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsr, (lds_ptr)(sRv + (slot * 4 + hd) * 64), 4, (px0 + lane) * 4, 0, 0, 0);
   };
 
   bf16x8 wq[KS], wo0[8], wo1[8];                          // (wo1: the second 32-row block, C = 256 only)
@@ -272,7 +265,7 @@ __global__ __launch_bounds__(NTH2, C == 128 ? 3 : 2) void la2_t_kernel(La2Args25
   }
   stage(0, tile0 * TM2);
   if (T > 1) stage(1, (tile0 + 1) * TM2);
-  if (T > 1) wait_all_but<PPW + 1>(); else LB_WAIT_VM(0);
+  if (T > 1) wait_all_but<PPW + 1>(); else WAIT_VM(0);
   LB_SYNC();
 
   for (int t = 0; t < T; ++t) {
