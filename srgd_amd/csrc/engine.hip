@@ -359,13 +359,18 @@ struct srgd_engine {
   int* d_step = nullptr;
   hipStream_t cap_stream = nullptr;
   bool use_graphs = true;
-  bool capturing = false;
-  struct StepGraph {
+  struct StepKey {                   // everything a captured step bakes in besides what it reads through d_step
+    int mode;                        // 0: DDPM step, 1: EDM step
     int parity, passes, kind, sub_batch; float scale; const void *img, *cond, *xs; uint64_t seed; bool last;
     int tile_first, tile_count; bool ring;
-    int mode; const void* work;      // 0: DDPM step, 1: EDM step (work = its scratch canvases)
-    int seen; hipGraphExec_t exec; hipGraph_t graph;
+    const void* work;                // EDM step: its scratch canvases
+    bool operator==(const StepKey& o) const {
+      return mode == o.mode && parity == o.parity && passes == o.passes && kind == o.kind && sub_batch == o.sub_batch &&
+             scale == o.scale && img == o.img && cond == o.cond && xs == o.xs && seed == o.seed && last == o.last &&
+             tile_first == o.tile_first && tile_count == o.tile_count && ring == o.ring && work == o.work;
+    }
   };
+  struct StepGraph { StepKey key; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; };   // no exec yet: seen once, run eagerly
   std::vector<StepGraph> graphs;
 
   // profiling
@@ -644,6 +649,20 @@ template <typename T> int ensure(srgd_engine* e, T** p, size_t* cap, size_t need
   *p = nullptr;
   SRGD_HIP(hipMalloc((void**)p, need_elems * sizeof(T)));
   *cap = need_elems;
+  return 0;
+}
+
+// The per-step scalar records of a run (StepScalars into d_sc, EdmScalars into d_edm; the C ABI's host struct has Rec's
+// layout).  Unlike ensure() it drops no step graph: the begin entry it serves does that (sampler_begin_common).
+template <typename Rec> int upload_step_scalars(srgd_engine* e, Rec** dev, int* cap, int n_steps, const void* host, hipStream_t st) {
+  SRGD_HIP(hipSetDevice(e->cfg.device));
+  if (*cap < n_steps) {
+    if (*dev) hipFree(*dev);
+    *dev = nullptr;
+    SRGD_HIP(hipMalloc((void**)dev, (size_t)n_steps * sizeof(Rec)));
+    *cap = n_steps;
+  }
+  SRGD_HIP(hipMemcpyAsync(*dev, host, (size_t)n_steps * sizeof(Rec), hipMemcpyHostToDevice, st));
   return 0;
 }
 
@@ -1248,6 +1267,107 @@ void launch_step_rows(srgd_engine* e, int nb, int nt, const int* tiles, int firs
                      2 * ev + (pass1_null ? row_null : row_label));
 }
 
+// what a network evaluation of a sampler step needs besides its tiles
+struct StepEval {
+  int passes, guidance_kind;
+  float guidance_scale;
+  float *img, *x_start;      // the canvases the final step updates
+  int ev;                    // evaluation of the step whose conditioning rows it takes (EDM: 0 at sigma_hat, 1 at sigma_next)
+  int evals;                 // evaluations per step the conditioning table holds: 1 (DDPM), 2 (EDM, both solvers)
+};
+
+// One U-Net evaluation of one launch's tiles, the same for every sampler step: input conv from the canvases -> conditioning
+// rows -> U-Net body -> fused output conv + step update scattered into the canvases.  The two launches that differ between the
+// steps come in as callables: gather(use_cond_mask, padded) fills the input conv's haloed image, final_launch(fa) sets the
+// FinalStepArgs fields of its own (noise, noise_per_class, sc: zero on arrival) and launches the step's final kernel.
+// The order of pool gets / puts and of launches is fixed: it is the topology of a captured step, and under Pool::no_alloc the
+// pool's reuse pattern decides the addresses.
+template <typename Gather, typename Final>
+int eval_tile_batch(srgd_engine* e, const TileBatch& tb, const StepEval& s, hipStream_t st, Gather&& gather, Final&& final_launch) {
+  const int tile = tb.tile, nt = tb.ntiles, nb = nt * s.passes;
+  // the second pass of a guided step: without the condition (condition guidance, kind 2: mask bit p = pass p sees it) or on
+  // the null conditioning row (class guidance, kind 1)
+  const int mask = (s.passes == 2 && s.guidance_kind == 2) ? 0x1 : 0x3;
+  const bool pass1_null = s.passes == 2 && s.guidance_kind == 1;
+  void* x0 = e->pool.get((size_t)nb * tile * tile * e->dim * e->es);
+  if (!x0) return -1;
+  {
+    Prof p(e, KC_INIT, st);
+    void* padded = e->pool.get((size_t)nb * (tile + 6) * (tile + 8) * 8 * e->es);
+    if (!padded) return -1;
+    SRGD_TRY(gather(mask, padded));
+    SRGD_TRY(run_init7(e, padded, nb, tile, tile, x0, st));
+    e->pool.put(padded);
+  }
+  // conditioning row = base + evals * (K+1) * step (the step's share is added on the device: Ctx::step_mul), base = (K+1) * ev +
+  // (label row / K: none); K = 1 unless the run has per-image labels
+  launch_step_rows(e, nb, nt, tb.tile_yx, tb.first, s.ev, pass1_null, st);
+  Ctx x{e, nb, tile, tile, e->d_rows, e->ct_sampler.table, st, e->d_step, s.evals * (e->n_labels + 1)};
+  void* act = nullptr;
+  float* eps4 = final_fusion_possible(e) ? (float*)e->pool.get((size_t)nb * tile * tile * 16) : nullptr;
+  if (final_fusion_possible(e) && !eps4) return -1;
+  x.eps4 = eps4;
+  SRGD_TRY(unet_body(x, x0, &act));
+  FinalStepArgs fa{};
+  fa.act = act; fa.C = e->dim; fa.passes = s.passes; fa.guidance = s.guidance_scale;
+  fa.w = e->final_w; fa.bias = e->final_b; fa.img = s.img; fa.x_start = s.x_start;
+  fa.step_ptr = e->d_step;
+  fa.eps4 = x.eps4_done ? eps4 : nullptr;
+  { Prof p(e, KC_FINAL, st); SRGD_TRY(final_launch(fa)); }
+  if (eps4) e->pool.put(eps4);
+  e->pool.put(act);
+  e->pool.put(x0);
+  return 0;
+}
+
+// what step_prologue works out for a step entry
+struct StepPlan {
+  int parity;                // grid of the step
+  bool last;
+  int tile_first, tile_count;   // the (normalised) range of the grid's image-major tile list this call covers
+  int sub_batch;             // tiles per U-Net launch
+};
+
+// What every step entry does before its launches: the argument checks (messages under the entry's `name`; `null_arg` is the
+// entry's test of its own pointers, reported after the step check), the tile range (tile_count < 0: to the end of the grid),
+// the size of a launch, and the scratch for it - every allocation of a step happens before any capture.
+int step_prologue(srgd_engine* e, const char* name, bool edm, bool null_arg, int step, int tile_first, int tile_count, int passes,
+                  int guidance_kind, int sub_batch, StepPlan* plan) {
+  const std::string nm(name);
+  if (!e || !e->run_active || e->run_is_edm != edm) SRGD_FAIL(nm + ": call " + (edm ? "srgd_edm_begin" : "srgd_sampler_begin") + " first");
+  if (step < 0 || step >= e->n_steps) SRGD_FAIL(nm + ": step out of range");
+  if (null_arg) SRGD_FAIL(nm + ": null argument");
+  if (passes != 1 && passes != 2) SRGD_FAIL(nm + ": passes must be 1 or 2");
+  if (passes == 2 && guidance_kind != 1 && guidance_kind != 2) SRGD_FAIL(nm + ": guidance_kind must be 1 or 2");
+  if (sub_batch < 1) SRGD_FAIL(nm + ": sub_batch must be >= 1");
+  SRGD_HIP(hipSetDevice(e->cfg.device));
+  const int parity = step & 1;
+  const int n = e->n_grid[parity];
+  if (tile_count < 0) tile_count = n - tile_first;
+  if (tile_first < 0 || tile_count < 0 || tile_first + tile_count > n) SRGD_FAIL(nm + "_tiles: tile range outside the grid");
+  e->run_stepped = true;
+  // at most the range's tiles per launch (a whole grid is never empty - the begin entries reject one - so for an entry without
+  // a range this is min(sub_batch, n))
+  sub_batch = std::max(1, std::min(sub_batch, std::max(tile_count, 1)));
+  // balanced launches: the same number of U-Net launches, but of (almost) equal size - 1,089 tiles at a limit of 125 run as
+  // 9 x 121, not 8 x 125 + 89, and a rank's 137-tile slice of a sharded canvas as 69 + 68, not 125 + 12 (a 12-tile launch
+  // fills a fraction of the chip on the deep layers and costs about as much as a 16-tile one).  Tiles are independent within
+  // a step, so the result does not depend on how a step's tiles are grouped (tested bit-identical).
+  if (tile_count > sub_batch) sub_batch = cdiv(tile_count, cdiv(tile_count, sub_batch));
+  e->pool.reset_busy();
+  SRGD_TRY(ensure_scratch(e, sub_batch * passes, e->geo.tile, e->geo.tile));
+  *plan = StepPlan{parity, step == e->n_steps - 1, tile_first, tile_count, sub_batch};
+  return 0;
+}
+
+// The last act of a step entry before the step's launches: the step index goes to the device counter they read it through.
+// Not part of step_prologue: the entry's own noise-buffer allocations come between the two, ahead of the counter's.
+int set_device_step(srgd_engine* e, int step, hipStream_t st) {
+  if (!e->d_step) SRGD_HIP(hipMalloc((void**)&e->d_step, sizeof(int)));
+  hipLaunchKernelGGL(set_step_kernel, dim3(1), dim3(1), 0, st, e->d_step, step);
+  return 0;
+}
+
 }  // namespace
 
 // Graph cache shared by the DDPM and the EDM step: the first occurrence of a key runs eagerly (it warms the activation pool and
@@ -1255,16 +1375,12 @@ void launch_step_rows(srgd_engine* e, int nb, int nt, const int* tiles, int firs
 // stream, which cannot capture; nothing executes during capture), later ones replay on the caller's stream.
 extern "C++" {
 template <typename Launch>
-static int run_step_through_graph(srgd_engine* e, const srgd_engine::StepGraph& key, hipStream_t st, Launch&& launch) {
+static int run_step_through_graph(srgd_engine* e, const srgd_engine::StepKey& key, hipStream_t st, Launch&& launch) {
   srgd_engine::StepGraph* sg = nullptr;
   for (auto& c : e->graphs)
-    if (c.mode == key.mode && c.parity == key.parity && c.passes == key.passes && c.kind == key.kind &&
-        c.sub_batch == key.sub_batch && c.scale == key.scale && c.img == key.img && c.cond == key.cond && c.xs == key.xs &&
-        c.seed == key.seed && c.last == key.last && c.tile_first == key.tile_first && c.tile_count == key.tile_count &&
-        c.ring == key.ring && c.work == key.work)
-      sg = &c;
+    if (c.key == key) sg = &c;
   if (!sg) {
-    e->graphs.push_back(key);
+    e->graphs.push_back({key});
     return launch(st);
   }
   if (!sg->exec) {
@@ -1675,25 +1791,13 @@ static int sampler_begin_uniform(srgd_engine* e, const srgd_sampler_geometry* g,
   return 0;
 }
 
-static int upload_step_scalars(srgd_engine* e, int n_steps, const srgd_step_scalars* scalars_host, hipStream_t st) {
-  SRGD_HIP(hipSetDevice(e->cfg.device));
-  if (e->sc_cap < n_steps) {
-    if (e->d_sc) hipFree(e->d_sc);
-    e->d_sc = nullptr;
-    SRGD_HIP(hipMalloc((void**)&e->d_sc, (size_t)n_steps * sizeof(StepScalars)));
-    e->sc_cap = n_steps;
-  }
-  SRGD_HIP(hipMemcpyAsync(e->d_sc, scalars_host, (size_t)n_steps * sizeof(StepScalars), hipMemcpyHostToDevice, st));
-  return 0;
-}
-
 int srgd_sampler_begin(srgd_engine* e, const srgd_sampler_geometry* g, const float* cond01, float* cond_canvas,
                        const int32_t* tiles_even_host, const int32_t* tiles_odd_host, int n_steps,
                        const srgd_step_scalars* scalars_host, const float* log_snr_host, int class_id, void* stream) {
   if (!scalars_host) SRGD_FAIL("srgd_sampler_begin: null argument");
   hipStream_t st = (hipStream_t)stream;
   static_assert(sizeof(StepScalars) == sizeof(srgd_step_scalars), "step scalar layout");
-  if (e && n_steps > 0) SRGD_TRY(upload_step_scalars(e, n_steps, scalars_host, st));
+  if (e && n_steps > 0) SRGD_TRY(upload_step_scalars(e, &e->d_sc, &e->sc_cap, n_steps, scalars_host, st));
   SRGD_TRY(sampler_begin_uniform(e, g, cond01, cond_canvas, tiles_even_host, tiles_odd_host, n_steps, log_snr_host, n_steps,
                                  class_id, st));
   e->run_active = true;
@@ -1715,7 +1819,7 @@ int srgd_sampler_begin_images(srgd_engine* e, int tile, int n_images, const srgd
     oe += images[i].n_even;
     oo += images[i].n_odd;
   }
-  if (e && n_steps > 0) SRGD_TRY(upload_step_scalars(e, n_steps, scalars_host, st));
+  if (e && n_steps > 0) SRGD_TRY(upload_step_scalars(e, &e->d_sc, &e->sc_cap, n_steps, scalars_host, st));
   SRGD_TRY(sampler_begin_common(e, tile, ims, cond01, cond_canvas, n_steps, log_snr_host, n_steps, class_id, st));
   e->geo = srgd_sampler_geometry{};
   e->geo.tile = tile;
@@ -1731,17 +1835,8 @@ int srgd_edm_begin(srgd_engine* e, const srgd_sampler_geometry* g, const float* 
                    const srgd_edm_scalars* scalars_host, const float* c_noise_host, int class_id, void* stream) {
   if (!scalars_host) SRGD_FAIL("srgd_edm_begin: null argument");
   hipStream_t st = (hipStream_t)stream;
-  if (e && n_steps > 0) {
-    SRGD_HIP(hipSetDevice(e->cfg.device));
-    if (e->edm_cap < n_steps) {
-      if (e->d_edm) hipFree(e->d_edm);
-      e->d_edm = nullptr;
-      SRGD_HIP(hipMalloc((void**)&e->d_edm, (size_t)n_steps * sizeof(EdmScalars)));
-      e->edm_cap = n_steps;
-    }
-    static_assert(sizeof(EdmScalars) == sizeof(srgd_edm_scalars), "EDM scalar layout");
-    SRGD_HIP(hipMemcpyAsync(e->d_edm, scalars_host, (size_t)n_steps * sizeof(EdmScalars), hipMemcpyHostToDevice, st));
-  }
+  static_assert(sizeof(EdmScalars) == sizeof(srgd_edm_scalars), "EDM scalar layout");
+  if (e && n_steps > 0) SRGD_TRY(upload_step_scalars(e, &e->d_edm, &e->edm_cap, n_steps, scalars_host, st));
   // two network evaluations per step: rows 4i..4i+1 for c_noise(sigma_hat_i), 4i+2..4i+3 for c_noise(sigma_next_i)
   SRGD_TRY(sampler_begin_uniform(e, g, cond01, cond_canvas, tiles_even_host, tiles_odd_host, n_steps, c_noise_host,
                                  2 * n_steps, class_id, st));
@@ -1820,42 +1915,19 @@ static int edm_step_launch(srgd_engine* e, bool last, int parity, int tile_first
     SRGD_TRY(philox_normal(e->rng_tiles, canvas1, seed, 2ull << 32, e->d_step, st));
     z = e->rng_tiles;
   }
-  const int mask = (passes == 2 && guidance_kind == 2) ? 0x1 : 0x3;
   for (int first = tile_first; first < n; first += sub_batch) {
-    const int nt = std::min(sub_batch, n - first);
-    const int nb = nt * passes;
-    TileBatch tb{tiles, first, nt, g.Hp, g.Wp, g.tile, n_local, e->d_images, parity};
-    for (int ep = 0; ep < (last ? 1 : 2); ++ep) {
-      void* x0 = e->pool.get((size_t)nb * g.tile * g.tile * e->dim * e->es);
-      if (!x0) return -1;
-      {
-        Prof p(e, KC_INIT, st);
-        void* padded = e->pool.get((size_t)nb * (g.tile + 6) * (g.tile + 8) * 8 * e->es);
-        if (!padded) return -1;
-        SRGD_TRY(init_gather_from_canvas_edm(ep == 0 ? img : work, ep == 0 ? z : nullptr, cond_canvas, tb, passes, mask,
-                                             e->d_edm, e->d_step, ep, padded, e->bf16, st));
-        SRGD_TRY(run_init7(e, padded, nb, g.tile, g.tile, x0, st));
-        e->pool.put(padded);
-      }
-      // conditioning row = base + 2(K+1) * step, base = (K+1) * (evaluation: 0 at sigma_hat, 1 at sigma_next) + (label row / K: none);
-      // K = 1 unless the run has per-image labels
-      launch_step_rows(e, nb, nt, tiles, first, ep, passes == 2 && guidance_kind == 1, st);
-      Ctx x{e, nb, g.tile, g.tile, e->d_rows, e->ct_sampler.table, st, e->d_step, 2 * (e->n_labels + 1)};
-      void* act = nullptr;
-      float* eps4 = final_fusion_possible(e) ? (float*)e->pool.get((size_t)nb * g.tile * g.tile * 16) : nullptr;
-      if (final_fusion_possible(e) && !eps4) return -1;
-      x.eps4 = eps4;
-      SRGD_TRY(unet_body(x, x0, &act));
-      FinalStepArgs fa;
-      fa.act = act; fa.C = e->dim; fa.passes = passes; fa.guidance = guidance_scale;
-      fa.w = e->final_w; fa.bias = e->final_b; fa.img = img; fa.x_start = x_start; fa.noise = z;
-      fa.sc = nullptr; fa.step_ptr = e->d_step;
-      fa.eps4 = x.eps4_done ? eps4 : nullptr;
-      { Prof p(e, KC_FINAL, st); SRGD_TRY(final_step_edm(fa, e->d_edm, work, canvas_elems, ep, tb, e->bf16, st)); }
-      if (eps4) e->pool.put(eps4);
-      e->pool.put(act);
-      e->pool.put(x0);
-    }
+    const TileBatch tb{tiles, first, std::min(sub_batch, n - first), g.Hp, g.Wp, g.tile, n_local, e->d_images, parity};
+    for (int ep = 0; ep < (last ? 1 : 2); ++ep)      // Euler evaluation from the canvas, Heun evaluation from the Euler result in `work`
+      SRGD_TRY(eval_tile_batch(
+          e, tb, StepEval{passes, guidance_kind, guidance_scale, img, x_start, ep, 2}, st,
+          [&](int mask, void* padded) {
+            return init_gather_from_canvas_edm(ep == 0 ? img : work, ep == 0 ? z : nullptr, cond_canvas, tb, passes, mask, e->d_edm,
+                                               e->d_step, ep, padded, e->bf16, st);
+          },
+          [&](FinalStepArgs& fa) {
+            fa.noise = z;
+            return final_step_edm(fa, e->d_edm, work, canvas_elems, ep, tb, e->bf16, st);
+          }));
   }
   if (parity == 1 && ring) {
     Prof p(e, KC_CANVAS, st);
@@ -1885,45 +1957,27 @@ int srgd_edm_step_tiles(srgd_engine* e, int step, int tile_first, int tile_count
                         const float* cond_canvas, float* x_start, float* work, const float* noise_canvas,
                         const float* ring_noise_canvas, int passes, int guidance_kind, float guidance_scale, int sub_batch,
                         uint64_t seed, void* stream) {
-  if (!e || !e->run_active || !e->run_is_edm) SRGD_FAIL("srgd_edm_step: call srgd_edm_begin first");
-  if (step < 0 || step >= e->n_steps) SRGD_FAIL("srgd_edm_step: step out of range");
-  if (!img || !cond_canvas || !work) SRGD_FAIL("srgd_edm_step: null argument");
-  if (passes != 1 && passes != 2) SRGD_FAIL("srgd_edm_step: passes must be 1 or 2");
-  if (passes == 2 && guidance_kind != 1 && guidance_kind != 2) SRGD_FAIL("srgd_edm_step: guidance_kind must be 1 or 2");
-  if (sub_batch < 1) SRGD_FAIL("srgd_edm_step: sub_batch must be >= 1");
   hipStream_t st = (hipStream_t)stream;
-  SRGD_HIP(hipSetDevice(e->cfg.device));
-  const srgd_sampler_geometry& g = e->geo;
-  const int parity = step & 1;
-  const int n = (parity ? g.n_odd : g.n_even) * g.n_images;
-  const bool last = step == e->n_steps - 1;
-  if (tile_count < 0) tile_count = n - tile_first;
-  if (tile_first < 0 || tile_count < 0 || tile_first + tile_count > n) SRGD_FAIL("srgd_edm_step_tiles: tile range outside the grid");
+  StepPlan p;
+  SRGD_TRY(step_prologue(e, "srgd_edm_step", /*edm=*/true, /*null_arg=*/!img || !cond_canvas || !work, step, tile_first, tile_count, passes,
+                         guidance_kind, sub_batch, &p));
   const bool ring = do_ring != 0;
-  e->run_stepped = true;
-  sub_batch = std::max(1, std::min(sub_batch, std::max(tile_count, 1)));
-  // balanced launches: the same number of U-Net launches, but of (almost) equal size - 1,089 tiles at a limit of 125 run as
-  // 9 x 121, not 8 x 125 + 89, and a rank's 137-tile slice of a sharded canvas as 69 + 68, not 125 + 12 (a 12-tile launch
-  // fills a fraction of the chip on the deep layers and costs about as much as a 16-tile one).  Tiles are independent within
-  // a step, so the result does not depend on how a step's tiles are grouped (tested bit-identical).
-  if (tile_count > sub_batch) sub_batch = cdiv(tile_count, cdiv(tile_count, sub_batch));
-  const size_t canvas1 = (size_t)3 * g.Hp * g.Wp;
-  e->pool.reset_busy();
-  // every allocation happens here, before any capture
-  SRGD_TRY(ensure_scratch(e, sub_batch * passes, g.tile, g.tile));
+  const size_t canvas1 = (size_t)3 * e->geo.Hp * e->geo.Wp;
   if (!noise_canvas) SRGD_TRY(ensure(e, &e->rng_tiles, &e->rng_tiles_cap, canvas1));
-  if (!ring_noise_canvas && parity == 1 && ring) SRGD_TRY(ensure(e, &e->rng_canvas, &e->rng_canvas_cap, canvas1));
-  if (!e->d_step) SRGD_HIP(hipMalloc((void**)&e->d_step, sizeof(int)));
-  hipLaunchKernelGGL(set_step_kernel, dim3(1), dim3(1), 0, st, e->d_step, step);
+  if (!ring_noise_canvas && p.parity == 1 && ring) SRGD_TRY(ensure(e, &e->rng_canvas, &e->rng_canvas_cap, canvas1));
+  SRGD_TRY(set_device_step(e, step, st));
   const bool graphable = e->use_graphs && !e->prof_on && !noise_canvas && !ring_noise_canvas;
   if (!graphable)
-    return edm_step_launch(e, last, parity, tile_first, tile_count, ring, img, cond_canvas, x_start, work, noise_canvas,
-                           ring_noise_canvas, passes, guidance_kind, guidance_scale, sub_batch, seed, st);
-  const srgd_engine::StepGraph key{parity, passes, guidance_kind, sub_batch, guidance_scale, img, cond_canvas, x_start, seed, last,
-                                   tile_first, tile_count, ring, 1, work, 1, nullptr, nullptr};
+    return edm_step_launch(e, p.last, p.parity, p.tile_first, p.tile_count, ring, img, cond_canvas, x_start, work, noise_canvas,
+                           ring_noise_canvas, passes, guidance_kind, guidance_scale, p.sub_batch, seed, st);
+  srgd_engine::StepKey key{};
+  key.mode = 1; key.work = work;
+  key.parity = p.parity; key.last = p.last; key.tile_first = p.tile_first; key.tile_count = p.tile_count; key.sub_batch = p.sub_batch;
+  key.passes = passes; key.kind = guidance_kind; key.scale = guidance_scale; key.seed = seed; key.ring = ring;
+  key.img = img; key.cond = cond_canvas; key.xs = x_start;
   return run_step_through_graph(e, key, st, [&](hipStream_t s2) {
-    return edm_step_launch(e, last, parity, tile_first, tile_count, ring, img, cond_canvas, x_start, work, nullptr, nullptr,
-                           passes, guidance_kind, guidance_scale, sub_batch, seed, s2);
+    return edm_step_launch(e, p.last, p.parity, p.tile_first, p.tile_count, ring, img, cond_canvas, x_start, work, nullptr, nullptr,
+                           passes, guidance_kind, guidance_scale, p.sub_batch, seed, s2);
   });
 }
 
@@ -1931,60 +1985,26 @@ int srgd_edm_step_tiles(srgd_engine* e, int step, int tile_first, int tile_count
 // multistep update against the previous step's denoised canvas.  Deterministic (no noise), launched eagerly.
 int srgd_edm_dpmpp_step(srgd_engine* e, int step, float* img, const float* cond_canvas, float* x_start, float* old_denoised,
                         int passes, int guidance_kind, float guidance_scale, int sub_batch, void* stream) {
-  if (!e || !e->run_active || !e->run_is_edm) SRGD_FAIL("srgd_edm_dpmpp_step: call srgd_edm_begin first");
-  if (step < 0 || step >= e->n_steps) SRGD_FAIL("srgd_edm_dpmpp_step: step out of range");
-  if (!img || !cond_canvas || !old_denoised) SRGD_FAIL("srgd_edm_dpmpp_step: null argument");
-  if (passes != 1 && passes != 2) SRGD_FAIL("srgd_edm_dpmpp_step: passes must be 1 or 2");
-  if (passes == 2 && guidance_kind != 1 && guidance_kind != 2) SRGD_FAIL("srgd_edm_dpmpp_step: guidance_kind must be 1 or 2");
-  if (sub_batch < 1) SRGD_FAIL("srgd_edm_dpmpp_step: sub_batch must be >= 1");
   hipStream_t st = (hipStream_t)stream;
-  SRGD_HIP(hipSetDevice(e->cfg.device));
+  StepPlan p;
+  SRGD_TRY(step_prologue(e, "srgd_edm_dpmpp_step", /*edm=*/true, /*null_arg=*/!img || !cond_canvas || !old_denoised, step, 0, -1, passes,
+                         guidance_kind, sub_batch, &p));
+  SRGD_TRY(set_device_step(e, step, st));
   const srgd_sampler_geometry& g = e->geo;
-  const int parity = step & 1;
-  const int n_local = parity ? g.n_odd : g.n_even;
-  const int n = n_local * g.n_images;
-  const int* tiles = parity ? e->d_tiles_odd : e->d_tiles_even;
-  sub_batch = std::min(sub_batch, n);
-  if (n > sub_batch) sub_batch = cdiv(n, cdiv(n, sub_batch));          // balanced launches (srgd_sampler_step_tiles)
+  const int* tiles = p.parity ? e->d_tiles_odd : e->d_tiles_even;
   const size_t canvas_elems = (size_t)3 * g.Hp * g.Wp * g.n_images;
-  e->pool.reset_busy();
-  SRGD_TRY(ensure_scratch(e, sub_batch * passes, g.tile, g.tile));
-  if (!e->d_step) SRGD_HIP(hipMalloc((void**)&e->d_step, sizeof(int)));
-  hipLaunchKernelGGL(set_step_kernel, dim3(1), dim3(1), 0, st, e->d_step, step);
-  const int mask = (passes == 2 && guidance_kind == 2) ? 0x1 : 0x3;
-  e->run_stepped = true;
-  for (int first = 0; first < n; first += sub_batch) {
-    const int nt = std::min(sub_batch, n - first);
-    const int nb = nt * passes;
-    TileBatch tb{tiles, first, nt, g.Hp, g.Wp, g.tile, n_local, e->d_images, parity};
-    void* x0 = e->pool.get((size_t)nb * g.tile * g.tile * e->dim * e->es);
-    if (!x0) return -1;
-    {
-      Prof p(e, KC_INIT, st);
-      void* padded = e->pool.get((size_t)nb * (g.tile + 6) * (g.tile + 8) * 8 * e->es);
-      if (!padded) return -1;
-      SRGD_TRY(init_gather_from_canvas_edm(img, nullptr, cond_canvas, tb, passes, mask, e->d_edm, e->d_step, 2, padded,
-                                           e->bf16, st));
-      SRGD_TRY(run_init7(e, padded, nb, g.tile, g.tile, x0, st));
-      e->pool.put(padded);
-    }
-    // conditioning rows of evaluation 0 (c_noise at sigma_i), as in edm_step_launch
-    launch_step_rows(e, nb, nt, tiles, first, 0, passes == 2 && guidance_kind == 1, st);
-    Ctx x{e, nb, g.tile, g.tile, e->d_rows, e->ct_sampler.table, st, e->d_step, 2 * (e->n_labels + 1)};
-    void* act = nullptr;
-    float* eps4 = final_fusion_possible(e) ? (float*)e->pool.get((size_t)nb * g.tile * g.tile * 16) : nullptr;
-    if (final_fusion_possible(e) && !eps4) return -1;
-    x.eps4 = eps4;
-    SRGD_TRY(unet_body(x, x0, &act));
-    FinalStepArgs fa;
-    fa.act = act; fa.C = e->dim; fa.passes = passes; fa.guidance = guidance_scale;
-    fa.w = e->final_w; fa.bias = e->final_b; fa.img = img; fa.x_start = x_start; fa.noise = nullptr;
-    fa.sc = nullptr; fa.step_ptr = e->d_step;
-    fa.eps4 = x.eps4_done ? eps4 : nullptr;
-    { Prof p(e, KC_FINAL, st); SRGD_TRY(final_step_edm(fa, e->d_edm, old_denoised, canvas_elems, 2, tb, e->bf16, st)); }
-    if (eps4) e->pool.put(eps4);
-    e->pool.put(act);
-    e->pool.put(x0);
+  // conditioning rows of evaluation 0 (c_noise at sigma_i) of the two the table holds per step; gather and final step in their
+  // DPM-Solver++ form (edm_pass 2)
+  const StepEval ev{passes, guidance_kind, guidance_scale, img, x_start, 0, 2};
+  for (int first = 0; first < p.tile_count; first += p.sub_batch) {
+    const TileBatch tb{tiles, first, std::min(p.sub_batch, p.tile_count - first), g.Hp, g.Wp, g.tile, p.parity ? g.n_odd : g.n_even,
+                       e->d_images, p.parity};
+    SRGD_TRY(eval_tile_batch(
+        e, tb, ev, st,
+        [&](int mask, void* padded) {
+          return init_gather_from_canvas_edm(img, nullptr, cond_canvas, tb, passes, mask, e->d_edm, e->d_step, 2, padded, e->bf16, st);
+        },
+        [&](FinalStepArgs& fa) { return final_step_edm(fa, e->d_edm, old_denoised, canvas_elems, 2, tb, e->bf16, st); }));
   }
   return 0;
 }
@@ -2012,43 +2032,22 @@ static int sampler_step_launch(srgd_engine* e, bool last, int parity, int tile_f
       nz = e->rng_tiles;
     }
   }
+  const StepEval ev{passes, guidance_kind, guidance_scale, img, x_start, 0, 1};
   for (int first = tile_first; first < n; first += sub_batch) {
-    const int nt = std::min(sub_batch, n - first);
-    const int nb = nt * passes;
-    TileBatch tb{tiles, first, nt, g.Hp, g.Wp, g.tile, 0, e->d_images, parity};
-    void* x0 = e->pool.get((size_t)nb * g.tile * g.tile * e->dim * e->es);
-    if (!x0) return -1;
-    const int mask = (passes == 2 && guidance_kind == 2) ? 0x1 : 0x3;
-    {
-      Prof p(e, KC_INIT, st);
-      void* padded = e->pool.get((size_t)nb * (g.tile + 6) * (g.tile + 8) * 8 * e->es);
-      if (!padded) return -1;
-      SRGD_TRY(init_gather_from_canvas(img, cond_canvas, tb, passes, mask, padded, e->bf16, st));
-      SRGD_TRY(run_init7(e, padded, nb, g.tile, g.tile, x0, st));
-      e->pool.put(padded);
-    }
-    launch_step_rows(e, nb, nt, tiles, first, 0, passes == 2 && guidance_kind == 1, st);   // + (K+1) * step inside gn_finalize
-    Ctx x{e, nb, g.tile, g.tile, e->d_rows, e->ct_sampler.table, st, e->d_step, e->n_labels + 1};
-    void* act = nullptr;
-    float* eps4 = final_fusion_possible(e) ? (float*)e->pool.get((size_t)nb * g.tile * g.tile * 16) : nullptr;
-    if (final_fusion_possible(e) && !eps4) return -1;
-    x.eps4 = eps4;
-    SRGD_TRY(unet_body(x, x0, &act));
-    FinalStepArgs fa;
-    fa.act = act; fa.C = e->dim; fa.passes = passes; fa.guidance = guidance_scale;
-    fa.w = e->final_w; fa.bias = e->final_b; fa.img = img; fa.x_start = x_start; fa.noise = nz;
-    fa.noise_per_class = (noise_tiles || e->run_seeded) ? 1 : 0;
-    fa.sc = e->d_sc; fa.step_ptr = e->d_step;
-    fa.eps4 = x.eps4_done ? eps4 : nullptr;
-    { Prof p(e, KC_FINAL, st);
-      if (e->prof_on) {
-        const double px = (double)nt * g.tile * g.tile;
-        e->fam_bytes[KC_FINAL] += px * passes * (fa.eps4 ? 16.0 : (double)e->dim * e->es) + px * 12.0 * (3.0 + (x_start ? 1.0 : 0.0));
-      }
-      SRGD_TRY(final_step(fa, tb, e->bf16, st)); }
-    if (eps4) e->pool.put(eps4);
-    e->pool.put(act);
-    e->pool.put(x0);
+    const TileBatch tb{tiles, first, std::min(sub_batch, n - first), g.Hp, g.Wp, g.tile, 0, e->d_images, parity};
+    SRGD_TRY(eval_tile_batch(
+        e, tb, ev, st,
+        [&](int mask, void* padded) { return init_gather_from_canvas(img, cond_canvas, tb, passes, mask, padded, e->bf16, st); },
+        [&](FinalStepArgs& fa) {
+          fa.noise = nz;
+          fa.noise_per_class = (noise_tiles || e->run_seeded) ? 1 : 0;
+          fa.sc = e->d_sc;
+          if (e->prof_on) {
+            const double px = (double)tb.ntiles * g.tile * g.tile;
+            e->fam_bytes[KC_FINAL] += px * passes * (fa.eps4 ? 16.0 : (double)e->dim * e->es) + px * 12.0 * (3.0 + (x_start ? 1.0 : 0.0));
+          }
+          return final_step(fa, tb, e->bf16, st);
+        }));
   }
   if (parity == 1 && ring) {
     Prof p(e, KC_CANVAS, st);
@@ -2088,46 +2087,28 @@ int srgd_sampler_step_tiles(srgd_engine* e, int step, int tile_first, int tile_c
                             const float* cond_canvas, float* x_start, const float* noise_tiles,
                             const float* noise_canvas, int passes, int guidance_kind, float guidance_scale,
                             int sub_batch, uint64_t seed, void* stream) {
-  if (!e || !e->run_active || e->run_is_edm) SRGD_FAIL("srgd_sampler_step: call srgd_sampler_begin first");
-  if (step < 0 || step >= e->n_steps) SRGD_FAIL("srgd_sampler_step: step out of range");
-  if (passes != 1 && passes != 2) SRGD_FAIL("srgd_sampler_step: passes must be 1 or 2");
-  if (passes == 2 && guidance_kind != 1 && guidance_kind != 2) SRGD_FAIL("srgd_sampler_step: guidance_kind must be 1 or 2");
-  if (sub_batch < 1) SRGD_FAIL("srgd_sampler_step: sub_batch must be >= 1");
   hipStream_t st = (hipStream_t)stream;
-  SRGD_HIP(hipSetDevice(e->cfg.device));
-  const srgd_sampler_geometry& g = e->geo;
-  const int parity = step & 1;
-  const int n = e->n_grid[parity];
-  const bool last = step == e->n_steps - 1;
-  if (tile_count < 0) tile_count = n - tile_first;
-  if (tile_first < 0 || tile_count < 0 || tile_first + tile_count > n) SRGD_FAIL("srgd_sampler_step_tiles: tile range outside the grid");
+  StepPlan p;
+  SRGD_TRY(step_prologue(e, "srgd_sampler_step", /*edm=*/false, /*null_arg=*/false, step, tile_first, tile_count, passes, guidance_kind,
+                         sub_batch, &p));
   const bool ring = do_ring != 0;
-  e->run_stepped = true;
-  sub_batch = std::max(1, std::min(sub_batch, std::max(tile_count, 1)));
-  // balanced launches: the same number of U-Net launches, but of (almost) equal size - 1,089 tiles at a limit of 125 run as
-  // 9 x 121, not 8 x 125 + 89, and a rank's 137-tile slice of a sharded canvas as 69 + 68, not 125 + 12 (a 12-tile launch
-  // fills a fraction of the chip on the deep layers and costs about as much as a 16-tile one).  Tiles are independent within
-  // a step, so the result does not depend on how a step's tiles are grouped (tested bit-identical).
-  if (tile_count > sub_batch) sub_batch = cdiv(tile_count, cdiv(tile_count, sub_batch));
-  e->pool.reset_busy();
-  // every allocation happens here, before any capture
-  SRGD_TRY(ensure_scratch(e, sub_batch * passes, g.tile, g.tile));
   if (!noise_tiles)    // a seeded run draws every class's tiles (sized by srgd_sampler_noise_seeds already; a no-op then)
     SRGD_TRY(ensure(e, &e->rng_tiles, &e->rng_tiles_cap,
-                    (size_t)(e->run_seeded ? e->class_tiles[parity] : e->max_local[parity]) * 3 * g.tile * g.tile));
+                    (size_t)(e->run_seeded ? e->class_tiles[p.parity] : e->max_local[p.parity]) * 3 * e->geo.tile * e->geo.tile));
   if (!noise_canvas && ring) SRGD_TRY(ensure(e, &e->rng_canvas, &e->rng_canvas_cap, e->class_canvas_elems));
-  if (!e->d_step) SRGD_HIP(hipMalloc((void**)&e->d_step, sizeof(int)));
-  hipLaunchKernelGGL(set_step_kernel, dim3(1), dim3(1), 0, st, e->d_step, step);
-
+  SRGD_TRY(set_device_step(e, step, st));
   const bool graphable = e->use_graphs && !e->prof_on && !noise_tiles && !noise_canvas;
   if (!graphable)
-    return sampler_step_launch(e, last, parity, tile_first, tile_count, ring, img, cond_canvas, x_start, noise_tiles,
-                               noise_canvas, passes, guidance_kind, guidance_scale, sub_batch, seed, st);
-  const srgd_engine::StepGraph key{parity, passes, guidance_kind, sub_batch, guidance_scale, img, cond_canvas, x_start, seed, last,
-                                   tile_first, tile_count, ring, 0, nullptr, 1, nullptr, nullptr};
+    return sampler_step_launch(e, p.last, p.parity, p.tile_first, p.tile_count, ring, img, cond_canvas, x_start, noise_tiles,
+                               noise_canvas, passes, guidance_kind, guidance_scale, p.sub_batch, seed, st);
+  srgd_engine::StepKey key{};
+  key.mode = 0; key.work = nullptr;
+  key.parity = p.parity; key.last = p.last; key.tile_first = p.tile_first; key.tile_count = p.tile_count; key.sub_batch = p.sub_batch;
+  key.passes = passes; key.kind = guidance_kind; key.scale = guidance_scale; key.seed = seed; key.ring = ring;
+  key.img = img; key.cond = cond_canvas; key.xs = x_start;
   return run_step_through_graph(e, key, st, [&](hipStream_t s2) {
-    return sampler_step_launch(e, last, parity, tile_first, tile_count, ring, img, cond_canvas, x_start, nullptr, nullptr, passes,
-                               guidance_kind, guidance_scale, sub_batch, seed, s2);
+    return sampler_step_launch(e, p.last, p.parity, p.tile_first, p.tile_count, ring, img, cond_canvas, x_start, nullptr, nullptr,
+                               passes, guidance_kind, guidance_scale, p.sub_batch, seed, s2);
   });
 }
 
