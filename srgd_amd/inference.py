@@ -12,7 +12,9 @@ the reference-compatible host noise stream to on-device Philox.
 from __future__ import annotations
 
 import glob
+import json
 import logging
+import math
 import os
 import random
 from argparse import ArgumentParser
@@ -23,6 +25,8 @@ from PIL import Image
 
 from .colorfix import color_fix_on_device  # noqa: F401  (public: srgd_amd.inference.color_fix_on_device)
 from .config import load_config
+from .metrics import KEYS as METRIC_KEYS
+from .metrics import metrics_on_device  # noqa: F401  (public: srgd_amd.inference.metrics_on_device)
 from .model import ConditionalElucidatedDiffusionSR, get_model
 
 logger = logging.getLogger("srgd_amd")
@@ -75,7 +79,17 @@ def parse_args(argv=None):
                    help="colour-correct every output against its x4 bicubic input on the GPU (engine extension): wavelet = the input's "
                         "low frequencies (five a-trous levels) under the output's high frequencies, adain = the input's per-channel "
                         "mean and standard deviation; with --samples every sample is corrected against the same input")
+    p.add_argument("--reference_dir", type=str, default=None, metavar="DIR",
+                   help="ground truth of the inputs: the reference of IN/NAME.png is DIR/NAME.png, exactly x4 its size.  Y-channel "
+                        "PSNR, RGB PSNR and Y-channel SSIM of every written file (as saved, after --color_fix) are computed on the GPU "
+                        "and written to OUTPUT_DIR/metrics.json with per-image means over --samples and a mean over all images "
+                        "(engine extension)")
+    p.add_argument("--crop_border", type=int, default=4, metavar="N",
+                   help="pixels cut from every side of output and reference before the --reference_dir numbers are taken (default 4, "
+                        "the scale factor, as the x4 super-resolution literature does)")
     args = p.parse_args(argv)
+    if args.crop_border < 0:
+        raise SystemExit(f"--crop_border: N must be >= 0, got {args.crop_border}")
     if args.samples < 1:
         raise SystemExit(f"--samples: K must be >= 1, got {args.samples}")
     if args.seed < 0 and args.samples > 1:
@@ -134,6 +148,82 @@ def _label_tensor(test_label, n_images, device):
 def _color_fix_kw(color_fix):
     """``tiled_sample``'s ``color_fix`` keyword for a set mode; nothing for None / "none" (the call a run without the flag makes)."""
     return {} if color_fix in (None, "none") else {"color_fix": color_fix}
+
+
+def _reference_kw(reference, crop_border):
+    """``tiled_sample``'s ``reference`` / ``crop_border`` keywords where a reference is given; nothing otherwise."""
+    return {} if reference is None else {"reference": reference, "crop_border": crop_border}
+
+
+def _split_quality(output, reference):
+    """``tiled_sample``'s return value as ``(images, metric dicts or None)``."""
+    return output if reference is not None else (output, None)
+
+
+def reference_problems(file_names, reference_dir, scale=4, crop_border=4):
+    """``--reference_dir`` pre-flight: one line per input file whose reference ``reference_dir/<same name>`` is missing, unreadable,
+    not exactly ``scale`` times the input's size, or too small for an 11x11 window inside the crop.  Only image headers are read."""
+    problems = []
+    for f in file_names:
+        name = os.path.basename(f)
+        ref = os.path.join(reference_dir, name)
+        try:
+            with Image.open(f) as im:
+                w, h = im.size
+        except (IOError, SyntaxError):
+            continue                                     # not an image: the sampling loop reports and skips it
+        if not os.path.isfile(ref):
+            problems.append(f"{name}: reference {ref} is missing")
+            continue
+        try:
+            with Image.open(ref) as im:
+                rw, rh = im.size
+        except (IOError, SyntaxError):
+            problems.append(f"{name}: reference {ref} cannot be read as an image")
+            continue
+        if (rw, rh) != (w * scale, h * scale):
+            problems.append(f"{name}: reference is {rw}x{rh}, x{scale} of the {w}x{h} input is {w * scale}x{h * scale}")
+        elif min(rw, rh) - 2 * crop_border < 11:
+            problems.append(f"{name}: {rw}x{rh} keeps fewer than 11x11 pixels inside a crop of {crop_border}")
+    return problems
+
+
+def check_references(file_names, reference_dir, scale=4, crop_border=4):
+    """Ends the run (``SystemExit``, non-zero) with the names ``reference_problems`` lists, before any sampling."""
+    problems = reference_problems(file_names, reference_dir, scale, crop_border)
+    if problems:
+        raise SystemExit("--reference_dir: " + str(len(problems)) + " input(s) without a usable reference:\n  " + "\n  ".join(problems))
+
+
+def load_reference(path):
+    """A ground-truth image as the uint8 ``[H,W,3]`` tensor ``tiled_sample(reference=...)`` takes (decoded on the host)."""
+    with Image.open(path) as im:
+        return torch.from_numpy(np.asarray(im.convert("RGB"), dtype=np.uint8).copy())
+
+
+def mean_record(records):
+    """Key-wise arithmetic mean of metric dicts (PSNR averaged in dB, the SR convention); inf and NaN propagate."""
+    return {k: sum(r[k] for r in records) / len(records) for k in METRIC_KEYS}
+
+
+def _json_record(record):
+    """A metric dict for JSON: finite numbers as they are, the others as the strings "nan", "inf", "-inf"."""
+    return {k: (v if math.isfinite(v) else ("nan" if math.isnan(v) else ("inf" if v > 0 else "-inf"))) for k, v in record.items()}
+
+
+def metrics_document(file_records, samples, crop_border):
+    """``metrics.json``: ``file_records`` = ``[(input file name, written file name, metric dict)]`` in run order ->
+    ``{"crop_border", "files": {written file: record}, "images": {input file: mean over its samples} (with --samples only),
+    "mean": mean over the images}``."""
+    per_image = {}
+    for name, _, rec in file_records:
+        per_image.setdefault(name, []).append(rec)
+    image_means = {name: mean_record(recs) for name, recs in per_image.items()}
+    doc = {"crop_border": crop_border, "files": {written: _json_record(rec) for _, written, rec in file_records}}
+    if samples > 1:
+        doc["images"] = {name: _json_record(rec) for name, rec in image_means.items()}
+    doc["mean"] = _json_record(mean_record(list(image_means.values())))
+    return doc
 
 
 def sample_output_name(file_name, k):
@@ -204,7 +294,11 @@ def unit_tensor_to_pil_on_device(t: torch.Tensor) -> Image.Image:
 
 def sr_target_image(image, sr_model, scale=4, batch_size=8, test_label=2, cond_scale=1.0, guidance_start_steps=0,
                     class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0,
-                    num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None):
+                    num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None, reference=None,
+                    crop_border=4):
+    """``reference`` (engine extension; here and in the three group forms below): the ground truth as a uint8 ``[H,W,3]`` tensor (a
+    list of one per image in the group forms).  The return value is then ``(image(s), metric dicts)``: PSNR / SSIM of every image as
+    saved, with ``crop_border`` pixels cut from every side (srgd_amd.metrics)."""
     width, height = image.size
     # the reference maps 'lanczos' to bicubic too (inference.py:66-69)
     condition_x = upsample_bicubic_on_device(image, scale, sr_model.device)
@@ -217,15 +311,18 @@ def sr_target_image(image, sr_model, scale=4, batch_size=8, test_label=2, cond_s
                                        class_cond_scale=class_cond_scale,
                                        class_guidance_start_steps=class_guidance_start_steps,
                                        generation_start_steps=generation_start_steps,
-                                       num_sample_steps=num_sample_steps, amp=enable_amp, **_color_fix_kw(color_fix))
+                                       num_sample_steps=num_sample_steps, amp=enable_amp, **_color_fix_kw(color_fix),
+                                       **_reference_kw(reference, crop_border))
+    output, quality = _split_quality(output, reference)
     sr_img = unit_tensor_to_pil_on_device(output[0])
     assert sr_img.size == (width * 4, height * 4)
-    return sr_img
+    return sr_img if reference is None else (sr_img, quality)
 
 
 def sr_target_images(images, sr_model, scale=4, batch_size=8, test_label=2, cond_scale=1.0, guidance_start_steps=0,
                      class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0,
-                     num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None):
+                     num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None, reference=None,
+                     crop_border=4):
     """``sr_target_image`` for several same-sized images in lock-step (engine extension): one ``tiled_sample`` call on a
     ``[B,3,H,W]`` condition.  Each image is sampled exactly as it would be alone after the reference's per-image
     ``seed_everything(seed)`` (inference.py:73) - bit-identical outputs - while their tiles fill the U-Net launches.
@@ -242,15 +339,18 @@ def sr_target_images(images, sr_model, scale=4, batch_size=8, test_label=2, cond
                                        class_cond_scale=class_cond_scale,
                                        class_guidance_start_steps=class_guidance_start_steps,
                                        generation_start_steps=generation_start_steps,
-                                       num_sample_steps=num_sample_steps, amp=enable_amp, **_color_fix_kw(color_fix))
+                                       num_sample_steps=num_sample_steps, amp=enable_amp, **_color_fix_kw(color_fix),
+                                       **_reference_kw(reference, crop_border))
+    output, quality = _split_quality(output, reference)
     outs = [unit_tensor_to_pil_on_device(o) for o in output]
     assert all(o.size == (width * 4, height * 4) for o in outs)
-    return outs
+    return outs if reference is None else (outs, quality)
 
 
 def sr_target_images_mixed(images, sr_model, scale=4, batch_size=8, test_label=2, cond_scale=1.0, guidance_start_steps=0,
                            class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0,
-                           num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None):
+                           num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None, reference=None,
+                           crop_border=4):
     """``sr_target_image`` for several images of any sizes in lock-step (engine extension): one ``tiled_sample`` call on a list
     of conditions.  Each image comes out bit-identical to its own ``sr_target_image`` run (with its own label where
     ``test_label`` is a sequence of one label per image)."""
@@ -264,15 +364,18 @@ def sr_target_images_mixed(images, sr_model, scale=4, batch_size=8, test_label=2
                                        class_cond_scale=class_cond_scale,
                                        class_guidance_start_steps=class_guidance_start_steps,
                                        generation_start_steps=generation_start_steps,
-                                       num_sample_steps=num_sample_steps, amp=enable_amp, **_color_fix_kw(color_fix))
+                                       num_sample_steps=num_sample_steps, amp=enable_amp, **_color_fix_kw(color_fix),
+                                       **_reference_kw(reference, crop_border))
+    output, quality = _split_quality(output, reference)
     outs = [unit_tensor_to_pil_on_device(o[0]) for o in output]
     assert all(o.size == (im.size[0] * 4, im.size[1] * 4) for o, im in zip(outs, images))
-    return outs
+    return outs if reference is None else (outs, quality)
 
 
 def sr_target_images_seeded(images, seeds, sr_model, scale=4, batch_size=8, test_label=2, cond_scale=1.0, guidance_start_steps=0,
                             class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0,
-                            num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None):
+                            num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None,
+                            reference=None, crop_border=4):
     """``sr_target_images_mixed`` with one noise seed per image (engine extension, ``tiled_sample(seeds=...)``): image i comes out
     bit-identical to its own ``sr_target_image`` run with ``seed=seeds[i]``; an image may appear several times with different
     seeds (each PIL image is upsampled once).  ``seed`` seeds the process as the other entry points do and is not a noise seed."""
@@ -290,10 +393,11 @@ def sr_target_images_seeded(images, seeds, sr_model, scale=4, batch_size=8, test
                                        class_guidance_start_steps=class_guidance_start_steps,
                                        generation_start_steps=generation_start_steps,
                                        num_sample_steps=num_sample_steps, amp=enable_amp, seeds=list(seeds),
-                                       **_color_fix_kw(color_fix))
+                                       **_color_fix_kw(color_fix), **_reference_kw(reference, crop_border))
+    output, quality = _split_quality(output, reference)
     outs = [unit_tensor_to_pil_on_device(o[0]) for o in output]
     assert all(o.size == (im.size[0] * 4, im.size[1] * 4) for o, im in zip(outs, images))
-    return outs
+    return outs if reference is None else (outs, quality)
 
 
 def plan_sample_entries(file_names, output_dir, samples, seed):
@@ -322,8 +426,12 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
                            guidance_start_steps=0, class_cond_scale=1.0, class_guidance_start_steps=0,
                            generation_start_steps=0, num_sample_steps=250, start_index=0, end_index=None,
                            enable_amp=False, interpolation="bicubic", seed=71, lockstep=1, lockstep_tiles=None, labels=None,
-                           samples=1, color_fix=None):
-    """``color_fix``: ``--color_fix`` (None / "none", "wavelet", "adain"), handed by keyword to whichever ``sr_target_image*``
+                           samples=1, color_fix=None, reference_dir=None, crop_border=4, metrics_name="metrics.json"):
+    """``reference_dir`` (``--reference_dir``): every input's ground truth ``reference_dir/<same name>`` is checked first (present,
+    exactly ``scale`` times the input: ``check_references``), decoded on the writer pool while earlier groups sample, and handed to
+    the group's ``sr_target_image*`` call; the numbers of every file written go to ``output_dir/metrics_name``
+    (``metrics_document``).  Without it nothing is checked, decoded or written.
+    ``color_fix``: ``--color_fix`` (None / "none", "wavelet", "adain"), handed by keyword to whichever ``sr_target_image*``
     function samples a group.  ``lockstep``: groups of up to N consecutive same-sized images; ``lockstep_tiles``: groups of consecutive images of any
     size up to that many tiles per even step (srgd_amd.lockstep.plan_lockstep_groups).  ``labels``: ``{file name: label}``
     (``--label_file``) for the images that do not take ``test_label``; a group may mix labels.  ``samples``: every image is
@@ -341,8 +449,12 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
               class_guidance_start_steps=class_guidance_start_steps, generation_start_steps=generation_start_steps,
               num_sample_steps=num_sample_steps, enable_amp=enable_amp, interpolation=interpolation, seed=seed,
               color_fix=None if color_fix in (None, "none") else color_fix)
+    file_names = sorted(glob.glob(f"{input_dir}/*"))[start_index:end_index]
+    if reference_dir is not None:
+        check_references(file_names, reference_dir, scale, crop_border)
     from concurrent.futures import ThreadPoolExecutor
-    pending, saves = [], []                              # (image, save_path, label, noise seed) of the current lock-step group; PNG writers
+    pending, saves = [], []                              # (image, save_path, label, noise seed, reference) of the current lock-step group; PNG writers
+    file_records = []                                    # (input file name, written file name, metric dict) of --reference_dir
 
     with ThreadPoolExecutor(max_workers=2) as pool:      # PNG encoding overlaps the next group's sampling
         def flush():
@@ -356,26 +468,35 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
             group_seeds = [e[3] for e in pending]
             one_label = group_labels[0] if len(set(group_labels)) == 1 else group_labels
             group_images = [e[0] for e in pending]
+            ref_kw = {}
+            if reference_dir is not None:                # the decoded references of the group (one future per input file)
+                ref_kw = {"reference": [e[4].result() for e in pending], "crop_border": crop_border}
             if len(pending) == 1:                        # a solo run with that seed: what every sample of a group is identical to
-                outs = [sr_target_image(pending[0][0], sr_model, test_label=group_labels[0], **dict(kw, seed=group_seeds[0]))]
+                solo_kw = dict(ref_kw, reference=ref_kw["reference"][0]) if ref_kw else {}
+                outs = sr_target_image(pending[0][0], sr_model, test_label=group_labels[0], **dict(kw, seed=group_seeds[0]), **solo_kw)
+                outs = ([outs[0]], outs[1]) if ref_kw else [outs]
             elif len(set(group_seeds)) > 1:
-                outs = sr_target_images_seeded(group_images, group_seeds, sr_model, test_label=one_label, **kw)
+                outs = sr_target_images_seeded(group_images, group_seeds, sr_model, test_label=one_label, **kw, **ref_kw)
             elif lockstep_tiles is not None:
-                outs = sr_target_images_mixed(group_images, sr_model, test_label=one_label, **dict(kw, seed=group_seeds[0]))
+                outs = sr_target_images_mixed(group_images, sr_model, test_label=one_label, **dict(kw, seed=group_seeds[0]), **ref_kw)
             else:
-                outs = sr_target_images(group_images, sr_model, test_label=one_label, **dict(kw, seed=group_seeds[0]))
+                outs = sr_target_images(group_images, sr_model, test_label=one_label, **dict(kw, seed=group_seeds[0]), **ref_kw)
+            if ref_kw:
+                outs, quality = outs
+                file_records.extend((e[5], os.path.basename(e[1]), q) for e, q in zip(pending, quality))
             for e, sr in zip(pending, outs):
                 saves.append(pool.submit(sr.save, e[1]))
             pending.clear()
 
-        opened = (None, None)                            # the K samples of a file share one decoded image
-        for filename, save_path, noise_seed in plan_sample_entries(sorted(glob.glob(f"{input_dir}/*"))[start_index:end_index],
-                                                                   output_dir, samples, seed):
+        opened = (None, None, None)                      # the K samples of a file share one decoded image and one reference
+        for filename, save_path, noise_seed in plan_sample_entries(file_names, output_dir, samples, seed):
             if opened[0] != filename:
-                opened = (filename, try_open_image(filename))
+                opened = (filename, try_open_image(filename), None)
                 if opened[1] is None:
                     print("Invalid image or unable to open image:", filename)
-            image = opened[1]
+                elif reference_dir is not None:          # decoded on the pool while the groups before this one sample
+                    opened = opened[:2] + (pool.submit(load_reference, os.path.join(reference_dir, os.path.basename(filename))),)
+            image, ref = opened[1], opened[2]
             if image is None:
                 continue
             label = labels.get(os.path.basename(filename), test_label)
@@ -385,16 +506,20 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
                 hr = [(h * scale, w * scale) for (w, h) in [e[0].size for e in pending] + [image.size]]
                 if len(plan_lockstep_groups(hr, lockstep_tiles)) > 1:      # the image would push the group over the budget
                     flush()
-                pending.append((image, save_path, label, noise_seed))
+                pending.append((image, save_path, label, noise_seed, ref, os.path.basename(filename)))
                 continue
             if pending and (len(pending) >= max(1, lockstep) or pending[0][0].size != image.size):
                 flush()
-            pending.append((image, save_path, label, noise_seed))
+            pending.append((image, save_path, label, noise_seed, ref, os.path.basename(filename)))
             if len(pending) >= max(1, lockstep):
                 flush()
         flush()
         for f in saves:
             f.result()                                   # surface write errors
+    if file_records:                                     # --reference_dir, and at least one file was sampled in this run
+        with open(os.path.join(output_dir, metrics_name), "w") as f:
+            json.dump(metrics_document(file_records, samples, crop_border), f, indent=1)
+            f.write("\n")
 
 
 def rank_file_range(n_files, start_index, end_index, rank, world):
@@ -412,13 +537,16 @@ def rank_file_range(n_files, start_index, end_index, rank, world):
 def main(argv=None):
     logging.basicConfig(level=logging.INFO, format="[%(levelname)s %(asctime)s] %(message)s")
     args = parse_args(argv)
+    world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
+    if args.reference_dir is not None:                   # every rank checks the whole selection, before the model is built
+        check_references(sorted(glob.glob(f"{args.input_dir}/*"))[args.start_index:args.end_index], args.reference_dir, 4,
+                         args.crop_border)
     conf = load_config(args.conf)
     conf.num_sample_steps = args.num_sample_steps
     conf.ckpt_path = args.ckpt_path
     ema_model = get_model(conf, logger)
     if not torch.cuda.is_available():
         raise SystemExit("srgd_amd needs an MI355X: no GPU visible and there is no CPU fallback")
-    world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     if world > 1:                                        # one process per GPU, each with its own slice of the input files
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")) % torch.cuda.device_count())
         n_files = len(glob.glob(f"{args.input_dir}/*"))
@@ -458,7 +586,8 @@ def main(argv=None):
                            num_sample_steps=args.num_sample_steps, start_index=args.start_index,
                            end_index=args.end_index, enable_amp=args.amp, interpolation=args.interpolation,
                            seed=args.seed, lockstep=args.lockstep, lockstep_tiles=args.lockstep_tiles, labels=args.labels,
-                           samples=args.samples, color_fix=args.color_fix)
+                           samples=args.samples, color_fix=args.color_fix, reference_dir=args.reference_dir,
+                           crop_border=args.crop_border, metrics_name="metrics.json" if world == 1 else f"metrics_rank{rank}.json")
 
 
 if __name__ == "__main__":

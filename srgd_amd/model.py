@@ -24,6 +24,7 @@ import torch.nn as nn
 from . import _lib
 from ._lib import SamplerGeometry, StepScalars
 from .colorfix import check_mode, color_fix_flat
+from .metrics import check_sizes, metrics_flat, pack_references
 from .engine import HipEngine
 from .lanes import StepLanes, lanes_setting_from_env, lanes_wanted
 
@@ -223,6 +224,17 @@ def _noise_seeds(seeds, n_images):
     return out
 
 
+def _packed_reference(reference, condition_x, crop_border, sampler):
+    """``tiled_sample(reference=...)``: the ground truth of every image of ``condition_x`` (a ``[B,3,H,W]`` tensor or a list of
+    ``[1,3,H_i,W_i]``) checked against the images' sizes before any sampling and packed into ``(flat uint8 device buffer, byte
+    offsets)``.  ValueError: count, dtype or shape do not fit, or an image keeps fewer than 11 x 11 pixels inside the crop."""
+    if sampler.canvas_group is not None:
+        raise NotImplementedError("reference on a canvas sharded over ranks (canvas_group)")
+    sizes = [(int(c.shape[-2]), int(c.shape[-1])) for c in condition_x]
+    check_sizes(sizes, crop_border)
+    return pack_references(reference, sizes, sampler.device)
+
+
 def _as_tuple(v, n):
     return tuple(v) if isinstance(v, (tuple, list)) else (v,) * n
 
@@ -417,7 +429,8 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
     def tiled_sample(self, batch_size=4, tile_size=256, tile_stride=256, condition_x=None, class_label=None,
                      cond_scale=1.0, guidance_start_steps=0, class_cond_scale=1.0, class_guidance_start_steps=0,
                      generation_start_steps=0, num_sample_steps=None, with_images=False, with_x0_images=False,
-                     start_white_noise=True, amp=False, precision=None, seeds=None, color_fix=None):
+                     start_white_noise=True, amp=False, precision=None, seeds=None, color_fix=None, reference=None,
+                     crop_border=4):
         """Tiled CFG-DDPM sampling (reference model.py:3288-3413).
 
         ``amp`` is accepted and ignored exactly as in the reference (which always computes fp32); the engine
@@ -445,8 +458,17 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
         ``"adain"`` - the final [0,1] image of every image of the run is colour-corrected against its own ``condition_x`` on the
         GPU (srgd_amd.colorfix, one batched call per run) and equals ``color_fix_on_device(uncorrected result, condition_x, mode)``
         bit for bit.  Trajectories (``with_images`` / ``with_x0_images``) stay raw; on a canvas sharded over ranks every rank
-        corrects its own copy of the whole output."""
+        corrects its own copy of the whole output.
+
+        ``reference`` (engine-only keyword, absent upstream): ``None`` (default: nothing is launched, the return value is what it
+        always was) or the ground truth of the run - a uint8 ``[H,W,3]`` tensor, or a list of them, one per image.  The return
+        value then gains a trailing list of ``{"psnr_y", "psnr_rgb", "ssim_y"}`` dicts, one per image: Y-channel PSNR, RGB PSNR and
+        Y-channel SSIM of the final image as it would be saved (after the colour fix) with ``crop_border`` pixels cut from every
+        side, computed on the GPU (srgd_amd.metrics, one batched call and one copy of 4 doubles per image).  Not available on a
+        canvas sharded over ranks."""
         color_fix = check_mode(color_fix)
+        if reference is not None:
+            reference = _packed_reference(reference, condition_x, crop_border, self)
         num_sample_steps = self.num_sample_steps if num_sample_steps is None else num_sample_steps
         if seeds is not None:
             as_list = isinstance(condition_x, (list, tuple))
@@ -467,7 +489,9 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
             outs = self._tiled_sample_images(batch_size, tile_size, list(condition_x), class_label, cond_scale,
                                              guidance_start_steps, class_cond_scale, class_guidance_start_steps,
                                              generation_start_steps, num_sample_steps, start_white_noise, precision, seeds=seeds,
-                                             color_fix=color_fix)
+                                             color_fix=color_fix, reference=reference, crop_border=crop_border)
+            if reference is not None:
+                return (outs[0] if as_list else torch.cat(outs[0], 0)), outs[1]
             return outs if as_list else torch.cat(outs, 0)
         if isinstance(condition_x, (list, tuple)):
             if with_images or with_x0_images:
@@ -482,7 +506,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
             return self._tiled_sample_images(batch_size, tile_size, list(condition_x), class_label, cond_scale,
                                              guidance_start_steps, class_cond_scale, class_guidance_start_steps,
                                              generation_start_steps, num_sample_steps, start_white_noise, precision,
-                                             color_fix=color_fix)
+                                             color_fix=color_fix, reference=reference, crop_border=crop_border)
         if cond_scale != 1.0 and class_cond_scale != 1.0:
             raise NotImplementedError("Currently, you cannot specify both cond_scale and class_cond_scale at the same time.")
         if tile_size != 256 or tile_stride != 256:
@@ -588,13 +612,16 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
         eng.sampler_end(img, out)
         if color_fix is not None:           # in place on the [B,3,H,W] result; the trajectories above stay raw
             color_fix_flat(out, cond01, [b * 3 * h * w for b in range(batch)], [(h, w)] * batch, color_fix)
-        if with_images:
-            return (out, image_list, x0_image_list) if with_x0_images else (out, image_list)
-        return out
+        ret = ((out, image_list, x0_image_list) if with_x0_images else (out, image_list)) if with_images else out
+        if reference is not None:           # of the image as saved: after the colour fix
+            quality = metrics_flat(out.view(-1), reference[0], [b * 3 * h * w for b in range(batch)], reference[1], [(h, w)] * batch,
+                                   crop_border)
+            return ret + (quality,) if with_images else (out, quality)
+        return ret
 
     def _tiled_sample_images(self, batch_size, tile_size, conds, class_label, cond_scale, guidance_start_steps,
                              class_cond_scale, class_guidance_start_steps, generation_start_steps, num_sample_steps,
-                             start_white_noise, precision, seeds=None, color_fix=None):
+                             start_white_noise, precision, seeds=None, color_fix=None, reference=None, crop_border=4):
         """Mixed-size lock-step (srgd_sampler_begin_images): every image keeps its own canvas, crop box, padding, inner box and
         tile grids; a step's tiles of all images share the U-Net launches.  Noise: the images of one noise class (canvas size)
         see the draw sequence a run of one of them alone sees.  Host noise: the generator state is taken once at entry and
@@ -604,7 +631,10 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
         ``seeds`` (one per image, validated by the caller): a noise class is a noise stream (canvas size, seed).  Host noise:
         stream k draws from a private ``torch.Generator().manual_seed(seed_k)`` - the stream of the global generator after
         ``torch.manual_seed(seed_k)`` - and the caller's generator is left alone.  Device noise: every engine of the run gets
-        the streams' seeds (srgd_sampler_noise_seeds) and draws all of them in one launch per use."""
+        the streams' seeds (srgd_sampler_noise_seeds) and draws all of them in one launch per use.
+
+        ``reference``: None, or ``(flat uint8 buffer, byte offsets)`` of the images' ground truth (``pack_references``); the return
+        value is then ``(outputs, list of metric dicts)``."""
         from .lockstep import plan_mixed_group
         dev = self.device
         if dev.type != "cuda":
@@ -714,18 +744,21 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
 
         out = torch.empty(sum(3 * p.H * p.W for p in plans), device=dev, dtype=torch.float32)
         eng.sampler_end(img, out)
+        starts = [0]
+        for p in plans:
+            starts.append(starts[-1] + 3 * p.H * p.W)
         if color_fix is not None:           # on the run's flat buffers: out and cond01 share the per-image layout
-            starts = [0]
-            for p in plans:
-                starts.append(starts[-1] + 3 * p.H * p.W)
             color_fix_flat(out, cond01, starts[:-1], [(p.H, p.W) for p in plans], color_fix)
+        quality = None
+        if reference is not None:           # on the same flat layout, after the colour fix
+            quality = metrics_flat(out, reference[0], starts[:-1], reference[1], [(p.H, p.W) for p in plans], crop_border)
         if host_noise and class_seeds is None:
             caller_gen.set_state(gens[plans[0].noise_class].get_state())
         outs, off = [], 0
         for p in plans:
             outs.append(out[off:off + 3 * p.H * p.W].view(1, 3, p.H, p.W))
             off += 3 * p.H * p.W
-        return outs
+        return outs if reference is None else (outs, quality)
 
     @torch.inference_mode()
     def sample(self, batch_size=16, condition_x=None, class_label=None, cond_scale=1.0, guidance_start_steps=0,
@@ -915,12 +948,16 @@ class ConditionalElucidatedDiffusionSR(nn.Module):
     def tiled_sample(self, batch_size=4, tile_size=256, tile_stride=256, condition_x=None, class_label=None,
                      cond_scale=1.0, guidance_start_steps=0, class_cond_scale=1.0, class_guidance_start_steps=0,
                      generation_start_steps=0, num_sample_steps=None, clamp=True, zero_init=False, with_images=False,
-                     with_x0_images=False, start_white_noise=True, amp=False, precision=None, seeds=None, color_fix=None):
+                     with_x0_images=False, start_white_noise=True, amp=False, precision=None, seeds=None, color_fix=None,
+                     reference=None, crop_border=4):
         """Reference model.py:2309-2475 (``start_white_noise`` and ``amp`` are accepted and unused there too; ``precision``
         is the engine-only override of ``self.precision``).  ``seeds`` (per-image noise seeds) is a DDPM-sampler feature and is
         refused here.  ``color_fix``: as in the DDPM wrapper's ``tiled_sample`` - the final image of every image of the batch
-        colour-corrected against its condition, trajectories raw."""
+        colour-corrected against its condition, trajectories raw.  ``reference`` / ``crop_border``: as there too - the ground
+        truth of every image of the batch; the return value gains a trailing list of metric dicts."""
         color_fix = check_mode(color_fix)
+        if reference is not None and not isinstance(condition_x, (list, tuple)):
+            reference = _packed_reference(reference, condition_x, crop_border, self)
         n = self.num_sample_steps if num_sample_steps is None else num_sample_steps
         if isinstance(condition_x, (list, tuple)):
             raise NotImplementedError("mixed-size lock-step (a list condition_x) is built for the DDPM sampler only; "
@@ -1019,9 +1056,12 @@ class ConditionalElucidatedDiffusionSR(nn.Module):
         eng.sampler_end(img, out)
         if color_fix is not None:
             color_fix_flat(out, cond01, [b * 3 * h * w for b in range(batch)], [(h, w)] * batch, color_fix)
-        if with_images:
-            return (out, image_list, x0_image_list) if with_x0_images else (out, image_list)
-        return out
+        ret = ((out, image_list, x0_image_list) if with_x0_images else (out, image_list)) if with_images else out
+        if reference is not None:           # of the image as saved: after the colour fix
+            quality = metrics_flat(out.view(-1), reference[0], [b * 3 * h * w for b in range(batch)], reference[1], [(h, w)] * batch,
+                                   crop_border)
+            return ret + (quality,) if with_images else (out, quality)
+        return ret
 
     def _dpmpp_tables(self, n: int, clamp: bool):
         """Per-step scalars of ``sample_using_dpmpp`` (model.py:2513-2541), evaluated with the reference's fp32 tensor ops:
