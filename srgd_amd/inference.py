@@ -25,6 +25,7 @@ from PIL import Image
 
 from .colorfix import color_fix_on_device  # noqa: F401  (public: srgd_amd.inference.color_fix_on_device)
 from .config import load_config
+from .ensemble import ensemble_on_device  # noqa: F401  (public: srgd_amd.inference.ensemble_on_device)
 from .metrics import KEYS as METRIC_KEYS
 from .metrics import metrics_on_device  # noqa: F401  (public: srgd_amd.inference.metrics_on_device)
 from .model import ConditionalElucidatedDiffusionSR, get_model
@@ -87,7 +88,14 @@ def parse_args(argv=None):
     p.add_argument("--crop_border", type=int, default=4, metavar="N",
                    help="pixels cut from every side of output and reference before the --reference_dir numbers are taken (default 4, "
                         "the scale factor, as the x4 super-resolution literature does)")
+    p.add_argument("--ensemble", action="store_true",
+                   help="with --samples K >= 2: write the mean image of every input's K samples to <name>_out_mean.png and their "
+                        "per-pixel spread (twice the standard deviation, 8-bit) to <name>_out_std.png, both computed on the GPU from the "
+                        "samples as saved, and the spread statistics to OUTPUT_DIR/ensemble.json; with --reference_dir the mean "
+                        "image's PSNR / SSIM join metrics.json (engine extension)")
     args = p.parse_args(argv)
+    if args.ensemble and not 2 <= args.samples <= 256:
+        raise SystemExit(f"--ensemble: needs --samples K with 2 <= K <= 256, got K = {args.samples}")
     if args.crop_border < 0:
         raise SystemExit(f"--crop_border: N must be >= 0, got {args.crop_border}")
     if args.samples < 1:
@@ -211,10 +219,11 @@ def _json_record(record):
     return {k: (v if math.isfinite(v) else ("nan" if math.isnan(v) else ("inf" if v > 0 else "-inf"))) for k, v in record.items()}
 
 
-def metrics_document(file_records, samples, crop_border):
+def metrics_document(file_records, samples, crop_border, ensemble=None):
     """``metrics.json``: ``file_records`` = ``[(input file name, written file name, metric dict)]`` in run order ->
     ``{"crop_border", "files": {written file: record}, "images": {input file: mean over its samples} (with --samples only),
-    "mean": mean over the images}``."""
+    "mean": mean over the images}``.  ``ensemble`` (``--ensemble``): ``[(input file name, metric dict of its mean image)]`` adds
+    ``"ensemble": {input file: record}`` and ``"ensemble_mean"``, the mean over those; None or empty adds nothing."""
     per_image = {}
     for name, _, rec in file_records:
         per_image.setdefault(name, []).append(rec)
@@ -223,7 +232,29 @@ def metrics_document(file_records, samples, crop_border):
     if samples > 1:
         doc["images"] = {name: _json_record(rec) for name, rec in image_means.items()}
     doc["mean"] = _json_record(mean_record(list(image_means.values())))
+    if ensemble:
+        doc["ensemble"] = {name: _json_record(rec) for name, rec in ensemble}
+        doc["ensemble_mean"] = _json_record(mean_record([rec for _, rec in ensemble]))
     return doc
+
+
+def ensemble_output_names(file_name):
+    """``--ensemble``: the two file names of an input file's ensemble, ``<name>_out_mean.png`` and ``<name>_out_std.png``."""
+    base = os.path.basename(file_name)
+    return base.replace(".png", "_out_mean.png"), base.replace(".png", "_out_std.png")
+
+
+def ensemble_document(records, samples):
+    """``ensemble.json``: ``records`` = ``[(input file name, mean file name, std file name, {"mean_std", "max_std"})]`` in run order
+    -> ``{"samples": K, "files": {input file: {"mean", "std", "mean_std", "max_std"}}, "mean_std": mean over the files}`` (the
+    statistics in 8-bit units)."""
+    files = {name: {"mean": mean, "std": std, "mean_std": st["mean_std"], "max_std": st["max_std"]} for name, mean, std, st in records}
+    return {"samples": samples, "files": files, "mean_std": sum(st["mean_std"] for *_, st in records) / len(records)}
+
+
+def pil_to_u8_tensor(image):
+    """A PIL image as the uint8 ``[H,W,3]`` tensor it is saved as."""
+    return torch.from_numpy(np.asarray(image.convert("RGB"), dtype=np.uint8).copy())
 
 
 def sample_output_name(file_name, k):
@@ -426,8 +457,17 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
                            guidance_start_steps=0, class_cond_scale=1.0, class_guidance_start_steps=0,
                            generation_start_steps=0, num_sample_steps=250, start_index=0, end_index=None,
                            enable_amp=False, interpolation="bicubic", seed=71, lockstep=1, lockstep_tiles=None, labels=None,
-                           samples=1, color_fix=None, reference_dir=None, crop_border=4, metrics_name="metrics.json"):
-    """``reference_dir`` (``--reference_dir``): every input's ground truth ``reference_dir/<same name>`` is checked first (present,
+                           samples=1, color_fix=None, reference_dir=None, crop_border=4, metrics_name="metrics.json", ensemble=False,
+                           ensemble_name="ensemble.json"):
+    """``ensemble`` (``--ensemble``, ``samples`` >= 2): once the last sample of an input file has been handled and all its ``samples``
+    sample files exist - written by this run or found on disk by the skip-if-exists rule - the file's mean image and spread map
+    (srgd_amd.ensemble) are written to ``<name>_out_mean.png`` / ``<name>_out_std.png``; the files completed by one ``flush()`` go
+    through one batched ``ensemble_on_device`` call.  Samples of this run are taken from the PIL images the ``sr_target_image*``
+    functions return, samples found on disk are decoded on the writer pool, so a resumed run writes the same two files as an
+    uninterrupted one.  A file whose samples, mean and spread all exist is skipped; a sample on disk of another size than x``scale``
+    of the input is reported and that file's ensemble is left out.  The statistics of the files handled go to
+    ``output_dir/ensemble_name`` (``ensemble_document``) and, with ``reference_dir``, the mean images' PSNR / SSIM to ``metrics_name``.
+    ``reference_dir`` (``--reference_dir``): every input's ground truth ``reference_dir/<same name>`` is checked first (present,
     exactly ``scale`` times the input: ``check_references``), decoded on the writer pool while earlier groups sample, and handed to
     the group's ``sr_target_image*`` call; the numbers of every file written go to ``output_dir/metrics_name``
     (``metrics_document``).  Without it nothing is checked, decoded or written.
@@ -455,6 +495,19 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
     from concurrent.futures import ThreadPoolExecutor
     pending, saves = [], []                              # (image, save_path, label, noise seed, reference) of the current lock-step group; PNG writers
     file_records = []                                    # (input file name, written file name, metric dict) of --reference_dir
+    if ensemble and not 2 <= samples <= 256:
+        raise ValueError("ensemble: samples must be in 2..256")
+    ens_open = {}                                        # --ensemble: input file -> [its K samples (PIL image of this run) or None (on disk)], samples still to draw
+    ens_ready, ens_records, ens_quality = [], [], []     # files whose last sample is handled; ensemble.json rows; metrics.json rows
+    if ensemble:
+        for filename in file_names:
+            paths = [os.path.join(output_dir, sample_output_name(filename, k)) for k in range(samples)]
+            missing = sum(not os.path.exists(p) for p in paths)
+            if missing == 0 and all(os.path.exists(os.path.join(output_dir, n)) for n in ensemble_output_names(filename)):
+                continue                                 # samples, mean and spread exist: nothing to do for this file
+            if missing == 0:
+                ens_ready.append(filename)               # every sample is on disk: only the two ensemble files are missing
+            ens_open[filename] = [[None] * samples, missing]
 
     with ThreadPoolExecutor(max_workers=2) as pool:      # PNG encoding overlaps the next group's sampling
         def flush():
@@ -486,7 +539,59 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
                 file_records.extend((e[5], os.path.basename(e[1]), q) for e, q in zip(pending, quality))
             for e, sr in zip(pending, outs):
                 saves.append(pool.submit(sr.save, e[1]))
+                if e[6] in ens_open:                     # --ensemble: sample e[3] - seed of the file has been drawn
+                    state = ens_open[e[6]]
+                    state[0][e[3] - seed] = sr
+                    state[1] -= 1
+                    if state[1] == 0:
+                        ens_ready.append(e[6])
             pending.clear()
+            if ensemble:
+                flush_ensembles()
+
+        def flush_ensembles():
+            """One batched ensemble call for the files completed since the last one."""
+            todo = []                                    # (file name, futures / tensors of its K samples)
+            for filename in ens_ready:
+                drawn = ens_open.pop(filename)[0]
+                todo.append((filename, [pool.submit(load_reference, os.path.join(output_dir, sample_output_name(filename, k)))
+                                        if sr is None else pil_to_u8_tensor(sr) for k, sr in enumerate(drawn)]))
+            ens_ready.clear()
+            names, stacks = [], []
+            for filename, parts in todo:
+                try:
+                    with Image.open(filename) as im:     # the header only
+                        want = (im.size[1] * scale, im.size[0] * scale, 3)
+                except (IOError, SyntaxError):
+                    continue                             # not an image: the sampling loop has reported it
+                try:
+                    parts = [part if torch.is_tensor(part) else part.result() for part in parts]
+                except (IOError, SyntaxError) as err:
+                    print(f"ensemble: a sample of {os.path.basename(filename)} cannot be read ({err}): no ensemble for this file")
+                    continue
+                wrong = [k for k, part in enumerate(parts) if tuple(part.shape) != want]
+                if wrong:
+                    for k in wrong:
+                        print(f"ensemble: {sample_output_name(filename, k)} is {parts[k].shape[1]}x{parts[k].shape[0]}, x{scale} of the "
+                              f"input is {want[1]}x{want[0]}: no ensemble for {os.path.basename(filename)}")
+                    continue
+                names.append(filename)
+                stacks.append(torch.stack(parts))
+            if not names:
+                return
+            device = getattr(sr_model, "device", None)
+            if device is not None:
+                stacks = [st.to(device) for st in stacks]
+            results = ensemble_on_device(stacks, return_mean01=reference_dir is not None)
+            if reference_dir is not None:
+                refs = [pool.submit(load_reference, os.path.join(reference_dir, os.path.basename(f))) for f in names]
+                quality = metrics_on_device([r[3] for r in results], [f.result() for f in refs], crop_border)
+                ens_quality.extend((os.path.basename(f), q) for f, q in zip(names, quality))
+            for filename, res in zip(names, results):
+                mean_name, std_name = ensemble_output_names(filename)
+                for arr, out_name in ((res[0], mean_name), (res[1], std_name)):
+                    saves.append(pool.submit(Image.fromarray(arr.cpu().numpy(), "RGB").save, os.path.join(output_dir, out_name)))
+                ens_records.append((os.path.basename(filename), mean_name, std_name, res[2]))
 
         opened = (None, None, None)                      # the K samples of a file share one decoded image and one reference
         for filename, save_path, noise_seed in plan_sample_entries(file_names, output_dir, samples, seed):
@@ -506,19 +611,26 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
                 hr = [(h * scale, w * scale) for (w, h) in [e[0].size for e in pending] + [image.size]]
                 if len(plan_lockstep_groups(hr, lockstep_tiles)) > 1:      # the image would push the group over the budget
                     flush()
-                pending.append((image, save_path, label, noise_seed, ref, os.path.basename(filename)))
+                pending.append((image, save_path, label, noise_seed, ref, os.path.basename(filename), filename))
                 continue
             if pending and (len(pending) >= max(1, lockstep) or pending[0][0].size != image.size):
                 flush()
-            pending.append((image, save_path, label, noise_seed, ref, os.path.basename(filename)))
+            pending.append((image, save_path, label, noise_seed, ref, os.path.basename(filename), filename))
             if len(pending) >= max(1, lockstep):
                 flush()
         flush()
+        if ensemble:
+            flush_ensembles()
         for f in saves:
             f.result()                                   # surface write errors
     if file_records:                                     # --reference_dir, and at least one file was sampled in this run
         with open(os.path.join(output_dir, metrics_name), "w") as f:
-            json.dump(metrics_document(file_records, samples, crop_border), f, indent=1)
+            json.dump(metrics_document(file_records, samples, crop_border, **({"ensemble": ens_quality} if ens_quality else {})), f,
+                      indent=1)
+            f.write("\n")
+    if ens_records:                                      # --ensemble, and at least one file's ensemble was taken in this run
+        with open(os.path.join(output_dir, ensemble_name), "w") as f:
+            json.dump(ensemble_document(ens_records, samples), f, indent=1)
             f.write("\n")
 
 
@@ -587,7 +699,8 @@ def main(argv=None):
                            end_index=args.end_index, enable_amp=args.amp, interpolation=args.interpolation,
                            seed=args.seed, lockstep=args.lockstep, lockstep_tiles=args.lockstep_tiles, labels=args.labels,
                            samples=args.samples, color_fix=args.color_fix, reference_dir=args.reference_dir,
-                           crop_border=args.crop_border, metrics_name="metrics.json" if world == 1 else f"metrics_rank{rank}.json")
+                           crop_border=args.crop_border, metrics_name="metrics.json" if world == 1 else f"metrics_rank{rank}.json",
+                           ensemble=args.ensemble, ensemble_name="ensemble.json" if world == 1 else f"ensemble_rank{rank}.json")
 
 
 if __name__ == "__main__":
