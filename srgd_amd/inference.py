@@ -25,6 +25,9 @@ from PIL import Image
 
 from .colorfix import color_fix_on_device  # noqa: F401  (public: srgd_amd.inference.color_fix_on_device)
 from .config import load_config
+from .consistency import KEYS as CONSISTENCY_KEYS
+from .consistency import MIN_SIDE as CONSISTENCY_MIN_SIDE
+from .consistency import consistency_on_device  # noqa: F401  (public: srgd_amd.inference.consistency_on_device)
 from .ensemble import ensemble_on_device  # noqa: F401  (public: srgd_amd.inference.ensemble_on_device)
 from .metrics import KEYS as METRIC_KEYS
 from .metrics import metrics_on_device  # noqa: F401  (public: srgd_amd.inference.metrics_on_device)
@@ -93,6 +96,12 @@ def parse_args(argv=None):
                         "per-pixel spread (twice the standard deviation, 8-bit) to <name>_out_std.png, both computed on the GPU from the "
                         "samples as saved, and the spread statistics to OUTPUT_DIR/ensemble.json; with --reference_dir the mean "
                         "image's PSNR / SSIM join metrics.json (engine extension)")
+    p.add_argument("--consistency", action="store_true",
+                   help="LR consistency of every written file: the output as saved (after --color_fix) is reduced x4 on the GPU with the "
+                        "operator that made the condition (Pillow's bicubic) and compared with its own input - no ground truth "
+                        "needed.  LR-PSNR, LR-MSE and the largest 8-bit error go to OUTPUT_DIR/consistency.json with per-image means "
+                        "over --samples and a mean over all images; with --ensemble the mean images are measured too (engine "
+                        "extension)")
     args = p.parse_args(argv)
     if args.ensemble and not 2 <= args.samples <= 256:
         raise SystemExit(f"--ensemble: needs --samples K with 2 <= K <= 256, got K = {args.samples}")
@@ -235,6 +244,27 @@ def metrics_document(file_records, samples, crop_border, ensemble=None):
     if ensemble:
         doc["ensemble"] = {name: _json_record(rec) for name, rec in ensemble}
         doc["ensemble_mean"] = _json_record(mean_record([rec for _, rec in ensemble]))
+    return doc
+
+
+def consistency_document(file_records, samples, ensemble=None):
+    """``consistency.json``: ``file_records`` = ``[(input file name, written file name, {"lr_psnr", "lr_mse", "lr_max_abs"})]`` in run
+    order -> ``{"files": {written file: record}, "images": {input file: mean over its samples} (with --samples only), "mean": mean
+    over the images}``; PSNR is averaged in dB as in ``metrics.json``.  ``ensemble`` (``--ensemble``): ``[(input file name, record of
+    its mean image)]`` adds ``"ensemble": {input file: record}`` and ``"ensemble_mean"``, the mean over those; None or empty adds
+    nothing.  Non-finite values are written as strings (``_json_record``)."""
+    mean = lambda recs: {k: sum(r[k] for r in recs) / len(recs) for k in CONSISTENCY_KEYS}       # noqa: E731
+    per_image = {}
+    for name, _, rec in file_records:
+        per_image.setdefault(name, []).append(rec)
+    image_means = {name: mean(recs) for name, recs in per_image.items()}
+    doc = {"files": {written: _json_record(rec) for _, written, rec in file_records}}
+    if samples > 1:
+        doc["images"] = {name: _json_record(rec) for name, rec in image_means.items()}
+    doc["mean"] = _json_record(mean(list(image_means.values())))
+    if ensemble:
+        doc["ensemble"] = {name: _json_record(rec) for name, rec in ensemble}
+        doc["ensemble_mean"] = _json_record(mean([rec for _, rec in ensemble]))
     return doc
 
 
@@ -458,8 +488,13 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
                            generation_start_steps=0, num_sample_steps=250, start_index=0, end_index=None,
                            enable_amp=False, interpolation="bicubic", seed=71, lockstep=1, lockstep_tiles=None, labels=None,
                            samples=1, color_fix=None, reference_dir=None, crop_border=4, metrics_name="metrics.json", ensemble=False,
-                           ensemble_name="ensemble.json"):
-    """``ensemble`` (``--ensemble``, ``samples`` >= 2): once the last sample of an input file has been handled and all its ``samples``
+                           ensemble_name="ensemble.json", consistency=False, consistency_name="consistency.json"):
+    """``consistency`` (``--consistency``): after a group is sampled, the images it returned - as saved - and the inputs it was given
+    go through one ``consistency_on_device`` call per ``flush()`` (srgd_amd.consistency: the output reduced x4 by Pillow's bicubic
+    against its input); with ``ensemble`` the mean image of every completed file is measured the same way.  An input smaller than 5
+    pixels on a side is reported and left out.  The numbers of the files written go to ``output_dir/consistency_name``
+    (``consistency_document``) when at least one file was sampled in this run.  Without it nothing is computed or written.
+    ``ensemble`` (``--ensemble``, ``samples`` >= 2): once the last sample of an input file has been handled and all its ``samples``
     sample files exist - written by this run or found on disk by the skip-if-exists rule - the file's mean image and spread map
     (srgd_amd.ensemble) are written to ``<name>_out_mean.png`` / ``<name>_out_std.png``; the files completed by one ``flush()`` go
     through one batched ``ensemble_on_device`` call.  Samples of this run are taken from the PIL images the ``sr_target_image*``
@@ -499,6 +534,28 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
         raise ValueError("ensemble: samples must be in 2..256")
     ens_open = {}                                        # --ensemble: input file -> [its K samples (PIL image of this run) or None (on disk)], samples still to draw
     ens_ready, ens_records, ens_quality = [], [], []     # files whose last sample is handled; ensemble.json rows; metrics.json rows
+    cons_records, cons_ensemble = [], []                 # --consistency: consistency.json rows of the files written; of the mean images
+
+    def measure_consistency(names, outputs, inputs):
+        """One batched ``consistency_on_device`` call: ``outputs`` uint8 [4h,4w,3] tensors, ``inputs`` the PIL inputs ->
+        ``[(name, record)]`` of the images large enough."""
+        keep = []
+        for i, im in enumerate(inputs):
+            if min(im.size) < CONSISTENCY_MIN_SIDE:
+                print(f"consistency: {names[i]} is {im.size[0]}x{im.size[1]}, smaller than {CONSISTENCY_MIN_SIDE} pixels on a side: "
+                      "left out")
+            else:
+                keep.append(i)
+        if not keep:
+            return []
+        device = getattr(sr_model, "device", None)
+        place = (lambda t: t.to(device)) if device is not None else (lambda t: t)        # noqa: E731
+        lows = {}                                        # the K samples of a file share one upload of the input
+        for i in keep:
+            if id(inputs[i]) not in lows:
+                lows[id(inputs[i])] = place(pil_to_u8_tensor(inputs[i]))
+        recs = consistency_on_device([place(outputs[i]) for i in keep], [lows[id(inputs[i])] for i in keep])
+        return [(names[i], rec) for i, rec in zip(keep, recs)]
     if ensemble:
         for filename in file_names:
             paths = [os.path.join(output_dir, sample_output_name(filename, k)) for k in range(samples)]
@@ -537,6 +594,11 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
             if ref_kw:
                 outs, quality = outs
                 file_records.extend((e[5], os.path.basename(e[1]), q) for e, q in zip(pending, quality))
+            if consistency:                              # the images as saved against the inputs the group was given
+                written = [os.path.basename(e[1]) for e in pending]
+                source = dict(zip(written, (e[5] for e in pending)))
+                cons_records.extend((source[name], name, rec) for name, rec in
+                                    measure_consistency(written, [pil_to_u8_tensor(sr) for sr in outs], group_images))
             for e, sr in zip(pending, outs):
                 saves.append(pool.submit(sr.save, e[1]))
                 if e[6] in ens_open:                     # --ensemble: sample e[3] - seed of the file has been drawn
@@ -587,6 +649,11 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
                 refs = [pool.submit(load_reference, os.path.join(reference_dir, os.path.basename(f))) for f in names]
                 quality = metrics_on_device([r[3] for r in results], [f.result() for f in refs], crop_border)
                 ens_quality.extend((os.path.basename(f), q) for f, q in zip(names, quality))
+            if consistency:                              # the uint8 mean images against their inputs
+                lows = [try_open_image(f) for f in names]
+                have = [i for i, im in enumerate(lows) if im is not None]
+                cons_ensemble.extend(measure_consistency([os.path.basename(names[i]) for i in have], [results[i][0] for i in have],
+                                                         [lows[i] for i in have]))
             for filename, res in zip(names, results):
                 mean_name, std_name = ensemble_output_names(filename)
                 for arr, out_name in ((res[0], mean_name), (res[1], std_name)):
@@ -627,6 +694,10 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
         with open(os.path.join(output_dir, metrics_name), "w") as f:
             json.dump(metrics_document(file_records, samples, crop_border, **({"ensemble": ens_quality} if ens_quality else {})), f,
                       indent=1)
+            f.write("\n")
+    if cons_records:                                     # --consistency, and at least one file was sampled in this run
+        with open(os.path.join(output_dir, consistency_name), "w") as f:
+            json.dump(consistency_document(cons_records, samples, **({"ensemble": cons_ensemble} if cons_ensemble else {})), f, indent=1)
             f.write("\n")
     if ens_records:                                      # --ensemble, and at least one file's ensemble was taken in this run
         with open(os.path.join(output_dir, ensemble_name), "w") as f:
@@ -700,7 +771,9 @@ def main(argv=None):
                            seed=args.seed, lockstep=args.lockstep, lockstep_tiles=args.lockstep_tiles, labels=args.labels,
                            samples=args.samples, color_fix=args.color_fix, reference_dir=args.reference_dir,
                            crop_border=args.crop_border, metrics_name="metrics.json" if world == 1 else f"metrics_rank{rank}.json",
-                           ensemble=args.ensemble, ensemble_name="ensemble.json" if world == 1 else f"ensemble_rank{rank}.json")
+                           ensemble=args.ensemble, ensemble_name="ensemble.json" if world == 1 else f"ensemble_rank{rank}.json",
+                           consistency=args.consistency,
+                           consistency_name="consistency.json" if world == 1 else f"consistency_rank{rank}.json")
 
 
 if __name__ == "__main__":
