@@ -80,7 +80,8 @@ int srgd_k_conv3x3_mxfp8(const void* in0, const void* in1, int C0, int C1, int B
 /* GroupNorm (from the conv's partial statistics) -> x*(scale+1)+shift -> SiLU (+ residual).
  * replaces: Block.forward after the conv (model.py:250-259) and the ResnetBlock residual add (:285).
  * gamma, beta: device [C]; scale_shift: device [B][2C] (scale | shift) or NULL; in place if y == x.
- * gn_partial: [B][groups][nslots][2] as written by the conv (nslots from srgd_k_conv2d_timed / srgd_k_conv3x3_mxfp8). */
+ * gn_partial: [B][groups][nslots][2] as written by the conv (nslots from srgd_k_conv2d_timed / srgd_k_conv3x3_mxfp8).
+ * x must be that conv's output: with fp32 tensors, a group whose mean^2 exceeds 32 * (var + eps) takes its variance from x itself. */
 int srgd_k_groupnorm_silu(const void* x, void* y, const void* residual, const float* gn_partial, int B, int hw,
                           int C, int groups, const float* gamma, const float* beta, const float* scale_shift,
                           int nslots, int is_bf16, void* stream);

@@ -889,6 +889,7 @@ int run_gn(Ctx& x, const float* gamma, const float* beta, int C, int hw, int ss_
   f.ss_table = ss_offset >= 0 ? x.table : nullptr; f.ss_rows = x.rows; f.step_ptr = x.step_ptr; f.step_mul = x.step_mul;
   f.ss_stride = e->ss_stride; f.ss_offset = ss_offset < 0 ? 0 : ss_offset; f.eps = 1e-5f;
   f.coefA = e->coefA; f.coefB = e->coefB;
+  f.x = buf; f.x_is_bf16 = e->bf16;                // buf holds the producing convolution's output until gn_apply / the consumer runs
   SRGD_TRY(gn_finalize(f, x.st));
   if (finalize_only) return 0;                     // the consumer conv applies y = silu(A x + B) while staging
   QTensor tw;

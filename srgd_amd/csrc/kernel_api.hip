@@ -187,6 +187,7 @@ int srgd_k_groupnorm_silu(const void* x, void* y, const void* residual, const fl
   f.partial = gn_partial; f.nslots = nslots; f.B = B; f.C = C; f.groups = groups; f.hw = hw;
   f.gamma = gamma; f.beta = beta; f.ss_table = scale_shift; f.ss_rows = (const int*)rows.p; f.step_ptr = nullptr;
   f.step_mul = 0; f.ss_stride = 2 * C; f.ss_offset = 0; f.eps = 1e-5f; f.coefA = (float*)cA.p; f.coefB = (float*)cB.p;
+  f.x = x; f.x_is_bf16 = is_bf16 != 0;
   SRGD_TRY(gn_finalize(f, st));
   SRGD_TRY(gn_apply_silu(x, y, residual, (const float*)cA.p, (const float*)cB.p, B, hw, C, is_bf16 != 0, st));
   SRGD_HIP(hipStreamSynchronize(st));

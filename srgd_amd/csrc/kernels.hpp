@@ -177,6 +177,11 @@ struct GnFinalizeArgs {
   float eps;
   float* coefA;           // [B][C]   y = silu(coefA * x + coefB)
   float* coefB;
+  // The tensor the partial sums were taken of ([B][hw][C], the producing convolution's stored output) and its type.  With an fp32
+  // tensor, a (sample, group) whose mean^2 exceeds GN_RECOMPUTE_RATIO * (var + eps) takes its variance from a second pass over
+  // these values (norm_act.hip).  Null or bf16: the accumulator sums only.
+  const void* x = nullptr;
+  bool x_is_bf16 = false;
 };
 int gn_finalize(const GnFinalizeArgs& a, hipStream_t st);
 // out_q / out_s (nullable, bf16 only): MX-fp8 twin of y written alongside (see ConvArgs::out_q)

@@ -17,28 +17,88 @@ template <typename V> __device__ __forceinline__ void st_stream(V* p, const V& x
   __builtin_nontemporal_store(x.v, &p->v);
 }
 
-// One wave per (sample, group): sums the per-tile partials the conv epilogue wrote (fixed
+// One block per (sample, group); its first wave sums the per-tile partials the conv epilogue wrote (fixed
 // order, fp64) and folds GroupNorm's affine and the ResnetBlock's (scale+1, shift)
 // (reference model.py:250-257) into per-(sample, channel) coefficients y = A*x + B.
-__global__ __launch_bounds__(64) void gn_finalize_kernel(GnFinalizeArgs a) {
+//
+// LARGE GROUP MEANS.  The slots hold fp32 sums: a slot's sum of y^2 is rounded at the size of n_slot * (mean^2 + var), so
+// var = s2/n - mean^2 carries an absolute error of about u * mean^2 whatever the precision of the additions here (u = 2^-24 = 6e-8;
+// an emulation of the epilogues' summation gives 2e-8 ... 6e-8 * mean^2).  Relative to var + eps that is u * r with
+// r = mean^2 / (var + eps); rstd moves by half of it, a normalised value |z| <= 4 by 2 * u * r.  The fp32 GroupNorm of the reference
+// rounds a normalised value to about 2e-6 ... 4e-6 (a few ulp of z and of mean * rstd), so the accumulator statistics stay inside
+// the reference's own rounding while 2 * u * r <= 4e-6: r <= 32 (GN_RECOMPUTE_RATIO).  Beyond it the block reads the group's
+// stored values (fp32 tensors only: NHWC, the group's channels contiguous per pixel) and takes var = sum (x - mean)^2 / n in fp64:
+// a fixed walk (thread t takes the vectors t, t + T, ...; T depends on hw and C / groups alone), a butterfly per wave, the waves
+// in index order - the same bits for a sample whatever else is in the batch.  The branch is taken on device data, so a captured
+// graph holds both sides.  Groups with r <= 32 - every group of a network whose biases are near zero - get the bits of the
+// accumulator path unchanged.  bf16 tensors keep the accumulator statistics: their stored values are rounded to 2^-9, coarser
+// than the spread of a group with a large r, while the fp32 accumulators are not.
+constexpr double GN_RECOMPUTE_RATIO = 32.0;
+constexpr int GN_WIDE_ELEMS = 16384;      // hw * C / groups from which the launch has 256 threads per (sample, group) instead of 64
+
+__global__ __launch_bounds__(256) void gn_finalize_kernel(GnFinalizeArgs a) {
+  __shared__ double sh_mean, sh_part[4];
+  __shared__ int sh_redo;
   const int b = blockIdx.x / a.groups, g = blockIdx.x - b * a.groups;
-  const int lane = threadIdx.x;
-  const float* p = a.partial + (size_t)(b * a.groups + g) * a.nslots * 2;
-  double s1 = 0.0, s2 = 0.0;
-  for (int i = lane; i < a.nslots; i += 64) {
-    s1 += (double)p[2 * i];
-    s2 += (double)p[2 * i + 1];
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    s1 += __shfl_xor(s1, o, 64);
-    s2 += __shfl_xor(s2, o, 64);
-  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int cpg = a.C / a.groups;
   const double n = (double)a.hw * (double)cpg;
-  const double mean = s1 / n;
-  double var = s2 / n - mean * mean;
-  if (var < 0.0) var = 0.0;
+  double mean = 0.0, var = 0.0;
+  if (wave == 0) {
+    const float* p = a.partial + (size_t)(b * a.groups + g) * a.nslots * 2;
+    double s1 = 0.0, s2 = 0.0;
+    for (int i = lane; i < a.nslots; i += 64) {
+      s1 += (double)p[2 * i];
+      s2 += (double)p[2 * i + 1];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      s1 += __shfl_xor(s1, o, 64);
+      s2 += __shfl_xor(s2, o, 64);
+    }
+    mean = s1 / n;
+    var = s2 / n - mean * mean;
+    if (var < 0.0) var = 0.0;
+  }
+  if (a.x && !a.x_is_bf16) {                           // (uniform over the launch)
+    if (threadIdx.x == 0) {
+      sh_mean = mean;
+      sh_redo = mean * mean > GN_RECOMPUTE_RATIO * (var + (double)a.eps);      // false for a NaN: it stays visible
+    }
+    __syncthreads();
+    if (sh_redo) {                                     // (uniform over the block)
+      const double m = sh_mean;
+      const float* xg = (const float*)a.x + (size_t)b * a.hw * a.C + (size_t)g * cpg;
+      double acc = 0.0;
+      if ((cpg & 3) == 0) {                            // C % 4 == 0 (gn_apply's rule): 16-byte vectors
+        const int vpg = cpg >> 2, nv = a.hw * vpg;     // nv < 2^31 (gn_apply's check)
+        for (int v = threadIdx.x; v < nv; v += blockDim.x) {
+          const int px = v / vpg, j = v - px * vpg;
+          const f32x4 t = *reinterpret_cast<const f32x4*>(xg + (size_t)px * a.C + 4 * j);
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            const double d = (double)t[k] - m;
+            acc += d * d;
+          }
+        }
+      } else {
+        const int ne = a.hw * cpg;
+        for (int e = threadIdx.x; e < ne; e += blockDim.x) {
+          const int px = e / cpg, j = e - px * cpg;
+          const double d = (double)xg[(size_t)px * a.C + j] - m;
+          acc += d * d;
+        }
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+      if (lane == 0) sh_part[wave] = acc;
+      __syncthreads();
+      acc = 0.0;
+      for (int w = 0; w < (int)(blockDim.x >> 6); ++w) acc += sh_part[w];
+      var = acc / n;
+    }
+    if (wave != 0) return;
+  }
   const float rstd = (float)(1.0 / sqrt(var + (double)a.eps));
   const float fmean = (float)mean;
   const float* ss = nullptr;
@@ -178,7 +238,12 @@ __global__ __launch_bounds__(256) void rms_norm_kernel(const T* __restrict__ x, 
 
 int gn_finalize(const GnFinalizeArgs& a, hipStream_t st) {
   if (a.C % a.groups != 0) SRGD_FAIL("gn_finalize: C % groups != 0");
-  hipLaunchKernelGGL(gn_finalize_kernel, dim3(a.B * a.groups), dim3(64), 0, st, a);
+  const long elems = (long)a.hw * (a.C / a.groups);
+  const bool second_pass = a.x && !a.x_is_bf16;
+  if (second_pass && (a.C % 4 != 0 || elems >= (1L << 31))) SRGD_FAIL("gn_finalize: C must be a multiple of 4 and a group smaller than 2^31 elements");
+  // one wave sums the slots; the other three only take part in a group's second pass (a 256 x 256 tile's group is 2^20 values)
+  const int threads = second_pass && elems >= GN_WIDE_ELEMS ? 256 : 64;
+  hipLaunchKernelGGL(gn_finalize_kernel, dim3(a.B * a.groups), dim3(threads), 0, st, a);
   SRGD_HIP(hipGetLastError());
   return 0;
 }
