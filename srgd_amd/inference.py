@@ -23,6 +23,8 @@ import numpy as np
 import torch
 from PIL import Image
 
+from .backproject import MAX_ITERATIONS as BACK_PROJECT_MAX
+from .backproject import back_project_on_device  # noqa: F401  (public: srgd_amd.inference.back_project_on_device)
 from .colorfix import color_fix_on_device  # noqa: F401  (public: srgd_amd.inference.color_fix_on_device)
 from .config import load_config
 from .consistency import KEYS as CONSISTENCY_KEYS
@@ -102,7 +104,15 @@ def parse_args(argv=None):
                         "needed.  LR-PSNR, LR-MSE and the largest 8-bit error go to OUTPUT_DIR/consistency.json with per-image means "
                         "over --samples and a mean over all images; with --ensemble the mean images are measured too (engine "
                         "extension)")
+    p.add_argument("--back_project", type=int, default=0, metavar="N",
+                   help="pull every output back onto its own input on the GPU with N <= 64 steps of iterative back-projection, after "
+                        "--color_fix and before the file is saved: the output is reduced x4 and enlarged x4 again with Pillow's bicubic "
+                        "and the difference between the x4 input and that image is added, in 8 bits (0, the default: off); raises the "
+                        "LR-PSNR --consistency reports; with --samples every sample is corrected against the same input (engine "
+                        "extension)")
     args = p.parse_args(argv)
+    if not 0 <= args.back_project <= BACK_PROJECT_MAX:
+        raise SystemExit(f"--back_project: N must be in 0 .. {BACK_PROJECT_MAX}, got {args.back_project}")
     if args.ensemble and not 2 <= args.samples <= 256:
         raise SystemExit(f"--ensemble: needs --samples K with 2 <= K <= 256, got K = {args.samples}")
     if args.crop_border < 0:
@@ -165,6 +175,11 @@ def _label_tensor(test_label, n_images, device):
 def _color_fix_kw(color_fix):
     """``tiled_sample``'s ``color_fix`` keyword for a set mode; nothing for None / "none" (the call a run without the flag makes)."""
     return {} if color_fix in (None, "none") else {"color_fix": color_fix}
+
+
+def _back_project_kw(back_project):
+    """``tiled_sample``'s ``back_project`` keyword for N > 0; nothing for 0 / None (the call a run without the flag makes)."""
+    return {"back_project": back_project} if back_project else {}
 
 
 def _reference_kw(reference, crop_border):
@@ -356,7 +371,7 @@ def unit_tensor_to_pil_on_device(t: torch.Tensor) -> Image.Image:
 def sr_target_image(image, sr_model, scale=4, batch_size=8, test_label=2, cond_scale=1.0, guidance_start_steps=0,
                     class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0,
                     num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None, reference=None,
-                    crop_border=4):
+                    crop_border=4, back_project=0):
     """``reference`` (engine extension; here and in the three group forms below): the ground truth as a uint8 ``[H,W,3]`` tensor (a
     list of one per image in the group forms).  The return value is then ``(image(s), metric dicts)``: PSNR / SSIM of every image as
     saved, with ``crop_border`` pixels cut from every side (srgd_amd.metrics)."""
@@ -373,7 +388,7 @@ def sr_target_image(image, sr_model, scale=4, batch_size=8, test_label=2, cond_s
                                        class_guidance_start_steps=class_guidance_start_steps,
                                        generation_start_steps=generation_start_steps,
                                        num_sample_steps=num_sample_steps, amp=enable_amp, **_color_fix_kw(color_fix),
-                                       **_reference_kw(reference, crop_border))
+                                       **_reference_kw(reference, crop_border), **_back_project_kw(back_project))
     output, quality = _split_quality(output, reference)
     sr_img = unit_tensor_to_pil_on_device(output[0])
     assert sr_img.size == (width * 4, height * 4)
@@ -383,7 +398,7 @@ def sr_target_image(image, sr_model, scale=4, batch_size=8, test_label=2, cond_s
 def sr_target_images(images, sr_model, scale=4, batch_size=8, test_label=2, cond_scale=1.0, guidance_start_steps=0,
                      class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0,
                      num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None, reference=None,
-                     crop_border=4):
+                     crop_border=4, back_project=0):
     """``sr_target_image`` for several same-sized images in lock-step (engine extension): one ``tiled_sample`` call on a
     ``[B,3,H,W]`` condition.  Each image is sampled exactly as it would be alone after the reference's per-image
     ``seed_everything(seed)`` (inference.py:73) - bit-identical outputs - while their tiles fill the U-Net launches.
@@ -401,7 +416,7 @@ def sr_target_images(images, sr_model, scale=4, batch_size=8, test_label=2, cond
                                        class_guidance_start_steps=class_guidance_start_steps,
                                        generation_start_steps=generation_start_steps,
                                        num_sample_steps=num_sample_steps, amp=enable_amp, **_color_fix_kw(color_fix),
-                                       **_reference_kw(reference, crop_border))
+                                       **_reference_kw(reference, crop_border), **_back_project_kw(back_project))
     output, quality = _split_quality(output, reference)
     outs = [unit_tensor_to_pil_on_device(o) for o in output]
     assert all(o.size == (width * 4, height * 4) for o in outs)
@@ -411,7 +426,7 @@ def sr_target_images(images, sr_model, scale=4, batch_size=8, test_label=2, cond
 def sr_target_images_mixed(images, sr_model, scale=4, batch_size=8, test_label=2, cond_scale=1.0, guidance_start_steps=0,
                            class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0,
                            num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None, reference=None,
-                           crop_border=4):
+                           crop_border=4, back_project=0):
     """``sr_target_image`` for several images of any sizes in lock-step (engine extension): one ``tiled_sample`` call on a list
     of conditions.  Each image comes out bit-identical to its own ``sr_target_image`` run (with its own label where
     ``test_label`` is a sequence of one label per image)."""
@@ -426,7 +441,7 @@ def sr_target_images_mixed(images, sr_model, scale=4, batch_size=8, test_label=2
                                        class_guidance_start_steps=class_guidance_start_steps,
                                        generation_start_steps=generation_start_steps,
                                        num_sample_steps=num_sample_steps, amp=enable_amp, **_color_fix_kw(color_fix),
-                                       **_reference_kw(reference, crop_border))
+                                       **_reference_kw(reference, crop_border), **_back_project_kw(back_project))
     output, quality = _split_quality(output, reference)
     outs = [unit_tensor_to_pil_on_device(o[0]) for o in output]
     assert all(o.size == (im.size[0] * 4, im.size[1] * 4) for o, im in zip(outs, images))
@@ -436,7 +451,7 @@ def sr_target_images_mixed(images, sr_model, scale=4, batch_size=8, test_label=2
 def sr_target_images_seeded(images, seeds, sr_model, scale=4, batch_size=8, test_label=2, cond_scale=1.0, guidance_start_steps=0,
                             class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0,
                             num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None,
-                            reference=None, crop_border=4):
+                            reference=None, crop_border=4, back_project=0):
     """``sr_target_images_mixed`` with one noise seed per image (engine extension, ``tiled_sample(seeds=...)``): image i comes out
     bit-identical to its own ``sr_target_image`` run with ``seed=seeds[i]``; an image may appear several times with different
     seeds (each PIL image is upsampled once).  ``seed`` seeds the process as the other entry points do and is not a noise seed."""
@@ -454,7 +469,7 @@ def sr_target_images_seeded(images, seeds, sr_model, scale=4, batch_size=8, test
                                        class_guidance_start_steps=class_guidance_start_steps,
                                        generation_start_steps=generation_start_steps,
                                        num_sample_steps=num_sample_steps, amp=enable_amp, seeds=list(seeds),
-                                       **_color_fix_kw(color_fix), **_reference_kw(reference, crop_border))
+                                       **_color_fix_kw(color_fix), **_reference_kw(reference, crop_border), **_back_project_kw(back_project))
     output, quality = _split_quality(output, reference)
     outs = [unit_tensor_to_pil_on_device(o[0]) for o in output]
     assert all(o.size == (im.size[0] * 4, im.size[1] * 4) for o, im in zip(outs, images))
@@ -488,8 +503,11 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
                            generation_start_steps=0, num_sample_steps=250, start_index=0, end_index=None,
                            enable_amp=False, interpolation="bicubic", seed=71, lockstep=1, lockstep_tiles=None, labels=None,
                            samples=1, color_fix=None, reference_dir=None, crop_border=4, metrics_name="metrics.json", ensemble=False,
-                           ensemble_name="ensemble.json", consistency=False, consistency_name="consistency.json"):
-    """``consistency`` (``--consistency``): after a group is sampled, the images it returned - as saved - and the inputs it was given
+                           ensemble_name="ensemble.json", consistency=False, consistency_name="consistency.json", back_project=0):
+    """``back_project`` (``--back_project N``): N > 0 is handed by keyword to whichever ``sr_target_image*`` function samples a group
+    (``tiled_sample(back_project=N)``: the image is pulled back onto its input before it is saved, so every number below is taken of
+    the corrected file); with 0 the keyword is not passed at all.
+    ``consistency`` (``--consistency``): after a group is sampled, the images it returned - as saved - and the inputs it was given
     go through one ``consistency_on_device`` call per ``flush()`` (srgd_amd.consistency: the output reduced x4 by Pillow's bicubic
     against its input); with ``ensemble`` the mean image of every completed file is measured the same way.  An input smaller than 5
     pixels on a side is reported and left out.  The numbers of the files written go to ``output_dir/consistency_name``
@@ -523,7 +541,7 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
               guidance_start_steps=guidance_start_steps, class_cond_scale=class_cond_scale,
               class_guidance_start_steps=class_guidance_start_steps, generation_start_steps=generation_start_steps,
               num_sample_steps=num_sample_steps, enable_amp=enable_amp, interpolation=interpolation, seed=seed,
-              color_fix=None if color_fix in (None, "none") else color_fix)
+              color_fix=None if color_fix in (None, "none") else color_fix, **_back_project_kw(back_project))
     file_names = sorted(glob.glob(f"{input_dir}/*"))[start_index:end_index]
     if reference_dir is not None:
         check_references(file_names, reference_dir, scale, crop_border)
@@ -772,7 +790,7 @@ def main(argv=None):
                            samples=args.samples, color_fix=args.color_fix, reference_dir=args.reference_dir,
                            crop_border=args.crop_border, metrics_name="metrics.json" if world == 1 else f"metrics_rank{rank}.json",
                            ensemble=args.ensemble, ensemble_name="ensemble.json" if world == 1 else f"ensemble_rank{rank}.json",
-                           consistency=args.consistency,
+                           consistency=args.consistency, back_project=args.back_project,
                            consistency_name="consistency.json" if world == 1 else f"consistency_rank{rank}.json")
 
 

@@ -23,6 +23,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import SamplerGeometry, StepScalars
+from .backproject import back_project_flat, check_hr_sizes, check_iterations
 from .colorfix import check_mode, color_fix_flat
 from .metrics import check_sizes, metrics_flat, pack_references
 from .engine import HipEngine
@@ -235,6 +236,16 @@ def _packed_reference(reference, condition_x, crop_border, sampler):
     return pack_references(reference, sizes, sampler.device)
 
 
+def _back_project_steps(back_project, condition_x):
+    """``tiled_sample(back_project=N)``: None for 0 / None (nothing is launched), else N with every image of ``condition_x`` (a
+    ``[B,3,H,W]`` tensor or a list of ``[1,3,H_i,W_i]``) checked before any sampling.  ValueError: N outside 0 .. 64, a height or
+    width that is no multiple of 4 or below 20, 3*H*W >= 2^31 - 256."""
+    steps = check_iterations(back_project)
+    if steps is not None:
+        check_hr_sizes([(int(c.shape[-2]), int(c.shape[-1])) for c in condition_x])
+    return steps
+
+
 def _as_tuple(v, n):
     return tuple(v) if isinstance(v, (tuple, list)) else (v,) * n
 
@@ -430,7 +441,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                      cond_scale=1.0, guidance_start_steps=0, class_cond_scale=1.0, class_guidance_start_steps=0,
                      generation_start_steps=0, num_sample_steps=None, with_images=False, with_x0_images=False,
                      start_white_noise=True, amp=False, precision=None, seeds=None, color_fix=None, reference=None,
-                     crop_border=4):
+                     crop_border=4, back_project=0):
         """Tiled CFG-DDPM sampling (reference model.py:3288-3413).
 
         ``amp`` is accepted and ignored exactly as in the reference (which always computes fp32); the engine
@@ -465,8 +476,15 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
         value then gains a trailing list of ``{"psnr_y", "psnr_rgb", "ssim_y"}`` dicts, one per image: Y-channel PSNR, RGB PSNR and
         Y-channel SSIM of the final image as it would be saved (after the colour fix) with ``crop_border`` pixels cut from every
         side, computed on the GPU (srgd_amd.metrics, one batched call and one copy of 4 doubles per image).  Not available on a
-        canvas sharded over ranks."""
+        canvas sharded over ranks.
+
+        ``back_project`` (engine-only keyword, absent upstream): 0 (default: nothing is launched) or the number N <= 64 of
+        back-projection steps - after the colour fix and before the metrics, the final image of every image of the run is pulled
+        back onto its own ``condition_x`` on the GPU (srgd_amd.backproject, one batched call per run) and equals
+        ``back_project_on_device(result without the keyword, condition_x, N)`` bit for bit.  Trajectories stay raw.  The
+        condition's height and width must be multiples of 4 and at least 20: ``ValueError`` before anything is sampled."""
         color_fix = check_mode(color_fix)
+        back_project = _back_project_steps(back_project, condition_x)
         if reference is not None:
             reference = _packed_reference(reference, condition_x, crop_border, self)
         num_sample_steps = self.num_sample_steps if num_sample_steps is None else num_sample_steps
@@ -489,7 +507,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
             outs = self._tiled_sample_images(batch_size, tile_size, list(condition_x), class_label, cond_scale,
                                              guidance_start_steps, class_cond_scale, class_guidance_start_steps,
                                              generation_start_steps, num_sample_steps, start_white_noise, precision, seeds=seeds,
-                                             color_fix=color_fix, reference=reference, crop_border=crop_border)
+                                             color_fix=color_fix, reference=reference, crop_border=crop_border, back_project=back_project)
             if reference is not None:
                 return (outs[0] if as_list else torch.cat(outs[0], 0)), outs[1]
             return outs if as_list else torch.cat(outs, 0)
@@ -506,7 +524,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
             return self._tiled_sample_images(batch_size, tile_size, list(condition_x), class_label, cond_scale,
                                              guidance_start_steps, class_cond_scale, class_guidance_start_steps,
                                              generation_start_steps, num_sample_steps, start_white_noise, precision,
-                                             color_fix=color_fix, reference=reference, crop_border=crop_border)
+                                             color_fix=color_fix, reference=reference, crop_border=crop_border, back_project=back_project)
         if cond_scale != 1.0 and class_cond_scale != 1.0:
             raise NotImplementedError("Currently, you cannot specify both cond_scale and class_cond_scale at the same time.")
         if tile_size != 256 or tile_stride != 256:
@@ -612,6 +630,8 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
         eng.sampler_end(img, out)
         if color_fix is not None:           # in place on the [B,3,H,W] result; the trajectories above stay raw
             color_fix_flat(out, cond01, [b * 3 * h * w for b in range(batch)], [(h, w)] * batch, color_fix)
+        if back_project is not None:        # after the colour fix, in place: the image as it will be saved
+            back_project_flat(out.view(-1), cond01.view(-1), [b * 3 * h * w for b in range(batch)], [(h, w)] * batch, back_project)
         ret = ((out, image_list, x0_image_list) if with_x0_images else (out, image_list)) if with_images else out
         if reference is not None:           # of the image as saved: after the colour fix
             quality = metrics_flat(out.view(-1), reference[0], [b * 3 * h * w for b in range(batch)], reference[1], [(h, w)] * batch,
@@ -621,7 +641,8 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
 
     def _tiled_sample_images(self, batch_size, tile_size, conds, class_label, cond_scale, guidance_start_steps,
                              class_cond_scale, class_guidance_start_steps, generation_start_steps, num_sample_steps,
-                             start_white_noise, precision, seeds=None, color_fix=None, reference=None, crop_border=4):
+                             start_white_noise, precision, seeds=None, color_fix=None, reference=None, crop_border=4,
+                             back_project=None):
         """Mixed-size lock-step (srgd_sampler_begin_images): every image keeps its own canvas, crop box, padding, inner box and
         tile grids; a step's tiles of all images share the U-Net launches.  Noise: the images of one noise class (canvas size)
         see the draw sequence a run of one of them alone sees.  Host noise: the generator state is taken once at entry and
@@ -749,6 +770,8 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
             starts.append(starts[-1] + 3 * p.H * p.W)
         if color_fix is not None:           # on the run's flat buffers: out and cond01 share the per-image layout
             color_fix_flat(out, cond01, starts[:-1], [(p.H, p.W) for p in plans], color_fix)
+        if back_project is not None:        # after the colour fix, in place: the images as they will be saved
+            back_project_flat(out, cond01, starts[:-1], [(p.H, p.W) for p in plans], back_project)
         quality = None
         if reference is not None:           # on the same flat layout, after the colour fix
             quality = metrics_flat(out, reference[0], starts[:-1], reference[1], [(p.H, p.W) for p in plans], crop_border)
@@ -949,13 +972,15 @@ class ConditionalElucidatedDiffusionSR(nn.Module):
                      cond_scale=1.0, guidance_start_steps=0, class_cond_scale=1.0, class_guidance_start_steps=0,
                      generation_start_steps=0, num_sample_steps=None, clamp=True, zero_init=False, with_images=False,
                      with_x0_images=False, start_white_noise=True, amp=False, precision=None, seeds=None, color_fix=None,
-                     reference=None, crop_border=4):
+                     reference=None, crop_border=4, back_project=0):
         """Reference model.py:2309-2475 (``start_white_noise`` and ``amp`` are accepted and unused there too; ``precision``
         is the engine-only override of ``self.precision``).  ``seeds`` (per-image noise seeds) is a DDPM-sampler feature and is
         refused here.  ``color_fix``: as in the DDPM wrapper's ``tiled_sample`` - the final image of every image of the batch
         colour-corrected against its condition, trajectories raw.  ``reference`` / ``crop_border``: as there too - the ground
-        truth of every image of the batch; the return value gains a trailing list of metric dicts."""
+        truth of every image of the batch; the return value gains a trailing list of metric dicts.  ``back_project``: as there
+        too - N back-projection steps on the final image, after the colour fix and before the metrics."""
         color_fix = check_mode(color_fix)
+        back_project = _back_project_steps(back_project, condition_x)
         if reference is not None and not isinstance(condition_x, (list, tuple)):
             reference = _packed_reference(reference, condition_x, crop_border, self)
         n = self.num_sample_steps if num_sample_steps is None else num_sample_steps
@@ -1056,6 +1081,8 @@ class ConditionalElucidatedDiffusionSR(nn.Module):
         eng.sampler_end(img, out)
         if color_fix is not None:
             color_fix_flat(out, cond01, [b * 3 * h * w for b in range(batch)], [(h, w)] * batch, color_fix)
+        if back_project is not None:        # after the colour fix, in place: the image as it will be saved
+            back_project_flat(out.view(-1), cond01.view(-1), [b * 3 * h * w for b in range(batch)], [(h, w)] * batch, back_project)
         ret = ((out, image_list, x0_image_list) if with_x0_images else (out, image_list)) if with_images else out
         if reference is not None:           # of the image as saved: after the colour fix
             quality = metrics_flat(out.view(-1), reference[0], [b * 3 * h * w for b in range(batch)], reference[1], [(h, w)] * batch,
