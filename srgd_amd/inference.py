@@ -31,6 +31,7 @@ from .consistency import KEYS as CONSISTENCY_KEYS
 from .consistency import MIN_SIDE as CONSISTENCY_MIN_SIDE
 from .consistency import consistency_on_device  # noqa: F401  (public: srgd_amd.inference.consistency_on_device)
 from .ensemble import ensemble_on_device  # noqa: F401  (public: srgd_amd.inference.ensemble_on_device)
+from .guidance import MIN_SIDE as GUIDANCE_MIN_SIDE
 from .metrics import KEYS as METRIC_KEYS
 from .metrics import metrics_on_device  # noqa: F401  (public: srgd_amd.inference.metrics_on_device)
 from .model import ConditionalElucidatedDiffusionSR, get_model
@@ -110,7 +111,19 @@ def parse_args(argv=None):
                         "and the difference between the x4 input and that image is added, in 8 bits (0, the default: off); raises the "
                         "LR-PSNR --consistency reports; with --samples every sample is corrected against the same input (engine "
                         "extension)")
+    p.add_argument("--consistency_guidance", type=float, default=0.0, metavar="G",
+                   help="LR-consistency guidance inside the DDPM sampling loop, weight G in [0, 1] (0, the default: off): after every "
+                        "step the predicted clean image is reduced x4 and enlarged x4 again on the GPU with the coefficients of "
+                        "Pillow's bicubic, and G times the difference between the x4 input and that image is added to the prediction "
+                        "and, scaled by the step's weight of the prediction, to the image - the later steps harmonise the correction; "
+                        "raises the LR-PSNR --consistency reports; inputs must be at least 5 pixels on a side (engine extension)")
+    p.add_argument("--consistency_guidance_start_steps", type=int, default=0, metavar="S",
+                   help="with --consistency_guidance: the first guided step (default 0: every step)")
     args = p.parse_args(argv)
+    if not 0.0 <= args.consistency_guidance <= 1.0:         # NaN fails both comparisons
+        raise SystemExit(f"--consistency_guidance: G must be in [0, 1], got {args.consistency_guidance}")
+    if args.consistency_guidance_start_steps < 0:
+        raise SystemExit(f"--consistency_guidance_start_steps: S must be >= 0, got {args.consistency_guidance_start_steps}")
     if not 0 <= args.back_project <= BACK_PROJECT_MAX:
         raise SystemExit(f"--back_project: N must be in 0 .. {BACK_PROJECT_MAX}, got {args.back_project}")
     if args.ensemble and not 2 <= args.samples <= 256:
@@ -180,6 +193,14 @@ def _color_fix_kw(color_fix):
 def _back_project_kw(back_project):
     """``tiled_sample``'s ``back_project`` keyword for N > 0; nothing for 0 / None (the call a run without the flag makes)."""
     return {"back_project": back_project} if back_project else {}
+
+
+def _guidance_kw(consistency_guidance, consistency_guidance_start_steps=0):
+    """``tiled_sample``'s ``consistency_guidance`` keywords for a weight > 0; nothing for 0 / None (the call a run without the flag
+    makes)."""
+    if not consistency_guidance:
+        return {}
+    return {"consistency_guidance": consistency_guidance, "consistency_guidance_start_steps": consistency_guidance_start_steps}
 
 
 def _reference_kw(reference, crop_border):
@@ -371,7 +392,8 @@ def unit_tensor_to_pil_on_device(t: torch.Tensor) -> Image.Image:
 def sr_target_image(image, sr_model, scale=4, batch_size=8, test_label=2, cond_scale=1.0, guidance_start_steps=0,
                     class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0,
                     num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None, reference=None,
-                    crop_border=4, back_project=0):
+                    crop_border=4, back_project=0, consistency_guidance=0.0,
+                    consistency_guidance_start_steps=0):
     """``reference`` (engine extension; here and in the three group forms below): the ground truth as a uint8 ``[H,W,3]`` tensor (a
     list of one per image in the group forms).  The return value is then ``(image(s), metric dicts)``: PSNR / SSIM of every image as
     saved, with ``crop_border`` pixels cut from every side (srgd_amd.metrics)."""
@@ -388,7 +410,8 @@ def sr_target_image(image, sr_model, scale=4, batch_size=8, test_label=2, cond_s
                                        class_guidance_start_steps=class_guidance_start_steps,
                                        generation_start_steps=generation_start_steps,
                                        num_sample_steps=num_sample_steps, amp=enable_amp, **_color_fix_kw(color_fix),
-                                       **_reference_kw(reference, crop_border), **_back_project_kw(back_project))
+                                       **_reference_kw(reference, crop_border), **_back_project_kw(back_project),
+                                       **_guidance_kw(consistency_guidance, consistency_guidance_start_steps))
     output, quality = _split_quality(output, reference)
     sr_img = unit_tensor_to_pil_on_device(output[0])
     assert sr_img.size == (width * 4, height * 4)
@@ -398,7 +421,8 @@ def sr_target_image(image, sr_model, scale=4, batch_size=8, test_label=2, cond_s
 def sr_target_images(images, sr_model, scale=4, batch_size=8, test_label=2, cond_scale=1.0, guidance_start_steps=0,
                      class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0,
                      num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None, reference=None,
-                     crop_border=4, back_project=0):
+                     crop_border=4, back_project=0, consistency_guidance=0.0,
+                     consistency_guidance_start_steps=0):
     """``sr_target_image`` for several same-sized images in lock-step (engine extension): one ``tiled_sample`` call on a
     ``[B,3,H,W]`` condition.  Each image is sampled exactly as it would be alone after the reference's per-image
     ``seed_everything(seed)`` (inference.py:73) - bit-identical outputs - while their tiles fill the U-Net launches.
@@ -416,7 +440,8 @@ def sr_target_images(images, sr_model, scale=4, batch_size=8, test_label=2, cond
                                        class_guidance_start_steps=class_guidance_start_steps,
                                        generation_start_steps=generation_start_steps,
                                        num_sample_steps=num_sample_steps, amp=enable_amp, **_color_fix_kw(color_fix),
-                                       **_reference_kw(reference, crop_border), **_back_project_kw(back_project))
+                                       **_reference_kw(reference, crop_border), **_back_project_kw(back_project),
+                                       **_guidance_kw(consistency_guidance, consistency_guidance_start_steps))
     output, quality = _split_quality(output, reference)
     outs = [unit_tensor_to_pil_on_device(o) for o in output]
     assert all(o.size == (width * 4, height * 4) for o in outs)
@@ -426,7 +451,8 @@ def sr_target_images(images, sr_model, scale=4, batch_size=8, test_label=2, cond
 def sr_target_images_mixed(images, sr_model, scale=4, batch_size=8, test_label=2, cond_scale=1.0, guidance_start_steps=0,
                            class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0,
                            num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None, reference=None,
-                           crop_border=4, back_project=0):
+                           crop_border=4, back_project=0, consistency_guidance=0.0,
+                           consistency_guidance_start_steps=0):
     """``sr_target_image`` for several images of any sizes in lock-step (engine extension): one ``tiled_sample`` call on a list
     of conditions.  Each image comes out bit-identical to its own ``sr_target_image`` run (with its own label where
     ``test_label`` is a sequence of one label per image)."""
@@ -441,7 +467,8 @@ def sr_target_images_mixed(images, sr_model, scale=4, batch_size=8, test_label=2
                                        class_guidance_start_steps=class_guidance_start_steps,
                                        generation_start_steps=generation_start_steps,
                                        num_sample_steps=num_sample_steps, amp=enable_amp, **_color_fix_kw(color_fix),
-                                       **_reference_kw(reference, crop_border), **_back_project_kw(back_project))
+                                       **_reference_kw(reference, crop_border), **_back_project_kw(back_project),
+                                       **_guidance_kw(consistency_guidance, consistency_guidance_start_steps))
     output, quality = _split_quality(output, reference)
     outs = [unit_tensor_to_pil_on_device(o[0]) for o in output]
     assert all(o.size == (im.size[0] * 4, im.size[1] * 4) for o, im in zip(outs, images))
@@ -451,7 +478,8 @@ def sr_target_images_mixed(images, sr_model, scale=4, batch_size=8, test_label=2
 def sr_target_images_seeded(images, seeds, sr_model, scale=4, batch_size=8, test_label=2, cond_scale=1.0, guidance_start_steps=0,
                             class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0,
                             num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None,
-                            reference=None, crop_border=4, back_project=0):
+                            reference=None, crop_border=4, back_project=0, consistency_guidance=0.0,
+                            consistency_guidance_start_steps=0):
     """``sr_target_images_mixed`` with one noise seed per image (engine extension, ``tiled_sample(seeds=...)``): image i comes out
     bit-identical to its own ``sr_target_image`` run with ``seed=seeds[i]``; an image may appear several times with different
     seeds (each PIL image is upsampled once).  ``seed`` seeds the process as the other entry points do and is not a noise seed."""
@@ -469,7 +497,8 @@ def sr_target_images_seeded(images, seeds, sr_model, scale=4, batch_size=8, test
                                        class_guidance_start_steps=class_guidance_start_steps,
                                        generation_start_steps=generation_start_steps,
                                        num_sample_steps=num_sample_steps, amp=enable_amp, seeds=list(seeds),
-                                       **_color_fix_kw(color_fix), **_reference_kw(reference, crop_border), **_back_project_kw(back_project))
+                                       **_color_fix_kw(color_fix), **_reference_kw(reference, crop_border), **_back_project_kw(back_project),
+                                       **_guidance_kw(consistency_guidance, consistency_guidance_start_steps))
     output, quality = _split_quality(output, reference)
     outs = [unit_tensor_to_pil_on_device(o[0]) for o in output]
     assert all(o.size == (im.size[0] * 4, im.size[1] * 4) for o, im in zip(outs, images))
@@ -503,8 +532,13 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
                            generation_start_steps=0, num_sample_steps=250, start_index=0, end_index=None,
                            enable_amp=False, interpolation="bicubic", seed=71, lockstep=1, lockstep_tiles=None, labels=None,
                            samples=1, color_fix=None, reference_dir=None, crop_border=4, metrics_name="metrics.json", ensemble=False,
-                           ensemble_name="ensemble.json", consistency=False, consistency_name="consistency.json", back_project=0):
-    """``back_project`` (``--back_project N``): N > 0 is handed by keyword to whichever ``sr_target_image*`` function samples a group
+                           ensemble_name="ensemble.json", consistency=False, consistency_name="consistency.json", back_project=0,
+                           consistency_guidance=0.0, consistency_guidance_start_steps=0):
+    """``consistency_guidance`` / ``consistency_guidance_start_steps`` (``--consistency_guidance G``): G > 0 is handed by keyword to
+    whichever ``sr_target_image*`` function samples a group (``tiled_sample(consistency_guidance=G, ...)``: LR-consistency guidance
+    inside the sampling loop); with 0 the keywords are not passed at all.  An input smaller than 5 pixels on a side is then a
+    ``ValueError`` before anything is sampled.
+    ``back_project`` (``--back_project N``): N > 0 is handed by keyword to whichever ``sr_target_image*`` function samples a group
     (``tiled_sample(back_project=N)``: the image is pulled back onto its input before it is saved, so every number below is taken of
     the corrected file); with 0 the keyword is not passed at all.
     ``consistency`` (``--consistency``): after a group is sampled, the images it returned - as saved - and the inputs it was given
@@ -541,8 +575,15 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
               guidance_start_steps=guidance_start_steps, class_cond_scale=class_cond_scale,
               class_guidance_start_steps=class_guidance_start_steps, generation_start_steps=generation_start_steps,
               num_sample_steps=num_sample_steps, enable_amp=enable_amp, interpolation=interpolation, seed=seed,
-              color_fix=None if color_fix in (None, "none") else color_fix, **_back_project_kw(back_project))
+              color_fix=None if color_fix in (None, "none") else color_fix, **_back_project_kw(back_project),
+              **_guidance_kw(consistency_guidance, consistency_guidance_start_steps))
     file_names = sorted(glob.glob(f"{input_dir}/*"))[start_index:end_index]
+    if consistency_guidance:                             # the guidance kernels take inputs of 5 x 5 pixels and more
+        for filename in file_names:
+            image = try_open_image(filename)
+            if image is not None and min(image.size) < GUIDANCE_MIN_SIDE:
+                raise ValueError(f"consistency_guidance: {os.path.basename(filename)} is {image.size[0]}x{image.size[1]}, smaller than "
+                                 f"{GUIDANCE_MIN_SIDE} pixels on a side")
     if reference_dir is not None:
         check_references(file_names, reference_dir, scale, crop_border)
     from concurrent.futures import ThreadPoolExecutor
@@ -791,6 +832,8 @@ def main(argv=None):
                            crop_border=args.crop_border, metrics_name="metrics.json" if world == 1 else f"metrics_rank{rank}.json",
                            ensemble=args.ensemble, ensemble_name="ensemble.json" if world == 1 else f"ensemble_rank{rank}.json",
                            consistency=args.consistency, back_project=args.back_project,
+                           consistency_guidance=args.consistency_guidance,
+                           consistency_guidance_start_steps=args.consistency_guidance_start_steps,
                            consistency_name="consistency.json" if world == 1 else f"consistency_rank{rank}.json")
 
 

@@ -27,6 +27,10 @@ from .backproject import back_project_flat, check_hr_sizes, check_iterations
 from .colorfix import check_mode, color_fix_flat
 from .metrics import check_sizes, metrics_flat, pack_references
 from .engine import HipEngine
+from .guidance import check_start_steps, check_weight, guide_step_flat
+from .guidance import check_hr_sizes as check_guided_sizes
+from .guidance import records as guidance_records
+from .guidance import scratch_bytes as guidance_scratch_bytes
 from .lanes import StepLanes, lanes_setting_from_env, lanes_wanted
 
 __all__ = ["get_coord_and_pad", "get_coords", "get_area", "beta_linear_log_snr", "ConditionalSRUnet",
@@ -246,6 +250,36 @@ def _back_project_steps(back_project, condition_x):
     return steps
 
 
+def _consistency_guidance(weight, start_steps, condition_x):
+    """``tiled_sample(consistency_guidance=w, consistency_guidance_start_steps=s)``: None for a weight of 0 / None (nothing is
+    allocated, nothing is launched), else ``(w, s)`` with every image of ``condition_x`` (a ``[B,3,H,W]`` tensor or a list of
+    ``[1,3,H,W]`` tensors) checked: multiples of 4 and at least 20 on a side - ``ValueError`` before anything is sampled."""
+    weight, start_steps = check_weight(weight), check_start_steps(start_steps)
+    if weight is None:
+        return None
+    conds = condition_x if isinstance(condition_x, (list, tuple)) else [condition_x]
+    check_guided_sizes([(int(c.shape[-2]), int(c.shape[-1])) for c in conds])
+    return weight, start_steps
+
+
+class _GuidedRun:
+    """The LR-consistency guidance of one DDPM run (srgd_amd.guidance): the record array and the scratch are made once, ``step``
+    is one batched call on the run's canvases after step i - x_start += w * g, img += w * fp32(alpha_next_i * c_i) * g inside every
+    crop box (the posterior mean is linear in x_start: reference model.py:3164)."""
+
+    def __init__(self, guidance, images, dev):
+        self.weight, self.start = guidance
+        self.recs, low = guidance_records(images)
+        self.scratch = torch.empty(guidance_scratch_bytes(low), device=dev, dtype=torch.uint8)
+
+    def step(self, i, scalars, img, x_start, cond01):
+        if i < self.start:
+            return
+        mean_weight = float(torch.tensor(scalars[i].alpha_next, dtype=torch.float32) * torch.tensor(scalars[i].c, dtype=torch.float32))
+        guide_step_flat(img.view(-1), x_start.view(-1), cond01.view(-1), self.recs, self.weight, self.weight * mean_weight,
+                        self.scratch)
+
+
 def _as_tuple(v, n):
     return tuple(v) if isinstance(v, (tuple, list)) else (v,) * n
 
@@ -441,7 +475,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                      cond_scale=1.0, guidance_start_steps=0, class_cond_scale=1.0, class_guidance_start_steps=0,
                      generation_start_steps=0, num_sample_steps=None, with_images=False, with_x0_images=False,
                      start_white_noise=True, amp=False, precision=None, seeds=None, color_fix=None, reference=None,
-                     crop_border=4, back_project=0):
+                     crop_border=4, back_project=0, consistency_guidance=0.0, consistency_guidance_start_steps=0):
         """Tiled CFG-DDPM sampling (reference model.py:3288-3413).
 
         ``amp`` is accepted and ignored exactly as in the reference (which always computes fp32); the engine
@@ -482,9 +516,22 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
         back-projection steps - after the colour fix and before the metrics, the final image of every image of the run is pulled
         back onto its own ``condition_x`` on the GPU (srgd_amd.backproject, one batched call per run) and equals
         ``back_project_on_device(result without the keyword, condition_x, N)`` bit for bit.  Trajectories stay raw.  The
-        condition's height and width must be multiples of 4 and at least 20: ``ValueError`` before anything is sampled."""
+        condition's height and width must be multiples of 4 and at least 20: ``ValueError`` before anything is sampled.
+
+        ``consistency_guidance`` (engine-only keyword, absent upstream): a weight w in [0, 1]; 0 (default): nothing is allocated,
+        nothing is launched, the run is byte for byte what it is without the keyword.  With w > 0, after every step
+        i >= max(``consistency_guidance_start_steps``, ``generation_start_steps``) - the last one included - the step's prediction
+        of the clean image is pulled towards the input inside every image's crop box, on the GPU in one batched call per step
+        (srgd_amd.guidance, include/srgd_guidance.h): g = (2 condition_x - 1) - enlarge(reduce(x_start)), x_start += w g,
+        img += w alpha_next_i c_i g - the DDPM posterior mean is linear in x_start, so this is the step taken with the corrected
+        prediction (DDNM / ILVR), and the later steps harmonise the correction.  ``with_x0_images`` shows the corrected
+        predictions.  Every image of a group is bit-identical to its solo guided run.  The condition's height and width must be
+        multiples of 4 and at least 20: ``ValueError`` before anything is sampled.  Not available on a canvas sharded over ranks."""
         color_fix = check_mode(color_fix)
         back_project = _back_project_steps(back_project, condition_x)
+        guidance = _consistency_guidance(consistency_guidance, consistency_guidance_start_steps, condition_x)
+        if guidance is not None and self.canvas_group is not None:
+            raise NotImplementedError("consistency_guidance on a canvas sharded over ranks (canvas_group)")
         if reference is not None:
             reference = _packed_reference(reference, condition_x, crop_border, self)
         num_sample_steps = self.num_sample_steps if num_sample_steps is None else num_sample_steps
@@ -507,7 +554,8 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
             outs = self._tiled_sample_images(batch_size, tile_size, list(condition_x), class_label, cond_scale,
                                              guidance_start_steps, class_cond_scale, class_guidance_start_steps,
                                              generation_start_steps, num_sample_steps, start_white_noise, precision, seeds=seeds,
-                                             color_fix=color_fix, reference=reference, crop_border=crop_border, back_project=back_project)
+                                             color_fix=color_fix, reference=reference, crop_border=crop_border, back_project=back_project,
+                                             guidance=guidance)
             if reference is not None:
                 return (outs[0] if as_list else torch.cat(outs[0], 0)), outs[1]
             return outs if as_list else torch.cat(outs, 0)
@@ -524,7 +572,8 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
             return self._tiled_sample_images(batch_size, tile_size, list(condition_x), class_label, cond_scale,
                                              guidance_start_steps, class_cond_scale, class_guidance_start_steps,
                                              generation_start_steps, num_sample_steps, start_white_noise, precision,
-                                             color_fix=color_fix, reference=reference, crop_border=crop_border, back_project=back_project)
+                                             color_fix=color_fix, reference=reference, crop_border=crop_border, back_project=back_project,
+                                             guidance=guidance)
         if cond_scale != 1.0 and class_cond_scale != 1.0:
             raise NotImplementedError("Currently, you cannot specify both cond_scale and class_cond_scale at the same time.")
         if tile_size != 256 or tile_stride != 256:
@@ -578,9 +627,12 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
             img = _host_randn(self.host_generator, 1, 3, hp, wp).to(dev).repeat(batch, 1, 1, 1)   # reference draw #1 (model.py:3311)
         else:
             img = eng.randn_(torch.empty(1, 3, hp, wp, device=dev), self.device_noise_seed, 0).repeat(batch, 1, 1, 1)
-        x_start = img.clone() if with_x0_images else None
+        x_start = img.clone() if with_x0_images or guidance is not None else None
         image_list = [img[:, :, top:bottom, left:right].clone().cpu()] if with_images else None
         x0_image_list = [img[:, :, top:bottom, left:right].clone().cpu()] if with_x0_images else None
+        guided = None
+        if guidance is not None:            # x_start is laid out like img: final_step_kernel addresses both alike
+            guided = _GuidedRun(guidance, [(b * 3 * hp * wp, b * 3 * h * w, hp, wp, top, left, h, w) for b in range(batch)], dev)
 
         sub_batch = self.max_tiles_per_launch or batch_size
         grids = (coords0, coords1)
@@ -621,6 +673,8 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                 from .parallel import sharded_step
                 sharded_step(eng, self.canvas_group, i, n_tiles * batch, img, cond_canvas, x_start, noise_tiles,
                              noise_canvas, passes, kind, scale, sub_batch, self.device_noise_seed)
+            if guided is not None:          # the lanes have joined the main stream: a plain launch after the step's
+                guided.step(i, scalars, img, x_start, cond01)
             if with_images:
                 image_list.append(img.clone().cpu())
             if with_x0_images:
@@ -642,7 +696,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
     def _tiled_sample_images(self, batch_size, tile_size, conds, class_label, cond_scale, guidance_start_steps,
                              class_cond_scale, class_guidance_start_steps, generation_start_steps, num_sample_steps,
                              start_white_noise, precision, seeds=None, color_fix=None, reference=None, crop_border=4,
-                             back_project=None):
+                             back_project=None, guidance=None):
         """Mixed-size lock-step (srgd_sampler_begin_images): every image keeps its own canvas, crop box, padding, inner box and
         tile grids; a step's tiles of all images share the U-Net launches.  Noise: the images of one noise class (canvas size)
         see the draw sequence a run of one of them alone sees.  Host noise: the generator state is taken once at entry and
@@ -655,7 +709,10 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
         the streams' seeds (srgd_sampler_noise_seeds) and draws all of them in one launch per use.
 
         ``reference``: None, or ``(flat uint8 buffer, byte offsets)`` of the images' ground truth (``pack_references``); the return
-        value is then ``(outputs, list of metric dicts)``."""
+        value is then ``(outputs, list of metric dicts)``.
+
+        ``guidance``: None, or ``(weight, start step)`` of ``consistency_guidance`` (validated by the caller): the run keeps an
+        ``x_start`` buffer laid out like ``img`` and makes one batched guidance call for all images after every guided step."""
         from .lockstep import plan_mixed_group
         dev = self.device
         if dev.type != "cuda":
@@ -732,6 +789,16 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                                    for (hp, wp) in classes])
             img = torch.cat([start[offs[p.noise_class]:offs[p.noise_class + 1]] for p in plans])
 
+        x_start = guided = None
+        if guidance is not None:
+            x_start = img.clone()
+            canvas_offs, cond_offs = [0], [0]
+            for p in plans:
+                canvas_offs.append(canvas_offs[-1] + 3 * p.Hp * p.Wp)
+                cond_offs.append(cond_offs[-1] + 3 * p.H * p.W)
+            guided = _GuidedRun(guidance, [(canvas_offs[k], cond_offs[k], p.Hp, p.Wp, p.box[1], p.box[0], p.H, p.W)
+                                           for k, p in enumerate(plans)], dev)
+
         sub_batch = self.max_tiles_per_launch or batch_size
         n_grid = (len(tiles_even), len(tiles_odd))
         lanes = None
@@ -757,11 +824,13 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                         begin(e_, torch.empty_like(cond_canvas))
                     lanes = StepLanes([eng] + more, dev)
                 lanes.run(n_step, lambda e_, first, count, ring: e_.sampler_step_tiles(
-                    i, first, count, ring, img, cond_canvas, None, noise_tiles, noise_canvas, passes, kind, scale, sub_batch,
+                    i, first, count, ring, img, cond_canvas, x_start, noise_tiles, noise_canvas, passes, kind, scale, sub_batch,
                     seed=self.device_noise_seed))
             else:
-                eng.sampler_step(i, img, cond_canvas, None, noise_tiles, noise_canvas, passes, kind, scale, sub_batch,
+                eng.sampler_step(i, img, cond_canvas, x_start, noise_tiles, noise_canvas, passes, kind, scale, sub_batch,
                                  seed=self.device_noise_seed)
+            if guided is not None:
+                guided.step(i, scalars, img, x_start, cond01)
 
         out = torch.empty(sum(3 * p.H * p.W for p in plans), device=dev, dtype=torch.float32)
         eng.sampler_end(img, out)
@@ -972,15 +1041,20 @@ class ConditionalElucidatedDiffusionSR(nn.Module):
                      cond_scale=1.0, guidance_start_steps=0, class_cond_scale=1.0, class_guidance_start_steps=0,
                      generation_start_steps=0, num_sample_steps=None, clamp=True, zero_init=False, with_images=False,
                      with_x0_images=False, start_white_noise=True, amp=False, precision=None, seeds=None, color_fix=None,
-                     reference=None, crop_border=4, back_project=0):
+                     reference=None, crop_border=4, back_project=0, consistency_guidance=0.0, consistency_guidance_start_steps=0):
         """Reference model.py:2309-2475 (``start_white_noise`` and ``amp`` are accepted and unused there too; ``precision``
         is the engine-only override of ``self.precision``).  ``seeds`` (per-image noise seeds) is a DDPM-sampler feature and is
         refused here.  ``color_fix``: as in the DDPM wrapper's ``tiled_sample`` - the final image of every image of the batch
         colour-corrected against its condition, trajectories raw.  ``reference`` / ``crop_border``: as there too - the ground
         truth of every image of the batch; the return value gains a trailing list of metric dicts.  ``back_project``: as there
-        too - N back-projection steps on the final image, after the colour fix and before the metrics."""
+        too - N back-projection steps on the final image, after the colour fix and before the metrics.
+        ``consistency_guidance``: a DDPM-sampler feature; a non-zero weight is refused here."""
         color_fix = check_mode(color_fix)
         back_project = _back_project_steps(back_project, condition_x)
+        check_start_steps(consistency_guidance_start_steps)
+        if check_weight(consistency_guidance) is not None:
+            raise NotImplementedError("consistency_guidance is built for the DDPM sampler only: its correction of the canvas rests on "
+                                      "the DDPM posterior mean, linear in the predicted clean image")
         if reference is not None and not isinstance(condition_x, (list, tuple)):
             reference = _packed_reference(reference, condition_x, crop_border, self)
         n = self.num_sample_steps if num_sample_steps is None else num_sample_steps
