@@ -35,6 +35,7 @@ from .guidance import MIN_SIDE as GUIDANCE_MIN_SIDE
 from .metrics import KEYS as METRIC_KEYS
 from .metrics import metrics_on_device  # noqa: F401  (public: srgd_amd.inference.metrics_on_device)
 from .model import ConditionalElucidatedDiffusionSR, get_model
+from .solver import check_sampler
 
 logger = logging.getLogger("srgd_amd")
 
@@ -119,7 +120,23 @@ def parse_args(argv=None):
                         "raises the LR-PSNR --consistency reports; inputs must be at least 5 pixels on a side (engine extension)")
     p.add_argument("--consistency_guidance_start_steps", type=int, default=0, metavar="S",
                    help="with --consistency_guidance: the first guided step (default 0: every step)")
+    p.add_argument("--sampler", choices=["ddpm", "ddim", "dpmpp2m"], default="ddpm",
+                   help="the step of the tiled DDPM sampling loop: ddpm (default) is the reference's ancestral step; ddim is the DDIM "
+                        "family's step with --eta; dpmpp2m is the deterministic second-order multistep solver DPM-Solver++ 2M, which "
+                        "with --step_spacing logsnr reaches in 15-20 steps what the first-order steps need 50 and more for - one "
+                        "small extra GPU launch per step; the noise draws are those of a ddpm run of the same --num_sample_steps "
+                        "(engine extension)")
+    p.add_argument("--eta", type=float, default=None, metavar="E",
+                   help="with --sampler ddim: the share E in [0, 1] of the ancestral step's noise (default 0: deterministic; 1 is the "
+                        "ddpm step up to rounding); dpmpp2m takes 0 only, ddpm none")
+    p.add_argument("--step_spacing", choices=["time", "logsnr"], default="time",
+                   help="where the --num_sample_steps steps end: time (default) is the reference's uniform grid in t, whose last steps "
+                        "jump several units of log-SNR; logsnr is uniform in the log-SNR itself (engine extension)")
     args = p.parse_args(argv)
+    try:
+        check_sampler(args.sampler, args.eta, args.step_spacing)
+    except ValueError as e:
+        raise SystemExit(f"--sampler / --eta / --step_spacing: {e}")
     if not 0.0 <= args.consistency_guidance <= 1.0:         # NaN fails both comparisons
         raise SystemExit(f"--consistency_guidance: G must be in [0, 1], got {args.consistency_guidance}")
     if args.consistency_guidance_start_steps < 0:
@@ -201,6 +218,19 @@ def _guidance_kw(consistency_guidance, consistency_guidance_start_steps=0):
     if not consistency_guidance:
         return {}
     return {"consistency_guidance": consistency_guidance, "consistency_guidance_start_steps": consistency_guidance_start_steps}
+
+
+def _sampler_kw(sampler="ddpm", eta=None, step_spacing="time"):
+    """``tiled_sample``'s ``sampler`` / ``eta`` / ``step_spacing`` keywords, each only where it is not the default (nothing for the
+    call a run without the flags makes)."""
+    kw = {}
+    if sampler not in (None, "ddpm"):
+        kw["sampler"] = sampler
+    if eta is not None:
+        kw["eta"] = eta
+    if step_spacing not in (None, "time"):
+        kw["step_spacing"] = step_spacing
+    return kw
 
 
 def _reference_kw(reference, crop_border):
@@ -393,7 +423,7 @@ def sr_target_image(image, sr_model, scale=4, batch_size=8, test_label=2, cond_s
                     class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0,
                     num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None, reference=None,
                     crop_border=4, back_project=0, consistency_guidance=0.0,
-                    consistency_guidance_start_steps=0):
+                    consistency_guidance_start_steps=0, sampler="ddpm", eta=None, step_spacing="time"):
     """``reference`` (engine extension; here and in the three group forms below): the ground truth as a uint8 ``[H,W,3]`` tensor (a
     list of one per image in the group forms).  The return value is then ``(image(s), metric dicts)``: PSNR / SSIM of every image as
     saved, with ``crop_border`` pixels cut from every side (srgd_amd.metrics)."""
@@ -411,7 +441,8 @@ def sr_target_image(image, sr_model, scale=4, batch_size=8, test_label=2, cond_s
                                        generation_start_steps=generation_start_steps,
                                        num_sample_steps=num_sample_steps, amp=enable_amp, **_color_fix_kw(color_fix),
                                        **_reference_kw(reference, crop_border), **_back_project_kw(back_project),
-                                       **_guidance_kw(consistency_guidance, consistency_guidance_start_steps))
+                                       **_guidance_kw(consistency_guidance, consistency_guidance_start_steps),
+                                       **_sampler_kw(sampler, eta, step_spacing))
     output, quality = _split_quality(output, reference)
     sr_img = unit_tensor_to_pil_on_device(output[0])
     assert sr_img.size == (width * 4, height * 4)
@@ -422,7 +453,7 @@ def sr_target_images(images, sr_model, scale=4, batch_size=8, test_label=2, cond
                      class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0,
                      num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None, reference=None,
                      crop_border=4, back_project=0, consistency_guidance=0.0,
-                     consistency_guidance_start_steps=0):
+                     consistency_guidance_start_steps=0, sampler="ddpm", eta=None, step_spacing="time"):
     """``sr_target_image`` for several same-sized images in lock-step (engine extension): one ``tiled_sample`` call on a
     ``[B,3,H,W]`` condition.  Each image is sampled exactly as it would be alone after the reference's per-image
     ``seed_everything(seed)`` (inference.py:73) - bit-identical outputs - while their tiles fill the U-Net launches.
@@ -441,7 +472,8 @@ def sr_target_images(images, sr_model, scale=4, batch_size=8, test_label=2, cond
                                        generation_start_steps=generation_start_steps,
                                        num_sample_steps=num_sample_steps, amp=enable_amp, **_color_fix_kw(color_fix),
                                        **_reference_kw(reference, crop_border), **_back_project_kw(back_project),
-                                       **_guidance_kw(consistency_guidance, consistency_guidance_start_steps))
+                                       **_guidance_kw(consistency_guidance, consistency_guidance_start_steps),
+                                       **_sampler_kw(sampler, eta, step_spacing))
     output, quality = _split_quality(output, reference)
     outs = [unit_tensor_to_pil_on_device(o) for o in output]
     assert all(o.size == (width * 4, height * 4) for o in outs)
@@ -452,7 +484,7 @@ def sr_target_images_mixed(images, sr_model, scale=4, batch_size=8, test_label=2
                            class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0,
                            num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None, reference=None,
                            crop_border=4, back_project=0, consistency_guidance=0.0,
-                           consistency_guidance_start_steps=0):
+                           consistency_guidance_start_steps=0, sampler="ddpm", eta=None, step_spacing="time"):
     """``sr_target_image`` for several images of any sizes in lock-step (engine extension): one ``tiled_sample`` call on a list
     of conditions.  Each image comes out bit-identical to its own ``sr_target_image`` run (with its own label where
     ``test_label`` is a sequence of one label per image)."""
@@ -468,7 +500,8 @@ def sr_target_images_mixed(images, sr_model, scale=4, batch_size=8, test_label=2
                                        generation_start_steps=generation_start_steps,
                                        num_sample_steps=num_sample_steps, amp=enable_amp, **_color_fix_kw(color_fix),
                                        **_reference_kw(reference, crop_border), **_back_project_kw(back_project),
-                                       **_guidance_kw(consistency_guidance, consistency_guidance_start_steps))
+                                       **_guidance_kw(consistency_guidance, consistency_guidance_start_steps),
+                                       **_sampler_kw(sampler, eta, step_spacing))
     output, quality = _split_quality(output, reference)
     outs = [unit_tensor_to_pil_on_device(o[0]) for o in output]
     assert all(o.size == (im.size[0] * 4, im.size[1] * 4) for o, im in zip(outs, images))
@@ -479,7 +512,7 @@ def sr_target_images_seeded(images, seeds, sr_model, scale=4, batch_size=8, test
                             class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0,
                             num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None,
                             reference=None, crop_border=4, back_project=0, consistency_guidance=0.0,
-                            consistency_guidance_start_steps=0):
+                            consistency_guidance_start_steps=0, sampler="ddpm", eta=None, step_spacing="time"):
     """``sr_target_images_mixed`` with one noise seed per image (engine extension, ``tiled_sample(seeds=...)``): image i comes out
     bit-identical to its own ``sr_target_image`` run with ``seed=seeds[i]``; an image may appear several times with different
     seeds (each PIL image is upsampled once).  ``seed`` seeds the process as the other entry points do and is not a noise seed."""
@@ -498,7 +531,8 @@ def sr_target_images_seeded(images, seeds, sr_model, scale=4, batch_size=8, test
                                        generation_start_steps=generation_start_steps,
                                        num_sample_steps=num_sample_steps, amp=enable_amp, seeds=list(seeds),
                                        **_color_fix_kw(color_fix), **_reference_kw(reference, crop_border), **_back_project_kw(back_project),
-                                       **_guidance_kw(consistency_guidance, consistency_guidance_start_steps))
+                                       **_guidance_kw(consistency_guidance, consistency_guidance_start_steps),
+                                       **_sampler_kw(sampler, eta, step_spacing))
     output, quality = _split_quality(output, reference)
     outs = [unit_tensor_to_pil_on_device(o[0]) for o in output]
     assert all(o.size == (im.size[0] * 4, im.size[1] * 4) for o, im in zip(outs, images))
@@ -533,8 +567,12 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
                            enable_amp=False, interpolation="bicubic", seed=71, lockstep=1, lockstep_tiles=None, labels=None,
                            samples=1, color_fix=None, reference_dir=None, crop_border=4, metrics_name="metrics.json", ensemble=False,
                            ensemble_name="ensemble.json", consistency=False, consistency_name="consistency.json", back_project=0,
-                           consistency_guidance=0.0, consistency_guidance_start_steps=0):
-    """``consistency_guidance`` / ``consistency_guidance_start_steps`` (``--consistency_guidance G``): G > 0 is handed by keyword to
+                           consistency_guidance=0.0, consistency_guidance_start_steps=0, sampler="ddpm", eta=None,
+                           step_spacing="time"):
+    """``sampler`` / ``eta`` / ``step_spacing`` (``--sampler``, ``--eta``, ``--step_spacing``): each is handed by keyword to whichever
+    ``sr_target_image*`` function samples a group only where it is not the default ("ddpm", None, "time"); bad values are a
+    ``ValueError`` before anything is sampled.
+    ``consistency_guidance`` / ``consistency_guidance_start_steps`` (``--consistency_guidance G``): G > 0 is handed by keyword to
     whichever ``sr_target_image*`` function samples a group (``tiled_sample(consistency_guidance=G, ...)``: LR-consistency guidance
     inside the sampling loop); with 0 the keywords are not passed at all.  An input smaller than 5 pixels on a side is then a
     ``ValueError`` before anything is sampled.
@@ -576,7 +614,8 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
               class_guidance_start_steps=class_guidance_start_steps, generation_start_steps=generation_start_steps,
               num_sample_steps=num_sample_steps, enable_amp=enable_amp, interpolation=interpolation, seed=seed,
               color_fix=None if color_fix in (None, "none") else color_fix, **_back_project_kw(back_project),
-              **_guidance_kw(consistency_guidance, consistency_guidance_start_steps))
+              **_guidance_kw(consistency_guidance, consistency_guidance_start_steps), **_sampler_kw(sampler, eta, step_spacing))
+    check_sampler(sampler or "ddpm", eta, step_spacing or "time")
     file_names = sorted(glob.glob(f"{input_dir}/*"))[start_index:end_index]
     if consistency_guidance:                             # the guidance kernels take inputs of 5 x 5 pixels and more
         for filename in file_names:
@@ -834,6 +873,7 @@ def main(argv=None):
                            consistency=args.consistency, back_project=args.back_project,
                            consistency_guidance=args.consistency_guidance,
                            consistency_guidance_start_steps=args.consistency_guidance_start_steps,
+                           sampler=args.sampler, eta=args.eta, step_spacing=args.step_spacing,
                            consistency_name="consistency.json" if world == 1 else f"consistency_rank{rank}.json")
 
 

@@ -31,6 +31,8 @@ from .guidance import check_start_steps, check_weight, guide_step_flat
 from .guidance import check_hr_sizes as check_guided_sizes
 from .guidance import records as guidance_records
 from .guidance import scratch_bytes as guidance_scratch_bytes
+from .solver import check_sampler, history_step_flat, history_weights, is_default, step_coefficients
+from .solver import records as solver_records
 from .lanes import StepLanes, lanes_setting_from_env, lanes_wanted
 
 __all__ = ["get_coord_and_pad", "get_coords", "get_area", "beta_linear_log_snr", "ConditionalSRUnet",
@@ -87,11 +89,30 @@ def beta_linear_log_snr(t: torch.Tensor) -> torch.Tensor:
     return -torch.log(torch.special.expm1(1e-4 + 10 * (t ** 2)).clamp(min=1e-20))
 
 
-def _schedule(num_steps: int) -> Tuple[List[StepScalars], List[float]]:
+def _log_snr_levels(num_steps: int, step_spacing: str = "time") -> List[torch.Tensor]:
+    """The N + 1 fp32 log-SNR levels of a run (0-dim tensors): step i goes from level i to level i + 1.  "time": the levels of
+    ``linspace(1, 0, N + 1)`` in t, each computed as ``_schedule`` computes it; "logsnr": uniform in the log-SNR itself."""
+    if step_spacing == "logsnr":
+        levels = torch.linspace(float(beta_linear_log_snr(torch.tensor(1.0))), float(beta_linear_log_snr(torch.tensor(0.0))),
+                                num_steps + 1)
+        return [levels[i] for i in range(num_steps + 1)]
     times = torch.linspace(1.0, 0.0, num_steps + 1)
+    return [beta_linear_log_snr(times[i]) for i in range(num_steps + 1)]
+
+
+def _schedule(num_steps: int, sampler: str = "ddpm", eta: Optional[float] = None,
+              step_spacing: str = "time") -> Tuple[List[StepScalars], List[float]]:
+    """The step table and the log-SNR the U-Net is conditioned on at every step.  Called with ``num_steps`` alone: the reference's
+    ancestral step on its uniform times.  ``step_spacing="logsnr"`` takes the steps' ends from ``_log_snr_levels``; ``sampler``
+    "ddim" (``eta`` in [0, 1]) and "dpmpp2m" (eta 0) replace ``one_minus_c``, ``c`` and ``noise_scale`` - the three scalars the step
+    kernel reads independently - by fp32(A alpha / alpha_next), fp32(B / alpha_next) and fp32(S) of srgd_amd.solver's float64
+    ``step_coefficients``, so that the kernel's ``alpha_next * (x_t * one_minus_c / alpha + c * x0) + noise_scale * z`` is
+    ``A x_t + B x0 + S z``; ``alpha_next * c`` is then B, the weight of x0 the guidance reads."""
+    times = torch.linspace(1.0, 0.0, num_steps + 1)
+    levels = _log_snr_levels(num_steps, step_spacing) if step_spacing != "time" else None
     scalars, log_snrs = [], []
     for i in range(num_steps):
-        ls, ls_next = beta_linear_log_snr(times[i]), beta_linear_log_snr(times[i + 1])
+        ls, ls_next = (beta_linear_log_snr(times[i]), beta_linear_log_snr(times[i + 1])) if levels is None else (levels[i], levels[i + 1])
         c = -torch.special.expm1(ls - ls_next)
         alpha, sigma = ls.sigmoid().sqrt(), (-ls).sigmoid().sqrt()
         alpha_next = ls_next.sigmoid().sqrt()
@@ -101,6 +122,9 @@ def _schedule(num_steps: int) -> Tuple[List[StepScalars], List[float]]:
         s.one_minus_c = float(1 - c)
         s.noise_scale = float(var.sqrt())
         s.sigma_next = float((-ls_next).sigmoid().sqrt())
+        if sampler != "ddpm":
+            a_, b_, s_ = step_coefficients(float(ls), float(ls_next), eta or 0.0)
+            s.one_minus_c, s.c, s.noise_scale = a_ * s.alpha / s.alpha_next, b_ / s.alpha_next, s_
         scalars.append(s)
         log_snrs.append(float(ls))
     return scalars, log_snrs
@@ -278,6 +302,31 @@ class _GuidedRun:
         mean_weight = float(torch.tensor(scalars[i].alpha_next, dtype=torch.float32) * torch.tensor(scalars[i].c, dtype=torch.float32))
         guide_step_flat(img.view(-1), x_start.view(-1), cond01.view(-1), self.recs, self.weight, self.weight * mean_weight,
                         self.scratch)
+
+
+def _start_log_snr(generation_start_steps, num_sample_steps, step_spacing):
+    """The log-SNR level a run that does not start from white noise is forward-diffused to (0-dim fp32): the reference's
+    t0 = 1 - g / N under "time"; level g of the run's own list under "logsnr"."""
+    if step_spacing != "time":
+        return _log_snr_levels(num_sample_steps, step_spacing)[generation_start_steps]
+    t0 = (1.0 - torch.tensor(generation_start_steps / num_sample_steps)) if generation_start_steps > 0 \
+        else torch.tensor(1.0)
+    return beta_linear_log_snr(t0)
+
+
+class _SolverRun:
+    """The history of one dpmpp2m run (srgd_amd.solver): ``x_prev`` - a clone of ``x_start``, so it is finite from the start - and
+    the record array of the images' inner boxes are made once; ``step`` is one batched call on the run's canvases after step i (and
+    after the step's guidance call, so that the history holds the corrected predictions): img += w_i (x_start - x_prev) inside
+    every inner box, x_prev = x_start.  The ring outside the box is re-noised on every odd step: it has no history."""
+
+    def __init__(self, num_sample_steps, step_spacing, first_step, images, x_start):
+        self.weights = history_weights(_log_snr_levels(num_sample_steps, step_spacing), first_step)
+        self.recs = solver_records(images)
+        self.x_prev = x_start.clone()
+
+    def step(self, i, img, x_start):
+        history_step_flat(img.view(-1), x_start.view(-1), self.x_prev.view(-1), self.recs, self.weights[i])
 
 
 def _as_tuple(v, n):
@@ -475,7 +524,8 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                      cond_scale=1.0, guidance_start_steps=0, class_cond_scale=1.0, class_guidance_start_steps=0,
                      generation_start_steps=0, num_sample_steps=None, with_images=False, with_x0_images=False,
                      start_white_noise=True, amp=False, precision=None, seeds=None, color_fix=None, reference=None,
-                     crop_border=4, back_project=0, consistency_guidance=0.0, consistency_guidance_start_steps=0):
+                     crop_border=4, back_project=0, consistency_guidance=0.0, consistency_guidance_start_steps=0,
+                     sampler="ddpm", eta=None, step_spacing="time"):
         """Tiled CFG-DDPM sampling (reference model.py:3288-3413).
 
         ``amp`` is accepted and ignored exactly as in the reference (which always computes fp32); the engine
@@ -526,12 +576,28 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
         img += w alpha_next_i c_i g - the DDPM posterior mean is linear in x_start, so this is the step taken with the corrected
         prediction (DDNM / ILVR), and the later steps harmonise the correction.  ``with_x0_images`` shows the corrected
         predictions.  Every image of a group is bit-identical to its solo guided run.  The condition's height and width must be
-        multiples of 4 and at least 20: ``ValueError`` before anything is sampled.  Not available on a canvas sharded over ranks."""
+        multiples of 4 and at least 20: ``ValueError`` before anything is sampled.  Not available on a canvas sharded over ranks.
+
+        ``sampler``, ``eta``, ``step_spacing`` (engine-only keywords, absent upstream): the defaults "ddpm", None, "time" are the
+        run byte for byte as it is without them.  ``sampler="ddim"`` with ``eta`` in [0, 1] (default 0) is the DDIM family's step
+        A x_t + B x0 + S z as a step table (srgd_amd.solver.step_coefficients; eta = 1 is the ancestral step up to rounding);
+        ``sampler="dpmpp2m"`` (``eta`` None or 0) is the second-order multistep DPM-Solver++ 2M: the eta = 0 table and, after every
+        step but the first executed and the last, img += w_i (x_start_i - x_start_{i-1}) inside every image's inner box on the GPU,
+        one batched call per step after the guidance call if there is one (srgd_amd.solver, include/srgd_solver.h).  The noise
+        draws of every sampler are those of a ddpm run of the same length (with S = 0 the tile noise is multiplied by zero).
+        ``step_spacing="logsnr"`` places the N + 1 step ends uniformly in the log-SNR instead of in t, which is what makes few
+        steps worth taking; ``generation_start_steps = g`` then starts from level g of that list.  Bad values: ``ValueError``
+        before anything is sampled.  dpmpp2m is not available on a canvas sharded over ranks (its history would have to travel
+        with the tile exchange); ddim and ``step_spacing`` only change tables and are."""
+        sampler, eta, step_spacing = check_sampler(sampler, eta, step_spacing)
+        solver = None if is_default(sampler, eta, step_spacing) else (sampler, eta, step_spacing)
         color_fix = check_mode(color_fix)
         back_project = _back_project_steps(back_project, condition_x)
         guidance = _consistency_guidance(consistency_guidance, consistency_guidance_start_steps, condition_x)
         if guidance is not None and self.canvas_group is not None:
             raise NotImplementedError("consistency_guidance on a canvas sharded over ranks (canvas_group)")
+        if sampler == "dpmpp2m" and self.canvas_group is not None:
+            raise NotImplementedError("sampler='dpmpp2m' on a canvas sharded over ranks (canvas_group)")
         if reference is not None:
             reference = _packed_reference(reference, condition_x, crop_border, self)
         num_sample_steps = self.num_sample_steps if num_sample_steps is None else num_sample_steps
@@ -555,7 +621,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                                              guidance_start_steps, class_cond_scale, class_guidance_start_steps,
                                              generation_start_steps, num_sample_steps, start_white_noise, precision, seeds=seeds,
                                              color_fix=color_fix, reference=reference, crop_border=crop_border, back_project=back_project,
-                                             guidance=guidance)
+                                             guidance=guidance, solver=solver)
             if reference is not None:
                 return (outs[0] if as_list else torch.cat(outs[0], 0)), outs[1]
             return outs if as_list else torch.cat(outs, 0)
@@ -573,7 +639,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                                              guidance_start_steps, class_cond_scale, class_guidance_start_steps,
                                              generation_start_steps, num_sample_steps, start_white_noise, precision,
                                              color_fix=color_fix, reference=reference, crop_border=crop_border, back_project=back_project,
-                                             guidance=guidance)
+                                             guidance=guidance, solver=solver)
         if cond_scale != 1.0 and class_cond_scale != 1.0:
             raise NotImplementedError("Currently, you cannot specify both cond_scale and class_cond_scale at the same time.")
         if tile_size != 256 or tile_stride != 256:
@@ -605,7 +671,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
         (sl, st_, sr, sb), _ = get_area(coords1, hp, wp)
         geo = SamplerGeometry(H=h, W=w, Hp=hp, Wp=wp, left=left, top=top, inner_l=sl, inner_t=st_, inner_r=sr,
                               inner_b=sb, tile=tile_size, n_even=len(coords0), n_odd=len(coords1), n_images=batch)
-        scalars, log_snrs = _schedule(num_sample_steps)
+        scalars, log_snrs = _schedule(num_sample_steps) if solver is None else _schedule(num_sample_steps, *solver)
 
         cond01 = condition_x.to(dev, torch.float32).contiguous()
         cond_canvas = torch.empty(batch, 3, hp, wp, device=dev, dtype=torch.float32)
@@ -617,9 +683,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
         host_noise = self.noise_source == "host"
         if generation_start_steps > 0 or not start_white_noise:
             # start from the forward-diffused condition (model.py:3305-3308 / :3312-3315); same single draw
-            t0 = (1.0 - torch.tensor(generation_start_steps / num_sample_steps)) if generation_start_steps > 0 \
-                else torch.tensor(1.0)
-            ls0 = beta_linear_log_snr(t0)
+            ls0 = _start_log_snr(generation_start_steps, num_sample_steps, step_spacing)
             img = torch.empty(batch, 3, hp, wp, device=dev)
             eng.sampler_q_start(cond01, _host_randn(self.host_generator, 1, 3, hp, wp).to(dev) if host_noise else None,
                                 float(ls0.sigmoid().sqrt()), float((-ls0).sigmoid().sqrt()), img, self.device_noise_seed)
@@ -627,12 +691,16 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
             img = _host_randn(self.host_generator, 1, 3, hp, wp).to(dev).repeat(batch, 1, 1, 1)   # reference draw #1 (model.py:3311)
         else:
             img = eng.randn_(torch.empty(1, 3, hp, wp, device=dev), self.device_noise_seed, 0).repeat(batch, 1, 1, 1)
-        x_start = img.clone() if with_x0_images or guidance is not None else None
+        x_start = img.clone() if with_x0_images or guidance is not None or sampler == "dpmpp2m" else None
         image_list = [img[:, :, top:bottom, left:right].clone().cpu()] if with_images else None
         x0_image_list = [img[:, :, top:bottom, left:right].clone().cpu()] if with_x0_images else None
         guided = None
         if guidance is not None:            # x_start is laid out like img: final_step_kernel addresses both alike
             guided = _GuidedRun(guidance, [(b * 3 * hp * wp, b * 3 * h * w, hp, wp, top, left, h, w) for b in range(batch)], dev)
+        history = None
+        if sampler == "dpmpp2m":            # the inner box of the odd grid: what is never re-noised
+            history = _SolverRun(num_sample_steps, step_spacing, generation_start_steps,
+                                 [(b * 3 * hp * wp, hp, wp, st_, sl, sb - st_, sr - sl) for b in range(batch)], x_start)
 
         sub_batch = self.max_tiles_per_launch or batch_size
         grids = (coords0, coords1)
@@ -675,6 +743,8 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                              noise_canvas, passes, kind, scale, sub_batch, self.device_noise_seed)
             if guided is not None:          # the lanes have joined the main stream: a plain launch after the step's
                 guided.step(i, scalars, img, x_start, cond01)
+            if history is not None:         # after the guidance: the history holds the corrected predictions
+                history.step(i, img, x_start)
             if with_images:
                 image_list.append(img.clone().cpu())
             if with_x0_images:
@@ -696,7 +766,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
     def _tiled_sample_images(self, batch_size, tile_size, conds, class_label, cond_scale, guidance_start_steps,
                              class_cond_scale, class_guidance_start_steps, generation_start_steps, num_sample_steps,
                              start_white_noise, precision, seeds=None, color_fix=None, reference=None, crop_border=4,
-                             back_project=None, guidance=None):
+                             back_project=None, guidance=None, solver=None):
         """Mixed-size lock-step (srgd_sampler_begin_images): every image keeps its own canvas, crop box, padding, inner box and
         tile grids; a step's tiles of all images share the U-Net launches.  Noise: the images of one noise class (canvas size)
         see the draw sequence a run of one of them alone sees.  Host noise: the generator state is taken once at entry and
@@ -712,7 +782,11 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
         value is then ``(outputs, list of metric dicts)``.
 
         ``guidance``: None, or ``(weight, start step)`` of ``consistency_guidance`` (validated by the caller): the run keeps an
-        ``x_start`` buffer laid out like ``img`` and makes one batched guidance call for all images after every guided step."""
+        ``x_start`` buffer laid out like ``img`` and makes one batched guidance call for all images after every guided step.
+
+        ``solver``: None, or ``(sampler, eta, step_spacing)`` of a non-default sampler (validated by the caller): the step table and
+        the levels are ``_schedule``'s of it; "dpmpp2m" keeps ``x_start`` and a history buffer and makes one batched history call
+        for all images after every step, after the guidance call."""
         from .lockstep import plan_mixed_group
         dev = self.device
         if dev.type != "cuda":
@@ -736,7 +810,8 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                                     n_odd=len(p.coords1), noise_class=p.noise_class) for p in plans]
         tiles_even = [(a, c_) for p in plans for (a, _, c_, _) in p.coords0]
         tiles_odd = [(a, c_) for p in plans for (a, _, c_, _) in p.coords1]
-        scalars, log_snrs = _schedule(num_sample_steps)
+        scalars, log_snrs = _schedule(num_sample_steps) if solver is None else _schedule(num_sample_steps, *solver)
+        sampler_name, step_spacing = ("ddpm", "time") if solver is None else (solver[0], solver[2])
         cond01 = torch.cat([c.to(dev, torch.float32).reshape(-1) for c in conds])
         cond_canvas = torch.empty(sum(3 * p.Hp * p.Wp for p in plans), device=dev, dtype=torch.float32)
 
@@ -769,9 +844,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
             def canvas_draw():
                 return draw(lambda k: (1, 3) + classes[k])
         if generation_start_steps > 0 or not start_white_noise:
-            t0 = (1.0 - torch.tensor(generation_start_steps / num_sample_steps)) if generation_start_steps > 0 \
-                else torch.tensor(1.0)
-            ls0 = beta_linear_log_snr(t0)
+            ls0 = _start_log_snr(generation_start_steps, num_sample_steps, step_spacing)
             img = torch.empty_like(cond_canvas)
             eng.sampler_q_start(cond01, canvas_draw() if host_noise else None, float(ls0.sigmoid().sqrt()),
                                 float((-ls0).sigmoid().sqrt()), img, self.device_noise_seed)
@@ -789,13 +862,18 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                                    for (hp, wp) in classes])
             img = torch.cat([start[offs[p.noise_class]:offs[p.noise_class + 1]] for p in plans])
 
-        x_start = guided = None
-        if guidance is not None:
+        x_start = guided = history = None
+        canvas_offs, cond_offs = [0], [0]
+        for p in plans:
+            canvas_offs.append(canvas_offs[-1] + 3 * p.Hp * p.Wp)
+            cond_offs.append(cond_offs[-1] + 3 * p.H * p.W)
+        if guidance is not None or sampler_name == "dpmpp2m":
             x_start = img.clone()
-            canvas_offs, cond_offs = [0], [0]
-            for p in plans:
-                canvas_offs.append(canvas_offs[-1] + 3 * p.Hp * p.Wp)
-                cond_offs.append(cond_offs[-1] + 3 * p.H * p.W)
+        if sampler_name == "dpmpp2m":       # every image's inner box: what is never re-noised
+            history = _SolverRun(num_sample_steps, step_spacing, generation_start_steps,
+                                 [(canvas_offs[k], p.Hp, p.Wp, p.inner[1], p.inner[0], p.inner[3] - p.inner[1], p.inner[2] - p.inner[0])
+                                  for k, p in enumerate(plans)], x_start)
+        if guidance is not None:
             guided = _GuidedRun(guidance, [(canvas_offs[k], cond_offs[k], p.Hp, p.Wp, p.box[1], p.box[0], p.H, p.W)
                                            for k, p in enumerate(plans)], dev)
 
@@ -831,6 +909,8 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                                  seed=self.device_noise_seed)
             if guided is not None:
                 guided.step(i, scalars, img, x_start, cond01)
+            if history is not None:
+                history.step(i, img, x_start)
 
         out = torch.empty(sum(3 * p.H * p.W for p in plans), device=dev, dtype=torch.float32)
         eng.sampler_end(img, out)
@@ -1041,20 +1121,25 @@ class ConditionalElucidatedDiffusionSR(nn.Module):
                      cond_scale=1.0, guidance_start_steps=0, class_cond_scale=1.0, class_guidance_start_steps=0,
                      generation_start_steps=0, num_sample_steps=None, clamp=True, zero_init=False, with_images=False,
                      with_x0_images=False, start_white_noise=True, amp=False, precision=None, seeds=None, color_fix=None,
-                     reference=None, crop_border=4, back_project=0, consistency_guidance=0.0, consistency_guidance_start_steps=0):
+                     reference=None, crop_border=4, back_project=0, consistency_guidance=0.0, consistency_guidance_start_steps=0,
+                     sampler="ddpm", eta=None, step_spacing="time"):
         """Reference model.py:2309-2475 (``start_white_noise`` and ``amp`` are accepted and unused there too; ``precision``
         is the engine-only override of ``self.precision``).  ``seeds`` (per-image noise seeds) is a DDPM-sampler feature and is
         refused here.  ``color_fix``: as in the DDPM wrapper's ``tiled_sample`` - the final image of every image of the batch
         colour-corrected against its condition, trajectories raw.  ``reference`` / ``crop_border``: as there too - the ground
         truth of every image of the batch; the return value gains a trailing list of metric dicts.  ``back_project``: as there
         too - N back-projection steps on the final image, after the colour fix and before the metrics.
-        ``consistency_guidance``: a DDPM-sampler feature; a non-zero weight is refused here."""
+        ``consistency_guidance``: a DDPM-sampler feature; a non-zero weight is refused here.
+        ``sampler``, ``eta``, ``step_spacing``: the DDPM wrapper's few-step samplers; any non-default value is refused here."""
         color_fix = check_mode(color_fix)
         back_project = _back_project_steps(back_project, condition_x)
         check_start_steps(consistency_guidance_start_steps)
         if check_weight(consistency_guidance) is not None:
             raise NotImplementedError("consistency_guidance is built for the DDPM sampler only: its correction of the canvas rests on "
                                       "the DDPM posterior mean, linear in the predicted clean image")
+        if not is_default(*check_sampler(sampler, eta, step_spacing)):
+            raise NotImplementedError("sampler / eta / step_spacing are built for the DDPM sampler only: the EDM wrapper has its own "
+                                      "schedule and its own solvers (sample_using_dpmpp)")
         if reference is not None and not isinstance(condition_x, (list, tuple)):
             reference = _packed_reference(reference, condition_x, crop_border, self)
         n = self.num_sample_steps if num_sample_steps is None else num_sample_steps
