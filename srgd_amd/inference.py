@@ -35,6 +35,8 @@ from .guidance import MIN_SIDE as GUIDANCE_MIN_SIDE
 from .metrics import KEYS as METRIC_KEYS
 from .metrics import metrics_on_device  # noqa: F401  (public: srgd_amd.inference.metrics_on_device)
 from .model import ConditionalElucidatedDiffusionSR, get_model
+from .resize import FILTERS as OUTSCALE_FILTERS
+from .resize import check_filter, check_outscale, outscale_size
 from .solver import check_sampler
 
 logger = logging.getLogger("srgd_amd")
@@ -90,8 +92,8 @@ def parse_args(argv=None):
     p.add_argument("--reference_dir", type=str, default=None, metavar="DIR",
                    help="ground truth of the inputs: the reference of IN/NAME.png is DIR/NAME.png, exactly x4 its size.  Y-channel "
                         "PSNR, RGB PSNR and Y-channel SSIM of every written file (as saved, after --color_fix) are computed on the GPU "
-                        "and written to OUTPUT_DIR/metrics.json with per-image means over --samples and a mean over all images "
-                        "(engine extension)")
+                        "and written to OUTPUT_DIR/metrics.json with per-image means over --samples and a mean over all images; with "
+                        "--outscale the x4 image is measured, before the resize (engine extension)")
     p.add_argument("--crop_border", type=int, default=4, metavar="N",
                    help="pixels cut from every side of output and reference before the --reference_dir numbers are taken (default 4, "
                         "the scale factor, as the x4 super-resolution literature does)")
@@ -104,8 +106,8 @@ def parse_args(argv=None):
                    help="LR consistency of every written file: the output as saved (after --color_fix) is reduced x4 on the GPU with the "
                         "operator that made the condition (Pillow's bicubic) and compared with its own input - no ground truth "
                         "needed.  LR-PSNR, LR-MSE and the largest 8-bit error go to OUTPUT_DIR/consistency.json with per-image means "
-                        "over --samples and a mean over all images; with --ensemble the mean images are measured too (engine "
-                        "extension)")
+                        "over --samples and a mean over all images; with --ensemble the mean images are measured too; with "
+                        "--outscale the x4 image is measured, before the resize (engine extension)")
     p.add_argument("--back_project", type=int, default=0, metavar="N",
                    help="pull every output back onto its own input on the GPU with N <= 64 steps of iterative back-projection, after "
                         "--color_fix and before the file is saved: the output is reduced x4 and enlarged x4 again with Pillow's bicubic "
@@ -132,7 +134,24 @@ def parse_args(argv=None):
     p.add_argument("--step_spacing", choices=["time", "logsnr"], default="time",
                    help="where the --num_sample_steps steps end: time (default) is the reference's uniform grid in t, whose last steps "
                         "jump several units of log-SNR; logsnr is uniform in the log-SNR itself (engine extension)")
+    p.add_argument("--outscale", type=float, default=4.0, metavar="S",
+                   help="write every file at S times the size of its input instead of 4 times, S in [0.5, 32] (4, the default: off): the "
+                        "x4 output as it would have been saved - after --color_fix and --back_project - is resampled on the GPU to "
+                        "max(1, floor(in * S + 0.5)) pixels per axis, bit for bit Pillow's Image.resize, immediately before the file "
+                        "is encoded; every sample of --samples is resized; not with --ensemble (engine extension)")
+    p.add_argument("--outscale_filter", choices=list(OUTSCALE_FILTERS), default=None,
+                   help="with --outscale: the filter of the resize (default bicubic, the operator that made the model's conditions)")
     args = p.parse_args(argv)
+    try:
+        args.outscale = check_outscale(args.outscale)
+    except ValueError as e:
+        raise SystemExit(f"--outscale: {e}")
+    if args.outscale is None and args.outscale_filter is not None:
+        raise SystemExit("--outscale_filter: needs --outscale S with S != 4")
+    args.outscale_filter = check_filter(args.outscale_filter)
+    if args.ensemble and args.outscale is not None:
+        raise SystemExit("--ensemble: not together with --outscale (the ensemble reads samples back at x4 of the input and feeds the x4 "
+                         "metrics)")
     try:
         check_sampler(args.sampler, args.eta, args.step_spacing)
     except ValueError as e:
@@ -568,8 +587,13 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
                            samples=1, color_fix=None, reference_dir=None, crop_border=4, metrics_name="metrics.json", ensemble=False,
                            ensemble_name="ensemble.json", consistency=False, consistency_name="consistency.json", back_project=0,
                            consistency_guidance=0.0, consistency_guidance_start_steps=0, sampler="ddpm", eta=None,
-                           step_spacing="time"):
-    """``sampler`` / ``eta`` / ``step_spacing`` (``--sampler``, ``--eta``, ``--step_spacing``): each is handed by keyword to whichever
+                           step_spacing="time", outscale=None, outscale_filter="bicubic"):
+    """``outscale`` / ``outscale_filter`` (``--outscale S``, ``--outscale_filter``): with S other than None / 4 every image a group
+    returned - the 8-bit image as it would have been saved, after everything above has been measured on it - goes through one batched
+    ``resize_on_device`` call per ``flush()`` (srgd_amd.resize: Pillow's ``Image.resize`` bit for bit) to ``outscale_size`` of its
+    input, and that image is saved; ``reference_dir`` and ``consistency`` keep measuring the x4 image.  With None / 4 the library is
+    not loaded and nothing is launched.  Not together with ``ensemble`` (``ValueError``).
+    ``sampler`` / ``eta`` / ``step_spacing`` (``--sampler``, ``--eta``, ``--step_spacing``): each is handed by keyword to whichever
     ``sr_target_image*`` function samples a group only where it is not the default ("ddpm", None, "time"); bad values are a
     ``ValueError`` before anything is sampled.
     ``consistency_guidance`` / ``consistency_guidance_start_steps`` (``--consistency_guidance G``): G > 0 is handed by keyword to
@@ -616,6 +640,9 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
               color_fix=None if color_fix in (None, "none") else color_fix, **_back_project_kw(back_project),
               **_guidance_kw(consistency_guidance, consistency_guidance_start_steps), **_sampler_kw(sampler, eta, step_spacing))
     check_sampler(sampler or "ddpm", eta, step_spacing or "time")
+    outscale, outscale_filter = check_outscale(outscale), check_filter(outscale_filter)
+    if ensemble and outscale is not None:
+        raise ValueError("ensemble: not together with outscale")
     file_names = sorted(glob.glob(f"{input_dir}/*"))[start_index:end_index]
     if consistency_guidance:                             # the guidance kernels take inputs of 5 x 5 pixels and more
         for filename in file_names:
@@ -697,6 +724,13 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
                 source = dict(zip(written, (e[5] for e in pending)))
                 cons_records.extend((source[name], name, rec) for name, rec in
                                     measure_consistency(written, [pil_to_u8_tensor(sr) for sr in outs], group_images))
+            if outscale is not None:                     # last of all: the images as they would have been saved, resized in one call
+                from .resize import resize_on_device
+                device = getattr(sr_model, "device", None)
+                u8 = [pil_to_u8_tensor(sr) for sr in outs]
+                resized = resize_on_device([t.to(device) for t in u8] if device is not None else u8,
+                                           [outscale_size(im.size[1], im.size[0], outscale) for im in group_images], outscale_filter)
+                outs = [Image.fromarray(t.cpu().numpy(), "RGB") for t in resized]
             for e, sr in zip(pending, outs):
                 saves.append(pool.submit(sr.save, e[1]))
                 if e[6] in ens_open:                     # --ensemble: sample e[3] - seed of the file has been drawn
@@ -874,6 +908,7 @@ def main(argv=None):
                            consistency_guidance=args.consistency_guidance,
                            consistency_guidance_start_steps=args.consistency_guidance_start_steps,
                            sampler=args.sampler, eta=args.eta, step_spacing=args.step_spacing,
+                           outscale=args.outscale, outscale_filter=args.outscale_filter,
                            consistency_name="consistency.json" if world == 1 else f"consistency_rank{rank}.json")
 
 
