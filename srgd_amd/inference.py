@@ -23,6 +23,9 @@ import numpy as np
 import torch
 from PIL import Image
 
+from .alpha import MAX_BLEED as ALPHA_BLEED_MAX
+from .alpha import alpha_of, check_bleed, check_mode
+from .alpha import attach_alpha_on_device, bleed_on_device, resize_planes_on_device  # noqa: F401  (public: srgd_amd.inference.*)
 from .backproject import MAX_ITERATIONS as BACK_PROJECT_MAX
 from .backproject import back_project_on_device  # noqa: F401  (public: srgd_amd.inference.back_project_on_device)
 from .colorfix import color_fix_on_device  # noqa: F401  (public: srgd_amd.inference.color_fix_on_device)
@@ -141,7 +144,26 @@ def parse_args(argv=None):
                         "is encoded; every sample of --samples is resized; not with --ensemble (engine extension)")
     p.add_argument("--outscale_filter", choices=list(OUTSCALE_FILTERS), default=None,
                    help="with --outscale: the filter of the resize (default bicubic, the operator that made the model's conditions)")
+    p.add_argument("--alpha", choices=["drop", "keep"], default="drop",
+                   help="keep: an input with transparency (modes RGBA, LA, PA, or a tRNS chunk) is written as an RGBA file: its alpha "
+                        "plane is enlarged x4 on the GPU with Pillow's bicubic, the operator that makes the model's conditions, and with "
+                        "--outscale resized again with --outscale_filter, bit for bit the alpha band of Pillow's Image.resize; the "
+                        "colour is the image a run without the flag writes and is not premultiplied; inputs without transparency are "
+                        "written as RGB as before; every sample of --samples gets the same alpha; not with --ensemble.  drop (the "
+                        "default): the alpha channel is ignored (engine extension)")
+    p.add_argument("--alpha_bleed", type=int, default=0, metavar="N",
+                   help="with --alpha keep: before anything else sees a transparent input, spread the colours of its visible pixels "
+                        "(alpha > 0) N <= 64 pixels into the transparent area on the GPU - every pass gives each unknown pixel the "
+                        "rounded mean of its known 8-neighbours - so that the arbitrary colour stored under transparent pixels does "
+                        "not leak across the outline as a halo; the bled image is the input of the whole run (condition, --color_fix, "
+                        "--back_project, --consistency_guidance, --consistency); the alpha itself is unchanged (0, the default: off)")
     args = p.parse_args(argv)
+    if not 0 <= args.alpha_bleed <= ALPHA_BLEED_MAX:
+        raise SystemExit(f"--alpha_bleed: N must be in 0 .. {ALPHA_BLEED_MAX}, got {args.alpha_bleed}")
+    if args.alpha_bleed and args.alpha != "keep":
+        raise SystemExit("--alpha_bleed: needs --alpha keep")
+    if args.ensemble and args.alpha == "keep":
+        raise SystemExit("--ensemble: not together with --alpha keep (the ensemble reads samples back as RGB; the mean image gets no alpha)")
     try:
         args.outscale = check_outscale(args.outscale)
     except ValueError as e:
@@ -580,6 +602,16 @@ def try_open_image(image_path):
         return None
 
 
+def try_open_image_with_alpha(image_path):
+    """``try_open_image`` for ``--alpha keep``: ``(the RGB image, its alpha plane as uint8 [h,w] or None)`` - ``srgd_amd.alpha.alpha_of``
+    of the decoded file - or ``(None, None)`` where the file cannot be opened."""
+    try:
+        image = Image.open(image_path)
+        return image.convert("RGB"), alpha_of(image)
+    except (IOError, SyntaxError):
+        return None, None
+
+
 def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=8, test_label=2, cond_scale=1.0,
                            guidance_start_steps=0, class_cond_scale=1.0, class_guidance_start_steps=0,
                            generation_start_steps=0, num_sample_steps=250, start_index=0, end_index=None,
@@ -587,8 +619,15 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
                            samples=1, color_fix=None, reference_dir=None, crop_border=4, metrics_name="metrics.json", ensemble=False,
                            ensemble_name="ensemble.json", consistency=False, consistency_name="consistency.json", back_project=0,
                            consistency_guidance=0.0, consistency_guidance_start_steps=0, sampler="ddpm", eta=None,
-                           step_spacing="time", outscale=None, outscale_filter="bicubic"):
-    """``outscale`` / ``outscale_filter`` (``--outscale S``, ``--outscale_filter``): with S other than None / 4 every image a group
+                           step_spacing="time", outscale=None, outscale_filter="bicubic", alpha="drop", alpha_bleed=0):
+    """``alpha`` / ``alpha_bleed`` (``--alpha keep``, ``--alpha_bleed N``): with "keep" every input is opened with its alpha plane
+    (``try_open_image_with_alpha``); an input that has one is, with N > 0, bled once per opened file (``bleed_on_device``: the bled RGB
+    image replaces the input for everything below, the K samples of a file share it), sampled and measured as RGB like every other
+    input, and last of all in ``flush()`` - after the ``outscale`` block - the outputs of such inputs get their alpha in one batched
+    ``attach_alpha_on_device`` call (srgd_amd.alpha) and are saved as RGBA files.  Inputs without transparency are written as RGB.
+    With "drop" (the default) the library is not loaded and nothing is launched.  Not together with ``ensemble``; N > 0 needs "keep"
+    (``ValueError``).
+    ``outscale`` / ``outscale_filter`` (``--outscale S``, ``--outscale_filter``): with S other than None / 4 every image a group
     returned - the 8-bit image as it would have been saved, after everything above has been measured on it - goes through one batched
     ``resize_on_device`` call per ``flush()`` (srgd_amd.resize: Pillow's ``Image.resize`` bit for bit) to ``outscale_size`` of its
     input, and that image is saved; ``reference_dir`` and ``consistency`` keep measuring the x4 image.  With None / 4 the library is
@@ -643,6 +682,11 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
     outscale, outscale_filter = check_outscale(outscale), check_filter(outscale_filter)
     if ensemble and outscale is not None:
         raise ValueError("ensemble: not together with outscale")
+    alpha, alpha_bleed = check_mode(alpha), check_bleed(alpha_bleed)
+    if alpha_bleed and alpha != "keep":
+        raise ValueError("alpha_bleed: needs alpha=\"keep\"")
+    if ensemble and alpha == "keep":
+        raise ValueError("ensemble: not together with alpha=\"keep\"")
     file_names = sorted(glob.glob(f"{input_dir}/*"))[start_index:end_index]
     if consistency_guidance:                             # the guidance kernels take inputs of 5 x 5 pixels and more
         for filename in file_names:
@@ -731,6 +775,19 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
                 resized = resize_on_device([t.to(device) for t in u8] if device is not None else u8,
                                            [outscale_size(im.size[1], im.size[0], outscale) for im in group_images], outscale_filter)
                 outs = [Image.fromarray(t.cpu().numpy(), "RGB") for t in resized]
+            with_alpha = [i for i, e in enumerate(pending) if e[7] is not None]
+            if with_alpha:                               # --alpha keep: the outputs whose input had an alpha plane leave as RGBA
+                device = getattr(sr_model, "device", None)
+                place = (lambda t: t.to(device)) if device is not None else (lambda t: t)        # noqa: E731
+                lows = {}                                # the K samples of a file share one upload of the plane
+                for i in with_alpha:
+                    if id(pending[i][7]) not in lows:
+                        lows[id(pending[i][7])] = place(torch.from_numpy(pending[i][7]))
+                rgba = attach_alpha_on_device([place(pil_to_u8_tensor(outs[i])) for i in with_alpha],
+                                              [lows[id(pending[i][7])] for i in with_alpha], scale, outscale_filter)
+                outs = list(outs)
+                for i, t in zip(with_alpha, rgba):
+                    outs[i] = Image.fromarray(t.cpu().numpy(), "RGBA")
             for e, sr in zip(pending, outs):
                 saves.append(pool.submit(sr.save, e[1]))
                 if e[6] in ens_open:                     # --ensemble: sample e[3] - seed of the file has been drawn
@@ -793,9 +850,19 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
                 ens_records.append((os.path.basename(filename), mean_name, std_name, res[2]))
 
         opened = (None, None, None)                      # the K samples of a file share one decoded image and one reference
+        plane = None                                     # --alpha keep: the alpha plane of the opened file, or None
         for filename, save_path, noise_seed in plan_sample_entries(file_names, output_dir, samples, seed):
             if opened[0] != filename:
-                opened = (filename, try_open_image(filename), None)
+                if alpha == "keep":
+                    image, plane = try_open_image_with_alpha(filename)
+                    if plane is not None and alpha_bleed:        # once per opened file: the bled image is the input from here on
+                        device = getattr(sr_model, "device", None)
+                        rgba = torch.from_numpy(np.dstack([np.asarray(image, dtype=np.uint8), plane]))
+                        bled = bleed_on_device([rgba.to(device) if device is not None else rgba], alpha_bleed)[0]
+                        image = Image.fromarray(bled.cpu().numpy(), "RGB")
+                    opened = (filename, image, None)
+                else:
+                    opened = (filename, try_open_image(filename), None)
                 if opened[1] is None:
                     print("Invalid image or unable to open image:", filename)
                 elif reference_dir is not None:          # decoded on the pool while the groups before this one sample
@@ -810,11 +877,11 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
                 hr = [(h * scale, w * scale) for (w, h) in [e[0].size for e in pending] + [image.size]]
                 if len(plan_lockstep_groups(hr, lockstep_tiles)) > 1:      # the image would push the group over the budget
                     flush()
-                pending.append((image, save_path, label, noise_seed, ref, os.path.basename(filename), filename))
+                pending.append((image, save_path, label, noise_seed, ref, os.path.basename(filename), filename, plane))
                 continue
             if pending and (len(pending) >= max(1, lockstep) or pending[0][0].size != image.size):
                 flush()
-            pending.append((image, save_path, label, noise_seed, ref, os.path.basename(filename), filename))
+            pending.append((image, save_path, label, noise_seed, ref, os.path.basename(filename), filename, plane))
             if len(pending) >= max(1, lockstep):
                 flush()
         flush()
@@ -908,7 +975,8 @@ def main(argv=None):
                            consistency_guidance=args.consistency_guidance,
                            consistency_guidance_start_steps=args.consistency_guidance_start_steps,
                            sampler=args.sampler, eta=args.eta, step_spacing=args.step_spacing,
-                           outscale=args.outscale, outscale_filter=args.outscale_filter,
+                           outscale=args.outscale, outscale_filter=args.outscale_filter, alpha=args.alpha,
+                           alpha_bleed=args.alpha_bleed,
                            consistency_name="consistency.json" if world == 1 else f"consistency_rank{rank}.json")
 
 

@@ -1,0 +1,388 @@
+"""srgd_amd.alpha without a GPU: the numpy restatements of tests/alpha_cases.py against Pillow itself (the ``L`` resize, band A of the
+RGBA resize, ``Image.merge``), ``alpha_of`` over the PNG modes, the properties of the bleed, the command line of --alpha and
+--alpha_bleed, the C ABI (header, prototypes, export tables of all nine libraries), the refusals of the three device calls (decided
+on the host before anything is launched) and the compiler's resource table of the five kernels."""
+import ctypes as C
+import io
+import os
+import re
+import shutil
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+from PIL import Image
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from srgd_amd import _lib  # noqa: E402
+from srgd_amd import alpha as AL  # noqa: E402
+from srgd_amd import backproject as BP  # noqa: E402
+from srgd_amd import consistency as CS  # noqa: E402
+from srgd_amd import ensemble as EN  # noqa: E402
+from srgd_amd import guidance as GD  # noqa: E402
+from srgd_amd import metrics as MX  # noqa: E402
+from srgd_amd import resize as RZ  # noqa: E402
+from srgd_amd import solver as SV  # noqa: E402
+from srgd_amd import inference as INF  # noqa: E402
+from srgd_amd.inference import parse_args  # noqa: E402
+from tests import alpha_cases as AC  # noqa: E402
+from tests import resize_cases as RC  # noqa: E402
+from tools.kernel_resources import kernel_table  # noqa: E402
+
+ENTRIES = {"srgd_alpha_last_error", "srgd_alpha_resize_planes", "srgd_alpha_pack_rgba", "srgd_alpha_bleed"}
+
+
+# ------------------------------------------------------------------------------------------- (a) the restatements are Pillow's
+@pytest.mark.parametrize("filter", list(RC.FILTERS))
+def test_the_plane_restatement_is_pillows_L_resize_and_band_A_of_its_RGBA_resize(filter):
+    pil = Image.Resampling(RC.FILTERS[filter])
+    assert len(AC.PLANE_CASES) >= 40 and AC.SMALLEST in AC.PLANE_CASES
+    assert {w % 4 for (_, w), _ in AC.PLANE_CASES} == {w % 4 for _, (_, w) in AC.PLANE_CASES} == {0, 1, 2, 3}
+    for in_size, out_size in AC.PLANE_CASES:
+        for name in AC.PATTERNS:
+            p = AC.plane(name, *in_size)
+            got = AC.expected_plane(name, in_size, out_size, filter)
+            want = np.asarray(Image.fromarray(p, "L").resize((out_size[1], out_size[0]), pil))
+            assert got.shape == want.shape == out_size and got.dtype == np.uint8
+            assert np.array_equal(got, want), (in_size, out_size, filter, name)
+            rgba = Image.fromarray(np.dstack([AC.colour(*in_size), p]), "RGBA").resize((out_size[1], out_size[0]), pil)
+            assert np.array_equal(got, np.asarray(rgba.getchannel("A"))), (in_size, out_size, filter, name)
+    if filter != "bilinear":                                                   # both ends of clip8
+        up = AC.expected_plane("checker", (8, 6), (64, 48), filter)
+        assert up.min() == 0 and up.max() == 255
+
+
+def test_the_attach_restatement_is_the_merge_composition():
+    for (h, w), final in [((10, 13), (40, 52))] + AC.TWO_STAGE + [((5, 7), (3, 4)), ((3, 5), (96, 160))]:
+        for filter in RC.FILTERS:
+            a = AC.plane("noise", h, w)
+            rgb = AC.colour(*final)
+            a4 = Image.fromarray(a, "L").resize((4 * w, 4 * h), Image.Resampling.BICUBIC)
+            if final != (4 * h, 4 * w):
+                # the alpha band Pillow's Image.resize gives for the RGBA image built at x4
+                at4 = Image.merge("RGBA", (*Image.fromarray(AC.colour(4 * h, 4 * w), "RGB").split(), a4))
+                band = at4.resize((final[1], final[0]), Image.Resampling(RC.FILTERS[filter])).getchannel("A")
+                a4 = a4.resize((final[1], final[0]), Image.Resampling(RC.FILTERS[filter]))
+                assert np.array_equal(np.asarray(a4), np.asarray(band))
+            want = np.asarray(Image.merge("RGBA", (*Image.fromarray(rgb, "RGB").split(), a4)))
+            got = AC.attach(rgb, a, 4, filter)
+            assert got.dtype == np.uint8 and np.array_equal(got, want), ((h, w), final, filter)
+    for h, w in AC.PACK_SIZES:
+        want = np.asarray(Image.merge("RGBA", (*Image.fromarray(AC.colour(h, w), "RGB").split(), Image.fromarray(AC.plane("noise", h, w), "L"))))
+        assert np.array_equal(AC.pack(AC.colour(h, w), AC.plane("noise", h, w)), want)
+    assert sorted({h * w % 4 for h, w in AC.PACK_SIZES}) == [0, 1, 2, 3] and (1, 1) in AC.PACK_SIZES
+    assert max(h * w for h, w in AC.PACK_SIZES) > 2 * AC.PACK_BLOCK
+
+
+# ------------------------------------------------------------------------------------------- (b) alpha_of
+def _png(image, **kw):
+    buf = io.BytesIO()
+    image.save(buf, "PNG", **kw)
+    return Image.open(io.BytesIO(buf.getvalue()))
+
+
+def test_alpha_of_over_the_png_modes():
+    rng = np.random.default_rng(5)
+    h, w = 6, 9
+    a = rng.integers(0, 256, (h, w), dtype=np.uint8)
+    rgb = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+    idx = rng.integers(0, 4, (h, w), dtype=np.uint8)
+    pal = Image.fromarray(idx, "P")
+    pal.putpalette([10, 20, 30, 200, 100, 50, 0, 0, 0, 255, 255, 255] + [0] * (3 * 252))
+    grey = Image.fromarray(rgb[:, :, 0], "L")
+    pa = Image.fromarray(np.dstack([rgb, a]), "RGBA").convert("PA")
+    cases = {"RGBA": (_png(Image.fromarray(np.dstack([rgb, a]), "RGBA")), "RGBA", a),
+             "LA": (_png(Image.fromarray(np.dstack([rgb[:, :, 0], a]), "LA")), "LA", a),
+             "PA": (pa, "PA", np.asarray(pa.getchannel("A"))),
+             "P+tRNS": (_png(pal, transparency=bytes([0, 128, 255, 7])), "P", np.array([0, 128, 255, 7], np.uint8)[idx]),
+             "L+tRNS": (_png(grey, transparency=int(rgb[0, 0, 0])), "L", np.where(rgb[:, :, 0] == rgb[0, 0, 0], 0, 255).astype(np.uint8)),
+             "RGB+tRNS": (_png(Image.fromarray(rgb, "RGB"), transparency=tuple(int(v) for v in rgb[2, 3])), "RGB",
+                          np.where((rgb == rgb[2, 3]).all(axis=2), 0, 255).astype(np.uint8)),
+             "L": (_png(grey), "L", None), "RGB": (_png(Image.fromarray(rgb, "RGB")), "RGB", None), "P": (_png(pal), "P", None)}
+    for name, (im, mode, want) in cases.items():
+        assert im.mode == mode, name
+        got = AL.alpha_of(im)
+        if want is None:
+            assert got is None and not im.has_transparency_data, name
+            continue
+        assert im.has_transparency_data, name
+        assert got.dtype == np.uint8 and got.shape == (h, w) and got.flags.writeable and np.array_equal(got, want), name
+        assert np.array_equal(got, np.asarray(im.convert("RGBA").getchannel("A"))), name
+        # the colour the driver samples is the first three bands of the RGBA form
+        assert np.array_equal(np.asarray(im.convert("RGB")), np.asarray(im.convert("RGBA"))[:, :, :3]), name
+    assert not np.array_equal(cases["L+tRNS"][2], np.full((h, w), 255)) and cases["RGB+tRNS"][2][2, 3] == 0
+
+
+def test_the_sibling_of_try_open_image_returns_the_plane(tmp_path):
+    rgba = np.dstack([AC.colour(5, 6), AC.plane("noise", 5, 6)])
+    Image.fromarray(rgba, "RGBA").save(tmp_path / "a.png")
+    Image.fromarray(AC.colour(5, 6), "RGB").save(tmp_path / "b.png")
+    (tmp_path / "c.png").write_bytes(b"not an image")
+    image, plane = INF.try_open_image_with_alpha(str(tmp_path / "a.png"))
+    assert image.mode == "RGB" and np.array_equal(np.asarray(image), rgba[:, :, :3]) and np.array_equal(plane, rgba[:, :, 3])
+    assert np.array_equal(np.asarray(image), np.asarray(INF.try_open_image(str(tmp_path / "a.png"))))
+    image, plane = INF.try_open_image_with_alpha(str(tmp_path / "b.png"))
+    assert image.mode == "RGB" and plane is None
+    assert INF.try_open_image_with_alpha(str(tmp_path / "c.png")) == (None, None)
+    assert INF.attach_alpha_on_device is AL.attach_alpha_on_device and INF.bleed_on_device is AL.bleed_on_device
+    assert INF.resize_planes_on_device is AL.resize_planes_on_device
+
+
+# ------------------------------------------------------------------------------------------- (c) the bleed
+def test_bleed_properties():
+    for h, w in AC.BLEED_SIZES:
+        for name in AC.BLEED_PATTERNS:
+            img = AC.bleed_image(name, h, w)
+            known = img[:, :, 3] > 0
+            dist = AC.chebyshev_to_known(img[:, :, 3])
+            assert np.array_equal(AC.expected_bleed(name, h, w, 0), img[:, :, :3])                 # N = 0 is the RGB as given
+            before = img[:, :, :3]
+            for n in AC.BLEED_PASSES:
+                out = AC.expected_bleed(name, h, w, n)
+                assert out.shape == (h, w, 3) and out.dtype == np.uint8
+                assert np.array_equal(out[known], img[:, :, :3][known]), (name, h, w, n)            # known pixels never change
+                assert np.array_equal(out[dist > n], img[:, :, :3][dist > n]), (name, h, w, n)      # out of reach: the original colour
+                if n > 0:                                # a pixel changes in pass d exactly: filled after N passes iff 0 < dist <= N
+                    again = AC.bleed(img, n - 1)
+                    ring = dist == n
+                    assert np.array_equal(out[~ring], again[~ring]), (name, h, w, n)
+                before = out
+            if name in ("transparent", "opaque"):
+                assert np.array_equal(before, img[:, :, :3])
+    # filled exactly when the Chebyshev distance is <= N: a marker colour that no mean of known pixels can produce
+    rng = np.random.default_rng(3)
+    a = np.where(rng.random((21, 30)) < 0.93, 0, 255).astype(np.uint8)
+    img = np.dstack([np.where(a[:, :, None] > 0, rng.integers(100, 200, (21, 30, 3)), 7).astype(np.uint8), a])
+    dist = AC.chebyshev_to_known(a)
+    for n in (0, 1, 2, 3, 5):
+        filled = (AC.bleed(img, n)[:, :, 0] != 7)
+        assert np.array_equal(filled, dist <= n), n
+    # a single opaque pixel grows into a (2 N + 1)^2 square of its colour
+    one = np.zeros((15, 15, 4), np.uint8)
+    one[7, 7] = (10, 200, 33, 1)
+    for n in (0, 1, 3, 7, 64):
+        out = AC.bleed(one, n)
+        r = min(n, 7)
+        want = np.zeros((15, 15, 3), np.uint8)
+        want[7 - r:8 + r, 7 - r:8 + r] = (10, 200, 33)
+        assert np.array_equal(out, want), n
+
+
+def test_bleed_hand_computed_9x9_with_two_seeds_meeting():
+    img = np.zeros((9, 9, 4), np.uint8)
+    img[:, :, :3] = 99                                                        # the colour stored under the transparent pixels
+    img[4, 1] = (10, 10, 10, 255)
+    img[4, 7] = (200, 200, 200, 3)
+    want = np.full((9, 9), 99)
+    # pass 1: the 3x3 rings round the seeds; pass 2: the 5x5 rings - columns 0..3 from the left seed, 5..8 from the right one
+    want[2:7, 0:4] = 10
+    want[2:7, 5:9] = 200
+    # pass 3: column 4 of rows 1..7 sees known pixels on both sides: rows 2..6 see as many 10s as 200s -> (2 s + c) // (2 c) = 105;
+    # rows 1 and 7 see one of each (the corners of the 5x5 squares) -> 105; the rest of rows 1 and 7 continue their own seed
+    want[1, 0:4] = want[7, 0:4] = 10
+    want[1, 5:9] = want[7, 5:9] = 200
+    want[1:8, 4] = 105
+    out = AC.bleed(img, 3)
+    assert np.array_equal(out[:, :, 0], want) and np.array_equal(out[:, :, 1], want) and np.array_equal(out[:, :, 2], want)
+    assert (2 * (3 * 10 + 3 * 200) + 6) // (2 * 6) == 105 and (2 * (10 + 200) + 2) // 4 == 105
+    # rounding half up: neighbours 10 and 11 -> 10.5 -> 11
+    two = np.zeros((1, 3, 4), np.uint8)
+    two[0, 0] = (10, 0, 255, 255)
+    two[0, 2] = (11, 1, 254, 255)
+    assert AC.bleed(two, 1)[0, 1].tolist() == [11, 1, 255]
+
+
+# ------------------------------------------------------------------------------------------- (d) the command line
+def test_argument_parsing(tmp_path):
+    base = ["-c", "conf.yaml", "-m", "ckpt.pth", "--input_dir", "in", "--output_dir", "out"]
+    plain = parse_args(base)
+    assert plain.alpha == "drop" and plain.alpha_bleed == 0
+    assert vars(parse_args(base + ["--alpha", "drop", "--alpha_bleed", "0"])) == vars(plain)
+    keep = parse_args(base + ["--alpha", "keep"])
+    assert keep.alpha == "keep" and keep.alpha_bleed == 0
+    bled = parse_args(base + ["--alpha", "keep", "--alpha_bleed", "64", "--samples", "3", "--outscale", "2", "--consistency"])
+    assert bled.alpha == "keep" and bled.alpha_bleed == 64 and bled.outscale == 2.0
+    # refused at argument parsing: no configuration file, checkpoint or folder of these names exists, no model is built
+    for extra in (["--alpha_bleed", "65"], ["--alpha", "keep", "--alpha_bleed", "65"], ["--alpha", "keep", "--alpha_bleed", "-1"],
+                  ["--alpha_bleed", "3"], ["--alpha", "drop", "--alpha_bleed", "3"], ["--alpha", "premultiply"],
+                  ["--alpha", "keep", "--alpha_bleed", "2.5"], ["--alpha", "keep", "--samples", "2", "--ensemble"],
+                  ["--alpha", "keep", "--alpha_bleed", "3", "--samples", "2", "--ensemble"]):
+        with pytest.raises(SystemExit) as err:
+            parse_args(base + extra)
+        assert err.value.code not in (0, None), extra
+    assert parse_args(base + ["--samples", "2", "--ensemble"]).ensemble         # --ensemble alone is kept
+    assert AL.check_mode(None) == "drop" and AL.check_bleed(0) == 0 and AL.check_bleed(64) == 64
+    for bad in (65, -1, 2.0, True, "3", None):
+        with pytest.raises(ValueError):
+            AL.check_bleed(bad)
+    with pytest.raises(ValueError):
+        AL.check_mode("premultiply")
+    for kw in (dict(alpha_bleed=3), dict(alpha="keep", ensemble=True, samples=2), dict(alpha="keep", alpha_bleed=65), dict(alpha="both")):
+        with pytest.raises(ValueError):                                       # before a file is listed or the model is touched
+            INF.batch_sr_target_images(str(tmp_path / "no_such_folder"), str(tmp_path / "out"), None, **kw)
+
+
+# ------------------------------------------------------------------------------------------- (e) C ABI, refusals, resources
+def _exports(path):
+    nm = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+    exported = {ln.split()[-1] for ln in nm.splitlines() if len(ln.split()) >= 3 and ln.split()[-2] in "TtWw"}
+    return {n for n in exported if not n.startswith(("_init", "_fini", "__"))}
+
+
+def test_entries_are_declared_prototyped_and_exported_by_a_library_of_their_own():
+    header = open(os.path.join(ROOT, "include", "srgd_alpha.h")).read()
+    flat = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    declared = set(re.findall(r"\b(srgd_[a-z0-9_]+)\s*\(", flat))
+    assert declared == ENTRIES == set(AL.PROTOTYPES)
+    for name, (_, argtypes) in AL.PROTOTYPES.items():
+        params = re.search(r"\b" + name + r"\s*\(([^)]*)\)", flat).group(1).strip()
+        assert (0 if params == "void" else len(params.split(","))) == len(argtypes), name
+    for struct, cls, size in (("srgd_alpha_plane", AL.AlphaPlane, 48), ("srgd_alpha_image", AL.AlphaImage, 32)):
+        fields = re.search(r"typedef struct " + struct + r" \{(.*?)\}", flat, flags=re.S).group(1)
+        names = [n.strip() for decl in fields.split(";") if decl.strip() for n in decl.strip().split(" ", 1)[1].split(",")]
+        assert names == [f[0] for f in cls._fields_] and C.sizeof(cls) == size, struct
+    for const, value in (("SRGD_ALPHA_MAX_TAPS", RZ.MAX_TAPS), ("SRGD_ALPHA_MAX_RATIO", RZ.MAX_RATIO), ("SRGD_ALPHA_MAX_SIDE", RZ.MAX_SIDE),
+                         ("SRGD_ALPHA_MAX_BLEED", AL.MAX_BLEED)):
+        assert re.search(r"#define " + const + r" +" + str(value) + r"\b", header), const
+    assert AL.MAX_BLEED == AC.MAX_BLEED == 64 and AL.MAX_SIDE == RZ.MAX_SIDE
+    assert os.path.exists(AL.LIB_PATH), "build the library first (python -m srgd_amd.build)"
+    assert _exports(AL.LIB_PATH) == ENTRIES
+    assert AL.lib().srgd_alpha_last_error() is not None                        # binds every prototype
+    for mod in (_lib, MX, EN, CS, BP, GD, SV, RZ):       # the eight other libraries keep their export tables
+        assert _exports(mod.LIB_PATH) == set(mod.PROTOTYPES), mod.__name__
+        assert not any(n.startswith("srgd_alpha") for n in _exports(mod.LIB_PATH)), mod.__name__
+        assert not set(AL.PROTOTYPES) & set(mod.PROTOTYPES)
+    for phrase in ("bit for bit", "A pass whose in == out is skipped; when both are skipped the plane is copied",
+                   "identical to the call on that image alone", "nothing is launched, nothing is written",
+                   "Asynchronous on `stream`; no allocation, no synchronisation", "known pixels never change",
+                   "(2 * s + c) / (2 * c) in integer division", "This library has no table code"):
+        assert phrase in re.sub(r"\s*\n \*\s*", " ", header), phrase
+    # the library has no table code of its own: no floating point in its source, and the tables come from srgd_amd.resize
+    source = open(os.path.join(ROOT, "srgd_amd", "csrc", "alpha.hip")).read()
+    assert not re.search(r"\b(double|float|ceil|sin)\b", source)
+
+
+def test_refusals_need_no_gpu():
+    # every refusal is decided on the host before anything is launched, so it can be checked here: -1 and a message
+    lib = AL.lib()
+    src, dst, tables, scratch, third = 1 << 30, 2 << 30, 3 << 30, 4 << 30, 5 << 30       # never dereferenced: a refused call launches nothing
+    big = 1 << 40
+
+    def plane(**kw):
+        return AL.AlphaPlane(**dict(dict(src_off=0, dst_off=0, tab_off=0, h_in=40, w_in=52, h_out=20, w_out=26, k_h=9, k_v=9), **kw))
+
+    def resize(planes=None, n=None, **kw):
+        planes = [plane()] if planes is None else planes
+        a = dict(dict(src=src, dst=dst, tables=tables, tables_bytes=big, scratch=scratch, scratch_bytes=big), **kw)
+        arr = (AL.AlphaPlane * len(planes))(*planes) if planes != "null" else None
+        rc = lib.srgd_alpha_resize_planes(a["src"], a["dst"], arr, len(planes) if n is None else n, a["tables"], a["tables_bytes"],
+                                          a["scratch"], a["scratch_bytes"], None)
+        return rc, lib.srgd_alpha_last_error().decode()
+    good = plane(src_off=16 * 400, dst_off=16 * 100, tab_off=16 * 3)
+    cases = {"null": [dict(src=None), dict(dst=None), dict(tables=None), dict(scratch=None), dict(planes="null", n=1)],
+             "n_planes": [dict(n=0), dict(n=-1)],
+             "bad size": [dict(planes=[plane(h_in=0)]), dict(planes=[plane(w_out=0)]), dict(planes=[plane(h_out=-3)]),
+                          dict(planes=[plane(w_in=16385, w_out=16385)]), dict(planes=[good, plane(w_in=0)])],
+             "ratio": [dict(planes=[plane(h_in=161)]), dict(planes=[plane(w_in=3)]), dict(planes=[plane(h_in=16, w_in=16, h_out=1, w_out=1)]),
+                       dict(planes=[good, good, plane(h_out=4)])],
+             "ksize": [dict(planes=[plane(k_h=0)]), dict(planes=[plane(k_v=50)]), dict(planes=[good, plane(k_v=-1)])],
+             "multiple of 16": [dict(planes=[plane(src_off=8)]), dict(planes=[plane(dst_off=17)]), dict(planes=[plane(tab_off=4)]),
+                                dict(planes=[good, plane(dst_off=24)])],
+             "outside [0, 2^36)": [dict(planes=[plane(src_off=-16)]), dict(planes=[plane(dst_off=1 << 36)]), dict(planes=[plane(tab_off=-16)])],
+             "scratch must be 16-byte aligned": [dict(scratch=scratch + 8)],
+             "tables must be 16-byte aligned": [dict(tables=tables + 4)],
+             "src and dst must be 16-byte aligned": [dict(src=src + 4), dict(dst=dst + 8)],
+             "tables_bytes": [dict(tables_bytes=4 * (26 * (2 + 9) + 20 * (2 + 9)) - 1), dict(planes=[plane(tab_off=64)], tables_bytes=64)],
+             "scratch_bytes": [dict(scratch_bytes=40 * 26 - 1), dict(planes=[good, plane()], scratch_bytes=2 * 40 * 26 - 16)],
+             "overlap": [dict(dst=src), dict(dst=src + 16 * 100), dict(planes=[plane(src_off=1 << 30)])]}
+    for phrase, calls in cases.items():
+        for kw in calls:
+            rc, msg = resize(**kw)
+            assert rc == -1 and phrase in msg and msg.startswith("srgd_alpha_resize_planes"), (phrase, kw, msg)
+    # a skipped pass takes no ksize: the copy and the one-pass forms pass the host checks up to the launch, which this test never
+    # reaches - so only the refusals are exercised here
+
+    def image(**kw):
+        return AL.AlphaImage(**dict(dict(rgb_off=0, a_off=0, rgba_off=0, h=7, w=5), **kw))
+
+    def pack(images=None, n=None, **kw):
+        images = [image()] if images is None else images
+        a = dict(dict(rgb=src, alpha=third, rgba=dst), **kw)
+        arr = (AL.AlphaImage * len(images))(*images) if images != "null" else None
+        rc = lib.srgd_alpha_pack_rgba(a["rgb"], a["alpha"], a["rgba"], arr, len(images) if n is None else n, None)
+        return rc, lib.srgd_alpha_last_error().decode()
+    cases = {"null": [dict(rgb=None), dict(alpha=None), dict(rgba=None), dict(images="null", n=1)],
+             "n_images": [dict(n=0), dict(n=-2)],
+             "bad size": [dict(images=[image(h=0)]), dict(images=[image(w=16385)]), dict(images=[image(), image(w=-1)])],
+             "multiple of 16": [dict(images=[image(rgb_off=8)]), dict(images=[image(a_off=4)]), dict(images=[image(), image(rgba_off=40)])],
+             "outside [0, 2^36)": [dict(images=[image(rgb_off=-16)]), dict(images=[image(a_off=1 << 36)]), dict(images=[image(rgba_off=-32)])],
+             "16-byte aligned": [dict(rgb=src + 4), dict(alpha=third + 1), dict(rgba=dst + 8)],
+             "overlap": [dict(rgba=src), dict(rgba=third), dict(rgba=src + 96), dict(images=[image(rgba_off=1 << 30)], rgba=src, rgb=dst)]}
+    for phrase, calls in cases.items():
+        for kw in calls:
+            rc, msg = pack(**kw)
+            assert rc == -1 and phrase in msg and msg.startswith("srgd_alpha_pack_rgba"), (phrase, kw, msg)
+
+    def bleed(images=None, n=None, **kw):
+        images = [image()] if images is None else images
+        a = dict(dict(rgba=src, rgb=dst, passes=3, scratch=scratch, scratch_bytes=big), **kw)
+        arr = (AL.AlphaImage * len(images))(*images) if images != "null" else None
+        rc = lib.srgd_alpha_bleed(a["rgba"], a["rgb"], arr, len(images) if n is None else n, a["passes"], a["scratch"], a["scratch_bytes"], None)
+        return rc, lib.srgd_alpha_last_error().decode()
+    cases = {"null": [dict(rgba=None), dict(rgb=None), dict(scratch=None), dict(images="null", n=1)],
+             "n_images": [dict(n=0)],
+             "passes": [dict(passes=-1), dict(passes=65)],
+             "bad size": [dict(images=[image(h=0)]), dict(images=[image(), image(w=16385)])],
+             "multiple of 16": [dict(images=[image(rgb_off=8)]), dict(images=[image(), image(rgba_off=40)])],
+             "outside [0, 2^36)": [dict(images=[image(rgb_off=-16)]), dict(images=[image(rgba_off=1 << 36)])],
+             "scratch must be 16-byte aligned": [dict(scratch=scratch + 4)],
+             "rgba and rgb must be 16-byte aligned": [dict(rgba=src + 4), dict(rgb=dst + 8)],
+             "scratch_bytes": [dict(scratch_bytes=2 * 144 - 1), dict(images=[image(), image()], scratch_bytes=4 * 144 - 16), dict(passes=1, scratch_bytes=0)],
+             "overlap": [dict(rgb=src), dict(rgb=src + 128), dict(images=[image(rgba_off=1 << 30)])]}
+    for phrase, calls in cases.items():
+        for kw in calls:
+            rc, msg = bleed(**kw)
+            assert rc == -1 and phrase in msg and msg.startswith("srgd_alpha_bleed"), (phrase, kw, msg)
+    assert AL.plane_scratch_bytes([(40, 52, 20, 26), (5, 7, 3, 2)]) == 40 * 26 + 16 and AL.bleed_scratch_bytes([(7, 5), (1, 1)]) == 2 * (144 + 16)
+
+
+def test_the_list_apis_refuse_bad_arguments_and_need_a_gpu():
+    import torch
+    rgba = torch.zeros(4, 5, 4, dtype=torch.uint8)
+    plane, rgb = torch.zeros(4, 5, dtype=torch.uint8), torch.zeros(16, 20, 3, dtype=torch.uint8)
+    for bad in (lambda: AL.bleed_on_device([rgba], 65), lambda: AL.bleed_on_device([rgba[:, :, :3]], 1), lambda: AL.bleed_on_device([], 1),
+                lambda: AL.bleed_on_device([rgba.float()], 1), lambda: AL.bleed_on_device(rgba, 1),
+                lambda: AL.resize_planes_on_device([plane], [(16, 20)], "box"), lambda: AL.resize_planes_on_device([plane], [(33, 20)]),
+                lambda: AL.resize_planes_on_device([plane], []), lambda: AL.resize_planes_on_device([rgb], [(16, 20)]),
+                lambda: AL.attach_alpha_on_device([rgb], [plane, plane]), lambda: AL.attach_alpha_on_device([rgb], [plane], scale=9),
+                lambda: AL.attach_alpha_on_device([rgb[:1]], [plane]), lambda: AL.attach_alpha_on_device([rgb], [plane], filter="box"),
+                lambda: AL.pack_rgba_on_device([rgb], [plane])):
+        with pytest.raises(ValueError):
+            bad()
+    if not torch.cuda.is_available():                                         # no CPU fallback
+        for call in (lambda: AL.bleed_on_device([rgba], 1), lambda: AL.resize_planes_on_device([plane], [(16, 20)]),
+                     lambda: AL.attach_alpha_on_device([rgb], [plane])):
+            with pytest.raises(_lib.SrgdHipError):
+                call()
+
+
+@pytest.fixture(scope="module")
+def table_of_resources():
+    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
+        pytest.skip("hipcc not available")
+    return kernel_table(os.path.join(ROOT, "srgd_amd", "csrc", "alpha.hip"))
+
+
+def test_the_kernels_do_not_spill(table_of_resources):
+    rows = {r["name"]: r for r in table_of_resources}
+    assert set(rows) == {"alpha_plane_horizontal_kernel", "alpha_plane_vertical_kernel", "alpha_pack_kernel", "alpha_bleed_pass_kernel",
+                         "alpha_bleed_store_kernel"}
+    for name, r in rows.items():
+        assert r["spill"] == 0 and r["scratch"] == 0, f"{name} spills ({r['spill']} VGPRs, {r['scratch']} B scratch)"
+        assert 0 < r["vgpr"] + max(r["agpr"], 0) <= 64, f"{name} uses {r['vgpr']} + {r['agpr']} registers"      # 8 waves per SIMD
+    assert rows["alpha_plane_horizontal_kernel"]["lds"] == 16 * 564 + 4 * 64 * 49 + 4 * 128 + 16 * 64
+    assert rows["alpha_plane_vertical_kernel"]["lds"] == 4 * 16 * 49 + 4 * 32
+    assert all(rows[name]["lds"] == 0 for name in ("alpha_pack_kernel", "alpha_bleed_pass_kernel", "alpha_bleed_store_kernel"))
+    assert AC.H_TILE == (64, 16) and AC.V_TILE == (256, 16)
