@@ -121,7 +121,7 @@ typedef struct srgd_step_scalars { /* fp32 values of model.py:3127-3134,:3168 fo
   float alpha, sigma, alpha_next, c, one_minus_c;
   float noise_scale; /* sqrt(sigma_next^2 * c) */
   float sigma_next;  /* sqrt(sigmoid(-log_snr(t'))) for the odd-step ring (model.py:3395) */
-  float reserved;
+  float no_clamp;    /* 0: x0 is clamped to [-1, 1] (model.py:3163); != 0: it is not - the caller thresholds it (srgd_threshold.h) */
 } srgd_step_scalars;
 
 typedef struct srgd_sampler_geometry { /* ints of get_coord_and_pad / get_coords / get_area (model.py:116-179) */

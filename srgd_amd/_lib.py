@@ -32,7 +32,7 @@ class UnetConfig(C.Structure):
 class StepScalars(C.Structure):
     _fields_ = [("alpha", C.c_float), ("sigma", C.c_float), ("alpha_next", C.c_float), ("c", C.c_float),
                 ("one_minus_c", C.c_float), ("noise_scale", C.c_float), ("sigma_next", C.c_float),
-                ("reserved", C.c_float)]
+                ("no_clamp", C.c_float)]
 
 
 class EdmScalars(C.Structure):

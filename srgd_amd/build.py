@@ -1,4 +1,4 @@
-"""Build ``libsrgd_hip.so`` (the C-ABI engine, include/srgd_hip.h), ``libsrgd_metrics.so`` (include/srgd_metrics.h), ``libsrgd_ensemble.so`` (include/srgd_ensemble.h), ``libsrgd_consistency.so`` (include/srgd_consistency.h), ``libsrgd_backproject.so`` (include/srgd_backproject.h), ``libsrgd_guidance.so`` (include/srgd_guidance.h), ``libsrgd_solver.so`` (include/srgd_solver.h), ``libsrgd_resize.so`` (include/srgd_resize.h) and ``libsrgd_alpha.so`` (include/srgd_alpha.h) in-tree with hipcc for gfx950.
+"""Build ``libsrgd_hip.so`` (the C-ABI engine, include/srgd_hip.h), ``libsrgd_metrics.so`` (include/srgd_metrics.h), ``libsrgd_ensemble.so`` (include/srgd_ensemble.h), ``libsrgd_consistency.so`` (include/srgd_consistency.h), ``libsrgd_backproject.so`` (include/srgd_backproject.h), ``libsrgd_guidance.so`` (include/srgd_guidance.h), ``libsrgd_solver.so`` (include/srgd_solver.h), ``libsrgd_resize.so`` (include/srgd_resize.h), ``libsrgd_alpha.so`` (include/srgd_alpha.h) and ``libsrgd_threshold.so`` (include/srgd_threshold.h) in-tree with hipcc for gfx950.
 
 hipcc cross-compiles without a GPU, so this runs in the build container; the resulting
 ``srgd_amd/libsrgd_hip.so`` travels to the GPU box with the tree (git-ignored, not
@@ -33,8 +33,11 @@ RESIZE_LIB = os.path.join(HERE, "libsrgd_resize.so")    # include/srgd_resize.h:
 RESIZE_SOURCES = ["resize.hip"]
 ALPHA_LIB = os.path.join(HERE, "libsrgd_alpha.so")    # include/srgd_alpha.h: a library of its own, from ALPHA_SOURCES
 ALPHA_SOURCES = ["alpha.hip"]
-# resize.hip's host code reproduces Pillow's double-precision tables: no fused multiply-adds in it (its kernels are integer code)
-EXTRA_FLAGS = {"resize.hip": ["-ffp-contract=off"]}
+THRESHOLD_LIB = os.path.join(HERE, "libsrgd_threshold.so")    # include/srgd_threshold.h: a library of its own, from THRESHOLD_SOURCES
+THRESHOLD_SOURCES = ["threshold.hip"]
+# resize.hip's host code reproduces Pillow's double-precision tables: no fused multiply-adds in it (its kernels are integer code);
+# threshold.hip's definition is in separate fp32 multiplications and additions, on the host and in its kernels
+EXTRA_FLAGS = {"resize.hip": ["-ffp-contract=off"], "threshold.hip": ["-ffp-contract=off"]}
 SOURCES = ["conv_igemm.hip", "conv3x3_bf16.hip", "conv3x3_split.hip", "conv3x3_mx2.hip", "conv1x1_split.hip", "conv1x1_bf16.hip", "conv3x3_mxfp8.hip", "conv1x1_mxfp8.hip", "quant_mxfp8.hip", "norm_act.hip", "attention.hip", "linattn_fused.hip", "linattn_fused256.hip", "cond.hip", "sampler.hip", "imageio.hip", "engine.hip", "kernel_api.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function", "-Wno-unused-result", "-Wno-unused-value",
          "-fno-gpu-rdc", "-DNDEBUG", "-fvisibility=hidden"]
@@ -63,7 +66,7 @@ def _digest() -> str:
 def build(force: bool = False, verbose: bool = False) -> str:
     stamp = os.path.join(OBJ_DIR, "stamp")
     digest = _digest()
-    if not force and os.path.exists(LIB) and os.path.exists(METRICS_LIB) and os.path.exists(ENSEMBLE_LIB) and os.path.exists(CONSISTENCY_LIB) and os.path.exists(BACKPROJECT_LIB) and os.path.exists(GUIDANCE_LIB) and os.path.exists(SOLVER_LIB) and os.path.exists(RESIZE_LIB) and os.path.exists(ALPHA_LIB) and os.path.exists(stamp) and open(stamp).read() == digest:
+    if not force and os.path.exists(LIB) and os.path.exists(METRICS_LIB) and os.path.exists(ENSEMBLE_LIB) and os.path.exists(CONSISTENCY_LIB) and os.path.exists(BACKPROJECT_LIB) and os.path.exists(GUIDANCE_LIB) and os.path.exists(SOLVER_LIB) and os.path.exists(RESIZE_LIB) and os.path.exists(ALPHA_LIB) and os.path.exists(THRESHOLD_LIB) and os.path.exists(stamp) and open(stamp).read() == digest:
         return LIB
     os.makedirs(OBJ_DIR, exist_ok=True)
     hipcc = _hipcc()
@@ -79,7 +82,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
         return obj
 
     with ThreadPoolExecutor(max_workers=min(6, os.cpu_count() or 1)) as ex:
-        objs = list(ex.map(compile_one, SOURCES + METRICS_SOURCES + ENSEMBLE_SOURCES + CONSISTENCY_SOURCES + BACKPROJECT_SOURCES + GUIDANCE_SOURCES + SOLVER_SOURCES + RESIZE_SOURCES + ALPHA_SOURCES))
+        objs = list(ex.map(compile_one, SOURCES + METRICS_SOURCES + ENSEMBLE_SOURCES + CONSISTENCY_SOURCES + BACKPROJECT_SOURCES + GUIDANCE_SOURCES + SOLVER_SOURCES + RESIZE_SOURCES + ALPHA_SOURCES + THRESHOLD_SOURCES))
+    threshold_objs = objs[len(objs) - len(THRESHOLD_SOURCES):]
+    objs = objs[:len(objs) - len(THRESHOLD_SOURCES)]
     alpha_objs = objs[len(objs) - len(ALPHA_SOURCES):]
     objs = objs[:len(objs) - len(ALPHA_SOURCES)]
     resize_objs = objs[len(objs) - len(RESIZE_SOURCES):]
@@ -158,6 +163,13 @@ def build(force: bool = False, verbose: bool = False) -> str:
                         *alpha_objs], capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"link of the alpha library failed:\n{r.stdout}\n{r.stderr}")
+    tvers = os.path.join(OBJ_DIR, "exports_threshold.map")
+    with open(tvers, "w") as f:
+        f.write("{ global: srgd_threshold*; local: *; };\n")
+    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", f"-Wl,--version-script={tvers}", "-o", THRESHOLD_LIB,
+                        *threshold_objs], capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"link of the threshold library failed:\n{r.stdout}\n{r.stderr}")
     with open(stamp, "w") as f:
         f.write(digest)
     return LIB

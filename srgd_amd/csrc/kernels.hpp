@@ -231,7 +231,7 @@ int linear_rows(const float* x, int x_stride, const float* W, const float* b, fl
 struct StepScalars {       // fp32 values computed by the host exactly as the reference does
   float alpha, sigma, alpha_next, c, one_minus_c, noise_scale;   // noise_scale = sqrt(sigma_next^2 * c), 0 on the last step
   float sigma_next;        // for the ring re-noise (q_sample(0, t'))
-  float pad;
+  float no_clamp;          // != 0: x0 is not clamped to [-1, 1] (the caller thresholds it: srgd_amd/csrc/threshold.hip)
 };
 struct EdmScalars {        // == srgd_edm_scalars (include/srgd_hip.h); fp32 values computed by the host as the reference does
   float s_noise, hat_coef;           // img_hat = img + hat_coef * (s_noise * z)            (model.py:2386-2389)

@@ -202,7 +202,7 @@ __global__ __launch_bounds__(256) void final_step_kernel(FinalStepArgs a, TileBa
   for (int c = 0; c < 3; ++c) {
     const float xt = a.img[c * plane + o];
     float x0 = (xt - sc.sigma * eps[c][threadIdx.x]) / sc.alpha;                // model.py:3160
-    x0 = clamp_keep_nan(x0, -1.0f, 1.0f);                                       // :3163
+    if (sc.no_clamp == 0.0f) x0 = clamp_keep_nan(x0, -1.0f, 1.0f);              // :3163
     float mean = sc.alpha_next * (xt * sc.one_minus_c / sc.alpha + sc.c * x0);  // :3164
     if (a.noise) mean += sc.noise_scale * a.noise[((long)tl * 3 + c) * per_tile + r];   // :3187-3188
     a.img[c * plane + o] = mean;

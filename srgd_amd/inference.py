@@ -41,6 +41,7 @@ from .model import ConditionalElucidatedDiffusionSR, get_model
 from .resize import FILTERS as OUTSCALE_FILTERS
 from .resize import check_filter, check_outscale, outscale_size
 from .solver import check_sampler
+from .threshold import check_percentile
 
 logger = logging.getLogger("srgd_amd")
 
@@ -137,6 +138,13 @@ def parse_args(argv=None):
     p.add_argument("--step_spacing", choices=["time", "logsnr"], default="time",
                    help="where the --num_sample_steps steps end: time (default) is the reference's uniform grid in t, whose last steps "
                         "jump several units of log-SNR; logsnr is uniform in the log-SNR itself (engine extension)")
+    p.add_argument("--dynamic_threshold", type=float, default=0.0, metavar="P",
+                   help="dynamic thresholding inside the DDPM sampling loop, percentile P in (0, 1] (0, the default: off; 0.995 is "
+                        "Imagen's choice): the steps are taken without the static clamp of the predicted clean image to [-1, 1]; "
+                        "after every step the GPU takes per image s = max(1, the exact P-quantile of the prediction's magnitudes), "
+                        "clips the prediction to [-s, s] and divides it by s - for guidance scales above 1 (--cond_scale, "
+                        "--class_cond_scale), whose overshoot a hard clamp turns into saturated regions; one small batched GPU "
+                        "call per step (engine extension)")
     p.add_argument("--outscale", type=float, default=4.0, metavar="S",
                    help="write every file at S times the size of its input instead of 4 times, S in [0.5, 32] (4, the default: off): the "
                         "x4 output as it would have been saved - after --color_fix and --back_project - is resampled on the GPU to "
@@ -178,6 +186,8 @@ def parse_args(argv=None):
         check_sampler(args.sampler, args.eta, args.step_spacing)
     except ValueError as e:
         raise SystemExit(f"--sampler / --eta / --step_spacing: {e}")
+    if not 0.0 <= args.dynamic_threshold <= 1.0:            # NaN fails both comparisons
+        raise SystemExit(f"--dynamic_threshold: P must be in [0, 1], got {args.dynamic_threshold}")
     if not 0.0 <= args.consistency_guidance <= 1.0:         # NaN fails both comparisons
         raise SystemExit(f"--consistency_guidance: G must be in [0, 1], got {args.consistency_guidance}")
     if args.consistency_guidance_start_steps < 0:
@@ -259,6 +269,12 @@ def _guidance_kw(consistency_guidance, consistency_guidance_start_steps=0):
     if not consistency_guidance:
         return {}
     return {"consistency_guidance": consistency_guidance, "consistency_guidance_start_steps": consistency_guidance_start_steps}
+
+
+def _threshold_kw(dynamic_threshold):
+    """``tiled_sample``'s ``dynamic_threshold`` keyword for a percentile > 0; nothing for 0 / None (the call a run without the flag
+    makes)."""
+    return {"dynamic_threshold": dynamic_threshold} if dynamic_threshold else {}
 
 
 def _sampler_kw(sampler="ddpm", eta=None, step_spacing="time"):
@@ -464,7 +480,7 @@ def sr_target_image(image, sr_model, scale=4, batch_size=8, test_label=2, cond_s
                     class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0,
                     num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None, reference=None,
                     crop_border=4, back_project=0, consistency_guidance=0.0,
-                    consistency_guidance_start_steps=0, sampler="ddpm", eta=None, step_spacing="time"):
+                    consistency_guidance_start_steps=0, sampler="ddpm", eta=None, step_spacing="time", dynamic_threshold=None):
     """``reference`` (engine extension; here and in the three group forms below): the ground truth as a uint8 ``[H,W,3]`` tensor (a
     list of one per image in the group forms).  The return value is then ``(image(s), metric dicts)``: PSNR / SSIM of every image as
     saved, with ``crop_border`` pixels cut from every side (srgd_amd.metrics)."""
@@ -483,7 +499,7 @@ def sr_target_image(image, sr_model, scale=4, batch_size=8, test_label=2, cond_s
                                        num_sample_steps=num_sample_steps, amp=enable_amp, **_color_fix_kw(color_fix),
                                        **_reference_kw(reference, crop_border), **_back_project_kw(back_project),
                                        **_guidance_kw(consistency_guidance, consistency_guidance_start_steps),
-                                       **_sampler_kw(sampler, eta, step_spacing))
+                                       **_sampler_kw(sampler, eta, step_spacing), **_threshold_kw(dynamic_threshold))
     output, quality = _split_quality(output, reference)
     sr_img = unit_tensor_to_pil_on_device(output[0])
     assert sr_img.size == (width * 4, height * 4)
@@ -494,7 +510,7 @@ def sr_target_images(images, sr_model, scale=4, batch_size=8, test_label=2, cond
                      class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0,
                      num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None, reference=None,
                      crop_border=4, back_project=0, consistency_guidance=0.0,
-                     consistency_guidance_start_steps=0, sampler="ddpm", eta=None, step_spacing="time"):
+                     consistency_guidance_start_steps=0, sampler="ddpm", eta=None, step_spacing="time", dynamic_threshold=None):
     """``sr_target_image`` for several same-sized images in lock-step (engine extension): one ``tiled_sample`` call on a
     ``[B,3,H,W]`` condition.  Each image is sampled exactly as it would be alone after the reference's per-image
     ``seed_everything(seed)`` (inference.py:73) - bit-identical outputs - while their tiles fill the U-Net launches.
@@ -514,7 +530,7 @@ def sr_target_images(images, sr_model, scale=4, batch_size=8, test_label=2, cond
                                        num_sample_steps=num_sample_steps, amp=enable_amp, **_color_fix_kw(color_fix),
                                        **_reference_kw(reference, crop_border), **_back_project_kw(back_project),
                                        **_guidance_kw(consistency_guidance, consistency_guidance_start_steps),
-                                       **_sampler_kw(sampler, eta, step_spacing))
+                                       **_sampler_kw(sampler, eta, step_spacing), **_threshold_kw(dynamic_threshold))
     output, quality = _split_quality(output, reference)
     outs = [unit_tensor_to_pil_on_device(o) for o in output]
     assert all(o.size == (width * 4, height * 4) for o in outs)
@@ -525,7 +541,7 @@ def sr_target_images_mixed(images, sr_model, scale=4, batch_size=8, test_label=2
                            class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0,
                            num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None, reference=None,
                            crop_border=4, back_project=0, consistency_guidance=0.0,
-                           consistency_guidance_start_steps=0, sampler="ddpm", eta=None, step_spacing="time"):
+                           consistency_guidance_start_steps=0, sampler="ddpm", eta=None, step_spacing="time", dynamic_threshold=None):
     """``sr_target_image`` for several images of any sizes in lock-step (engine extension): one ``tiled_sample`` call on a list
     of conditions.  Each image comes out bit-identical to its own ``sr_target_image`` run (with its own label where
     ``test_label`` is a sequence of one label per image)."""
@@ -542,7 +558,7 @@ def sr_target_images_mixed(images, sr_model, scale=4, batch_size=8, test_label=2
                                        num_sample_steps=num_sample_steps, amp=enable_amp, **_color_fix_kw(color_fix),
                                        **_reference_kw(reference, crop_border), **_back_project_kw(back_project),
                                        **_guidance_kw(consistency_guidance, consistency_guidance_start_steps),
-                                       **_sampler_kw(sampler, eta, step_spacing))
+                                       **_sampler_kw(sampler, eta, step_spacing), **_threshold_kw(dynamic_threshold))
     output, quality = _split_quality(output, reference)
     outs = [unit_tensor_to_pil_on_device(o[0]) for o in output]
     assert all(o.size == (im.size[0] * 4, im.size[1] * 4) for o, im in zip(outs, images))
@@ -553,7 +569,7 @@ def sr_target_images_seeded(images, seeds, sr_model, scale=4, batch_size=8, test
                             class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0,
                             num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None,
                             reference=None, crop_border=4, back_project=0, consistency_guidance=0.0,
-                            consistency_guidance_start_steps=0, sampler="ddpm", eta=None, step_spacing="time"):
+                            consistency_guidance_start_steps=0, sampler="ddpm", eta=None, step_spacing="time", dynamic_threshold=None):
     """``sr_target_images_mixed`` with one noise seed per image (engine extension, ``tiled_sample(seeds=...)``): image i comes out
     bit-identical to its own ``sr_target_image`` run with ``seed=seeds[i]``; an image may appear several times with different
     seeds (each PIL image is upsampled once).  ``seed`` seeds the process as the other entry points do and is not a noise seed."""
@@ -573,7 +589,7 @@ def sr_target_images_seeded(images, seeds, sr_model, scale=4, batch_size=8, test
                                        num_sample_steps=num_sample_steps, amp=enable_amp, seeds=list(seeds),
                                        **_color_fix_kw(color_fix), **_reference_kw(reference, crop_border), **_back_project_kw(back_project),
                                        **_guidance_kw(consistency_guidance, consistency_guidance_start_steps),
-                                       **_sampler_kw(sampler, eta, step_spacing))
+                                       **_sampler_kw(sampler, eta, step_spacing), **_threshold_kw(dynamic_threshold))
     output, quality = _split_quality(output, reference)
     outs = [unit_tensor_to_pil_on_device(o[0]) for o in output]
     assert all(o.size == (im.size[0] * 4, im.size[1] * 4) for o, im in zip(outs, images))
@@ -619,8 +635,12 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
                            samples=1, color_fix=None, reference_dir=None, crop_border=4, metrics_name="metrics.json", ensemble=False,
                            ensemble_name="ensemble.json", consistency=False, consistency_name="consistency.json", back_project=0,
                            consistency_guidance=0.0, consistency_guidance_start_steps=0, sampler="ddpm", eta=None,
-                           step_spacing="time", outscale=None, outscale_filter="bicubic", alpha="drop", alpha_bleed=0):
-    """``alpha`` / ``alpha_bleed`` (``--alpha keep``, ``--alpha_bleed N``): with "keep" every input is opened with its alpha plane
+                           step_spacing="time", outscale=None, outscale_filter="bicubic", alpha="drop", alpha_bleed=0,
+                           dynamic_threshold=0.0):
+    """``dynamic_threshold`` (``--dynamic_threshold P``): P > 0 is handed by keyword to whichever ``sr_target_image*`` function samples
+    a group (``tiled_sample(dynamic_threshold=P)``: percentile clipping of the predicted clean image inside the sampling loop); with 0
+    the keyword is not passed at all.  A P outside [0, 1] is a ``ValueError`` before anything is sampled.
+    ``alpha`` / ``alpha_bleed`` (``--alpha keep``, ``--alpha_bleed N``): with "keep" every input is opened with its alpha plane
     (``try_open_image_with_alpha``); an input that has one is, with N > 0, bled once per opened file (``bleed_on_device``: the bled RGB
     image replaces the input for everything below, the K samples of a file share it), sampled and measured as RGB like every other
     input, and last of all in ``flush()`` - after the ``outscale`` block - the outputs of such inputs get their alpha in one batched
@@ -677,8 +697,10 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
               class_guidance_start_steps=class_guidance_start_steps, generation_start_steps=generation_start_steps,
               num_sample_steps=num_sample_steps, enable_amp=enable_amp, interpolation=interpolation, seed=seed,
               color_fix=None if color_fix in (None, "none") else color_fix, **_back_project_kw(back_project),
-              **_guidance_kw(consistency_guidance, consistency_guidance_start_steps), **_sampler_kw(sampler, eta, step_spacing))
+              **_guidance_kw(consistency_guidance, consistency_guidance_start_steps), **_sampler_kw(sampler, eta, step_spacing),
+              **_threshold_kw(dynamic_threshold))
     check_sampler(sampler or "ddpm", eta, step_spacing or "time")
+    check_percentile(dynamic_threshold)
     outscale, outscale_filter = check_outscale(outscale), check_filter(outscale_filter)
     if ensemble and outscale is not None:
         raise ValueError("ensemble: not together with outscale")
@@ -976,7 +998,7 @@ def main(argv=None):
                            consistency_guidance_start_steps=args.consistency_guidance_start_steps,
                            sampler=args.sampler, eta=args.eta, step_spacing=args.step_spacing,
                            outscale=args.outscale, outscale_filter=args.outscale_filter, alpha=args.alpha,
-                           alpha_bleed=args.alpha_bleed,
+                           alpha_bleed=args.alpha_bleed, dynamic_threshold=args.dynamic_threshold,
                            consistency_name="consistency.json" if world == 1 else f"consistency_rank{rank}.json")
 
 

@@ -33,6 +33,9 @@ from .guidance import records as guidance_records
 from .guidance import scratch_bytes as guidance_scratch_bytes
 from .solver import check_sampler, history_step_flat, history_weights, is_default, step_coefficients
 from .solver import records as solver_records
+from .threshold import check_percentile, threshold_step_flat
+from .threshold import records as threshold_records
+from .threshold import scratch_bytes as threshold_scratch_bytes
 from .lanes import StepLanes, lanes_setting_from_env, lanes_wanted
 
 __all__ = ["get_coord_and_pad", "get_coords", "get_area", "beta_linear_log_snr", "ConditionalSRUnet",
@@ -107,7 +110,8 @@ def _schedule(num_steps: int, sampler: str = "ddpm", eta: Optional[float] = None
     "ddim" (``eta`` in [0, 1]) and "dpmpp2m" (eta 0) replace ``one_minus_c``, ``c`` and ``noise_scale`` - the three scalars the step
     kernel reads independently - by fp32(A alpha / alpha_next), fp32(B / alpha_next) and fp32(S) of srgd_amd.solver's float64
     ``step_coefficients``, so that the kernel's ``alpha_next * (x_t * one_minus_c / alpha + c * x0) + noise_scale * z`` is
-    ``A x_t + B x0 + S z``; ``alpha_next * c`` is then B, the weight of x0 the guidance reads."""
+    ``A x_t + B x0 + S z``; ``alpha_next * c`` is then B, the weight of x0 the guidance reads.  ``no_clamp`` stays 0 here: the
+    clamped step (``_schedule_of`` sets it on every step of a run with the dynamic threshold)."""
     times = torch.linspace(1.0, 0.0, num_steps + 1)
     levels = _log_snr_levels(num_steps, step_spacing) if step_spacing != "time" else None
     scalars, log_snrs = [], []
@@ -302,6 +306,41 @@ class _GuidedRun:
         mean_weight = float(torch.tensor(scalars[i].alpha_next, dtype=torch.float32) * torch.tensor(scalars[i].c, dtype=torch.float32))
         guide_step_flat(img.view(-1), x_start.view(-1), cond01.view(-1), self.recs, self.weight, self.weight * mean_weight,
                         self.scratch)
+
+
+class _ThresholdRun:
+    """The dynamic threshold of one DDPM run (srgd_amd.threshold): the record arrays of both step parities - the statistics box is
+    the crop box, the update box what the step wrote: the whole canvas on even steps, the inner box on odd ones - the scratch and the
+    [steps, images] array of s are made once; ``step`` is one batched call on the run's canvases after step i, before the guidance and
+    the history calls: x_start = clip(x_start, -s, s) / s, img += fp32(alpha_next_i * c_i) * (the change) (the posterior mean is
+    linear in x_start: reference model.py:3164)."""
+
+    def __init__(self, q, images, max_steps, dev):
+        """``images``: [(canvas_off, Hp, Wp, crop top, crop left, H, W, inner top, inner left, inner height, inner width)]."""
+        self.q = q
+        self.recs = (threshold_records([m[:7] + (0, 0, m[1], m[2]) for m in images]), threshold_records(images))
+        self.scratch = torch.empty(threshold_scratch_bytes(len(images)), device=dev, dtype=torch.uint8)
+        self.s = torch.empty(max(max_steps, 1), len(images), device=dev, dtype=torch.float32)
+        self.calls = 0
+
+    def step(self, i, scalars, img, x_start):
+        mean_weight = float(torch.tensor(scalars[i].alpha_next, dtype=torch.float32) * torch.tensor(scalars[i].c, dtype=torch.float32))
+        threshold_step_flat(img.view(-1), x_start.view(-1), self.recs[i % 2], self.q, mean_weight, self.s[self.calls], self.scratch)
+        self.calls += 1
+
+    def log(self):
+        """[executed steps, images] fp32 on the CPU: every call's s."""
+        return self.s[:self.calls].cpu()
+
+
+def _schedule_of(num_sample_steps, solver, no_clamp=False):
+    """The run's step table and log-SNR list: ``_schedule``'s, called as it always was.  ``no_clamp`` sets the field of that name on
+    every step: the step kernel then leaves x0 unclamped, for the dynamic threshold's call that follows it."""
+    scalars, log_snrs = _schedule(num_sample_steps) if solver is None else _schedule(num_sample_steps, *solver)
+    if no_clamp:
+        for s in scalars:
+            s.no_clamp = 1.0
+    return scalars, log_snrs
 
 
 def _start_log_snr(generation_start_steps, num_sample_steps, step_spacing):
@@ -525,7 +564,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                      generation_start_steps=0, num_sample_steps=None, with_images=False, with_x0_images=False,
                      start_white_noise=True, amp=False, precision=None, seeds=None, color_fix=None, reference=None,
                      crop_border=4, back_project=0, consistency_guidance=0.0, consistency_guidance_start_steps=0,
-                     sampler="ddpm", eta=None, step_spacing="time"):
+                     sampler="ddpm", eta=None, step_spacing="time", dynamic_threshold=None, threshold_log=None):
         """Tiled CFG-DDPM sampling (reference model.py:3288-3413).
 
         ``amp`` is accepted and ignored exactly as in the reference (which always computes fp32); the engine
@@ -588,8 +627,25 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
         ``step_spacing="logsnr"`` places the N + 1 step ends uniformly in the log-SNR instead of in t, which is what makes few
         steps worth taking; ``generation_start_steps = g`` then starts from level g of that list.  Bad values: ``ValueError``
         before anything is sampled.  dpmpp2m is not available on a canvas sharded over ranks (its history would have to travel
-        with the tile exchange); ddim and ``step_spacing`` only change tables and are."""
+        with the tile exchange); ddim and ``step_spacing`` only change tables and are.
+
+        ``dynamic_threshold`` (engine-only keyword, absent upstream): a percentile P; None / 0 (default): nothing is loaded,
+        allocated or launched, the run is byte for byte what it is without the keyword.  Otherwise P is rounded to fp32 and must lie
+        in (0, 1]: the steps are taken without the static clamp of the predicted clean image to [-1, 1], and after every executed step
+        - before the guidance and the history calls, whose corrections it completes - one batched call on the GPU (srgd_amd.threshold,
+        include/srgd_threshold.h) takes per image s = max(1, the P-quantile of |x_start| inside the crop box), an exact order statistic,
+        clips x_start to [-s, s] and divides it by s inside what the step wrote, and adds alpha_next_i c_i times the change to img
+        (Imagen's dynamic thresholding: guidance scales above 1 overshoot, and the static clamp saturates whole regions).
+        ``with_x0_images`` shows the thresholded predictions.  ``threshold_log``: a list that receives one CPU tensor
+        [executed steps, images] of s.  Every image of a group is bit-identical to its solo run.  Combines with every sampler, step
+        spacing, ``consistency_guidance``, ``generation_start_steps``, seeds and labels.  Not available on a canvas sharded over
+        ranks.  Picture quality on trained weights is not measured."""
         sampler, eta, step_spacing = check_sampler(sampler, eta, step_spacing)
+        threshold = check_percentile(dynamic_threshold)
+        if threshold is not None and self.canvas_group is not None:
+            raise NotImplementedError("dynamic_threshold on a canvas sharded over ranks (canvas_group)")
+        if threshold_log is not None and not isinstance(threshold_log, list):
+            raise ValueError("threshold_log: None or a list")
         solver = None if is_default(sampler, eta, step_spacing) else (sampler, eta, step_spacing)
         color_fix = check_mode(color_fix)
         back_project = _back_project_steps(back_project, condition_x)
@@ -621,7 +677,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                                              guidance_start_steps, class_cond_scale, class_guidance_start_steps,
                                              generation_start_steps, num_sample_steps, start_white_noise, precision, seeds=seeds,
                                              color_fix=color_fix, reference=reference, crop_border=crop_border, back_project=back_project,
-                                             guidance=guidance, solver=solver)
+                                             guidance=guidance, solver=solver, threshold=threshold, threshold_log=threshold_log)
             if reference is not None:
                 return (outs[0] if as_list else torch.cat(outs[0], 0)), outs[1]
             return outs if as_list else torch.cat(outs, 0)
@@ -639,7 +695,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                                              guidance_start_steps, class_cond_scale, class_guidance_start_steps,
                                              generation_start_steps, num_sample_steps, start_white_noise, precision,
                                              color_fix=color_fix, reference=reference, crop_border=crop_border, back_project=back_project,
-                                             guidance=guidance, solver=solver)
+                                             guidance=guidance, solver=solver, threshold=threshold, threshold_log=threshold_log)
         if cond_scale != 1.0 and class_cond_scale != 1.0:
             raise NotImplementedError("Currently, you cannot specify both cond_scale and class_cond_scale at the same time.")
         if tile_size != 256 or tile_stride != 256:
@@ -671,7 +727,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
         (sl, st_, sr, sb), _ = get_area(coords1, hp, wp)
         geo = SamplerGeometry(H=h, W=w, Hp=hp, Wp=wp, left=left, top=top, inner_l=sl, inner_t=st_, inner_r=sr,
                               inner_b=sb, tile=tile_size, n_even=len(coords0), n_odd=len(coords1), n_images=batch)
-        scalars, log_snrs = _schedule(num_sample_steps) if solver is None else _schedule(num_sample_steps, *solver)
+        scalars, log_snrs = _schedule_of(num_sample_steps, solver, no_clamp=threshold is not None)
 
         cond01 = condition_x.to(dev, torch.float32).contiguous()
         cond_canvas = torch.empty(batch, 3, hp, wp, device=dev, dtype=torch.float32)
@@ -691,9 +747,13 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
             img = _host_randn(self.host_generator, 1, 3, hp, wp).to(dev).repeat(batch, 1, 1, 1)   # reference draw #1 (model.py:3311)
         else:
             img = eng.randn_(torch.empty(1, 3, hp, wp, device=dev), self.device_noise_seed, 0).repeat(batch, 1, 1, 1)
-        x_start = img.clone() if with_x0_images or guidance is not None or sampler == "dpmpp2m" else None
+        x_start = img.clone() if with_x0_images or guidance is not None or sampler == "dpmpp2m" or threshold is not None else None
         image_list = [img[:, :, top:bottom, left:right].clone().cpu()] if with_images else None
         x0_image_list = [img[:, :, top:bottom, left:right].clone().cpu()] if with_x0_images else None
+        thresholded = None
+        if threshold is not None:
+            thresholded = _ThresholdRun(threshold, [(b * 3 * hp * wp, hp, wp, top, left, h, w, st_, sl, sb - st_, sr - sl)
+                                                    for b in range(batch)], num_sample_steps - generation_start_steps, dev)
         guided = None
         if guidance is not None:            # x_start is laid out like img: final_step_kernel addresses both alike
             guided = _GuidedRun(guidance, [(b * 3 * hp * wp, b * 3 * h * w, hp, wp, top, left, h, w) for b in range(batch)], dev)
@@ -741,7 +801,9 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                 from .parallel import sharded_step
                 sharded_step(eng, self.canvas_group, i, n_tiles * batch, img, cond_canvas, x_start, noise_tiles,
                              noise_canvas, passes, kind, scale, sub_batch, self.device_noise_seed)
-            if guided is not None:          # the lanes have joined the main stream: a plain launch after the step's
+            if thresholded is not None:     # the lanes have joined the main stream: plain launches after the step's
+                thresholded.step(i, scalars, img, x_start)
+            if guided is not None:          # after the threshold: it corrects the completed prediction
                 guided.step(i, scalars, img, x_start, cond01)
             if history is not None:         # after the guidance: the history holds the corrected predictions
                 history.step(i, img, x_start)
@@ -752,6 +814,8 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
 
         out = torch.empty(batch, 3, h, w, device=dev, dtype=torch.float32)
         eng.sampler_end(img, out)
+        if thresholded is not None and threshold_log is not None:
+            threshold_log.append(thresholded.log())
         if color_fix is not None:           # in place on the [B,3,H,W] result; the trajectories above stay raw
             color_fix_flat(out, cond01, [b * 3 * h * w for b in range(batch)], [(h, w)] * batch, color_fix)
         if back_project is not None:        # after the colour fix, in place: the image as it will be saved
@@ -766,7 +830,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
     def _tiled_sample_images(self, batch_size, tile_size, conds, class_label, cond_scale, guidance_start_steps,
                              class_cond_scale, class_guidance_start_steps, generation_start_steps, num_sample_steps,
                              start_white_noise, precision, seeds=None, color_fix=None, reference=None, crop_border=4,
-                             back_project=None, guidance=None, solver=None):
+                             back_project=None, guidance=None, solver=None, threshold=None, threshold_log=None):
         """Mixed-size lock-step (srgd_sampler_begin_images): every image keeps its own canvas, crop box, padding, inner box and
         tile grids; a step's tiles of all images share the U-Net launches.  Noise: the images of one noise class (canvas size)
         see the draw sequence a run of one of them alone sees.  Host noise: the generator state is taken once at entry and
@@ -786,7 +850,11 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
 
         ``solver``: None, or ``(sampler, eta, step_spacing)`` of a non-default sampler (validated by the caller): the step table and
         the levels are ``_schedule``'s of it; "dpmpp2m" keeps ``x_start`` and a history buffer and makes one batched history call
-        for all images after every step, after the guidance call."""
+        for all images after every step, after the guidance call.
+
+        ``threshold``: None, or the fp32 percentile of ``dynamic_threshold`` (validated by the caller): the step table is built with
+        ``no_clamp``, the run keeps ``x_start`` and makes one batched threshold call for all images after every executed step, before
+        the guidance call; ``threshold_log`` (a list or None) receives the [executed steps, images] tensor of s."""
         from .lockstep import plan_mixed_group
         dev = self.device
         if dev.type != "cuda":
@@ -810,7 +878,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                                     n_odd=len(p.coords1), noise_class=p.noise_class) for p in plans]
         tiles_even = [(a, c_) for p in plans for (a, _, c_, _) in p.coords0]
         tiles_odd = [(a, c_) for p in plans for (a, _, c_, _) in p.coords1]
-        scalars, log_snrs = _schedule(num_sample_steps) if solver is None else _schedule(num_sample_steps, *solver)
+        scalars, log_snrs = _schedule_of(num_sample_steps, solver, no_clamp=threshold is not None)
         sampler_name, step_spacing = ("ddpm", "time") if solver is None else (solver[0], solver[2])
         cond01 = torch.cat([c.to(dev, torch.float32).reshape(-1) for c in conds])
         cond_canvas = torch.empty(sum(3 * p.Hp * p.Wp for p in plans), device=dev, dtype=torch.float32)
@@ -862,13 +930,17 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                                    for (hp, wp) in classes])
             img = torch.cat([start[offs[p.noise_class]:offs[p.noise_class + 1]] for p in plans])
 
-        x_start = guided = history = None
+        x_start = guided = history = thresholded = None
         canvas_offs, cond_offs = [0], [0]
         for p in plans:
             canvas_offs.append(canvas_offs[-1] + 3 * p.Hp * p.Wp)
             cond_offs.append(cond_offs[-1] + 3 * p.H * p.W)
-        if guidance is not None or sampler_name == "dpmpp2m":
+        if guidance is not None or sampler_name == "dpmpp2m" or threshold is not None:
             x_start = img.clone()
+        if threshold is not None:
+            thresholded = _ThresholdRun(threshold, [(canvas_offs[k], p.Hp, p.Wp, p.box[1], p.box[0], p.H, p.W, p.inner[1], p.inner[0],
+                                                     p.inner[3] - p.inner[1], p.inner[2] - p.inner[0]) for k, p in enumerate(plans)],
+                                        num_sample_steps - generation_start_steps, dev)
         if sampler_name == "dpmpp2m":       # every image's inner box: what is never re-noised
             history = _SolverRun(num_sample_steps, step_spacing, generation_start_steps,
                                  [(canvas_offs[k], p.Hp, p.Wp, p.inner[1], p.inner[0], p.inner[3] - p.inner[1], p.inner[2] - p.inner[0])
@@ -907,6 +979,8 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
             else:
                 eng.sampler_step(i, img, cond_canvas, x_start, noise_tiles, noise_canvas, passes, kind, scale, sub_batch,
                                  seed=self.device_noise_seed)
+            if thresholded is not None:
+                thresholded.step(i, scalars, img, x_start)
             if guided is not None:
                 guided.step(i, scalars, img, x_start, cond01)
             if history is not None:
@@ -914,6 +988,8 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
 
         out = torch.empty(sum(3 * p.H * p.W for p in plans), device=dev, dtype=torch.float32)
         eng.sampler_end(img, out)
+        if thresholded is not None and threshold_log is not None:
+            threshold_log.append(thresholded.log())
         starts = [0]
         for p in plans:
             starts.append(starts[-1] + 3 * p.H * p.W)
@@ -1122,7 +1198,7 @@ class ConditionalElucidatedDiffusionSR(nn.Module):
                      generation_start_steps=0, num_sample_steps=None, clamp=True, zero_init=False, with_images=False,
                      with_x0_images=False, start_white_noise=True, amp=False, precision=None, seeds=None, color_fix=None,
                      reference=None, crop_border=4, back_project=0, consistency_guidance=0.0, consistency_guidance_start_steps=0,
-                     sampler="ddpm", eta=None, step_spacing="time"):
+                     sampler="ddpm", eta=None, step_spacing="time", dynamic_threshold=None, threshold_log=None):
         """Reference model.py:2309-2475 (``start_white_noise`` and ``amp`` are accepted and unused there too; ``precision``
         is the engine-only override of ``self.precision``).  ``seeds`` (per-image noise seeds) is a DDPM-sampler feature and is
         refused here.  ``color_fix``: as in the DDPM wrapper's ``tiled_sample`` - the final image of every image of the batch
@@ -1130,9 +1206,13 @@ class ConditionalElucidatedDiffusionSR(nn.Module):
         truth of every image of the batch; the return value gains a trailing list of metric dicts.  ``back_project``: as there
         too - N back-projection steps on the final image, after the colour fix and before the metrics.
         ``consistency_guidance``: a DDPM-sampler feature; a non-zero weight is refused here.
-        ``sampler``, ``eta``, ``step_spacing``: the DDPM wrapper's few-step samplers; any non-default value is refused here."""
+        ``sampler``, ``eta``, ``step_spacing``: the DDPM wrapper's few-step samplers; any non-default value is refused here.
+        ``dynamic_threshold``: a DDPM-sampler feature; a percentile other than None / 0 is refused here."""
         color_fix = check_mode(color_fix)
         back_project = _back_project_steps(back_project, condition_x)
+        if check_percentile(dynamic_threshold) is not None:
+            raise NotImplementedError("dynamic_threshold is built for the DDPM sampler only: its correction of the canvas rests on the "
+                                      "DDPM posterior mean, linear in the predicted clean image (the EDM wrapper has its own clamp)")
         check_start_steps(consistency_guidance_start_steps)
         if check_weight(consistency_guidance) is not None:
             raise NotImplementedError("consistency_guidance is built for the DDPM sampler only: its correction of the canvas rests on "
