@@ -1,4 +1,4 @@
-"""Build ``libsrgd_hip.so`` (the C-ABI engine, include/srgd_hip.h), ``libsrgd_metrics.so`` (include/srgd_metrics.h), ``libsrgd_ensemble.so`` (include/srgd_ensemble.h), ``libsrgd_consistency.so`` (include/srgd_consistency.h), ``libsrgd_backproject.so`` (include/srgd_backproject.h), ``libsrgd_guidance.so`` (include/srgd_guidance.h), ``libsrgd_solver.so`` (include/srgd_solver.h), ``libsrgd_resize.so`` (include/srgd_resize.h), ``libsrgd_alpha.so`` (include/srgd_alpha.h) and ``libsrgd_threshold.so`` (include/srgd_threshold.h) in-tree with hipcc for gfx950.
+"""Build ``libsrgd_hip.so`` (the C-ABI engine, include/srgd_hip.h), ``libsrgd_metrics.so`` (include/srgd_metrics.h), ``libsrgd_ensemble.so`` (include/srgd_ensemble.h), ``libsrgd_consistency.so`` (include/srgd_consistency.h), ``libsrgd_backproject.so`` (include/srgd_backproject.h), ``libsrgd_guidance.so`` (include/srgd_guidance.h), ``libsrgd_solver.so`` (include/srgd_solver.h), ``libsrgd_resize.so`` (include/srgd_resize.h), ``libsrgd_alpha.so`` (include/srgd_alpha.h), ``libsrgd_threshold.so`` (include/srgd_threshold.h) and ``libsrgd_selfens.so`` (include/srgd_selfens.h) in-tree with hipcc for gfx950.
 
 hipcc cross-compiles without a GPU, so this runs in the build container; the resulting
 ``srgd_amd/libsrgd_hip.so`` travels to the GPU box with the tree (git-ignored, not
@@ -35,6 +35,8 @@ ALPHA_LIB = os.path.join(HERE, "libsrgd_alpha.so")    # include/srgd_alpha.h: a 
 ALPHA_SOURCES = ["alpha.hip"]
 THRESHOLD_LIB = os.path.join(HERE, "libsrgd_threshold.so")    # include/srgd_threshold.h: a library of its own, from THRESHOLD_SOURCES
 THRESHOLD_SOURCES = ["threshold.hip"]
+SELFENS_LIB = os.path.join(HERE, "libsrgd_selfens.so")    # include/srgd_selfens.h: a library of its own, from SELFENS_SOURCES
+SELFENS_SOURCES = ["selfens.hip"]
 # resize.hip's host code reproduces Pillow's double-precision tables: no fused multiply-adds in it (its kernels are integer code);
 # threshold.hip's definition is in separate fp32 multiplications and additions, on the host and in its kernels
 EXTRA_FLAGS = {"resize.hip": ["-ffp-contract=off"], "threshold.hip": ["-ffp-contract=off"]}
@@ -66,7 +68,7 @@ def _digest() -> str:
 def build(force: bool = False, verbose: bool = False) -> str:
     stamp = os.path.join(OBJ_DIR, "stamp")
     digest = _digest()
-    if not force and os.path.exists(LIB) and os.path.exists(METRICS_LIB) and os.path.exists(ENSEMBLE_LIB) and os.path.exists(CONSISTENCY_LIB) and os.path.exists(BACKPROJECT_LIB) and os.path.exists(GUIDANCE_LIB) and os.path.exists(SOLVER_LIB) and os.path.exists(RESIZE_LIB) and os.path.exists(ALPHA_LIB) and os.path.exists(THRESHOLD_LIB) and os.path.exists(stamp) and open(stamp).read() == digest:
+    if not force and os.path.exists(LIB) and os.path.exists(METRICS_LIB) and os.path.exists(ENSEMBLE_LIB) and os.path.exists(CONSISTENCY_LIB) and os.path.exists(BACKPROJECT_LIB) and os.path.exists(GUIDANCE_LIB) and os.path.exists(SOLVER_LIB) and os.path.exists(RESIZE_LIB) and os.path.exists(ALPHA_LIB) and os.path.exists(THRESHOLD_LIB) and os.path.exists(SELFENS_LIB) and os.path.exists(stamp) and open(stamp).read() == digest:
         return LIB
     os.makedirs(OBJ_DIR, exist_ok=True)
     hipcc = _hipcc()
@@ -82,7 +84,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
         return obj
 
     with ThreadPoolExecutor(max_workers=min(6, os.cpu_count() or 1)) as ex:
-        objs = list(ex.map(compile_one, SOURCES + METRICS_SOURCES + ENSEMBLE_SOURCES + CONSISTENCY_SOURCES + BACKPROJECT_SOURCES + GUIDANCE_SOURCES + SOLVER_SOURCES + RESIZE_SOURCES + ALPHA_SOURCES + THRESHOLD_SOURCES))
+        objs = list(ex.map(compile_one, SOURCES + METRICS_SOURCES + ENSEMBLE_SOURCES + CONSISTENCY_SOURCES + BACKPROJECT_SOURCES + GUIDANCE_SOURCES + SOLVER_SOURCES + RESIZE_SOURCES + ALPHA_SOURCES + THRESHOLD_SOURCES + SELFENS_SOURCES))
+    selfens_objs = objs[len(objs) - len(SELFENS_SOURCES):]
+    objs = objs[:len(objs) - len(SELFENS_SOURCES)]
     threshold_objs = objs[len(objs) - len(THRESHOLD_SOURCES):]
     objs = objs[:len(objs) - len(THRESHOLD_SOURCES)]
     alpha_objs = objs[len(objs) - len(ALPHA_SOURCES):]
@@ -170,6 +174,13 @@ def build(force: bool = False, verbose: bool = False) -> str:
                         *threshold_objs], capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"link of the threshold library failed:\n{r.stdout}\n{r.stderr}")
+    evers = os.path.join(OBJ_DIR, "exports_selfens.map")
+    with open(evers, "w") as f:
+        f.write("{ global: srgd_selfens*; local: *; };\n")
+    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", f"-Wl,--version-script={evers}", "-o", SELFENS_LIB,
+                        *selfens_objs], capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"link of the self-ensemble library failed:\n{r.stdout}\n{r.stderr}")
     with open(stamp, "w") as f:
         f.write(digest)
     return LIB

@@ -40,6 +40,9 @@ from .metrics import metrics_on_device  # noqa: F401  (public: srgd_amd.inferenc
 from .model import ConditionalElucidatedDiffusionSR, get_model
 from .resize import FILTERS as OUTSCALE_FILTERS
 from .resize import check_filter, check_outscale, outscale_size
+from .selfens import OPS as SELF_ENSEMBLE_OPS
+from .selfens import check_self_ensemble
+from .selfens import dihedral_on_device, self_ensemble_on_device  # noqa: F401  (public: srgd_amd.inference.*)
 from .solver import check_sampler
 from .threshold import check_percentile
 
@@ -165,7 +168,19 @@ def parse_args(argv=None):
                         "rounded mean of its known 8-neighbours - so that the arbitrary colour stored under transparent pixels does "
                         "not leak across the outline as a halo; the bled image is the input of the whole run (condition, --color_fix, "
                         "--back_project, --consistency_guidance, --consistency); the alpha itself is unchanged (0, the default: off)")
+    p.add_argument("--self_ensemble", type=int, default=1, metavar="N",
+                   help="geometric self-ensemble, N in {1, 2, 4, 8} (1, the default: off): every input is sampled in N orientations - "
+                        "2: as it is and mirrored, 4: the four flips, 8: the four flips of the image and of its transpose, the x8 '+' "
+                        "variant of the SR literature - in lock-step (--lockstep N*K unless a lock-step flag is given), every output "
+                        "is turned back and the N are averaged on the GPU, halves up; --color_fix, --back_project, "
+                        "--consistency_guidance and --dynamic_threshold act on every orientation against its own turned input, "
+                        "--reference_dir, --consistency, --outscale, --alpha keep and --ensemble on the merged image (engine "
+                        "extension, DDPM configs only)")
     args = p.parse_args(argv)
+    try:
+        args.self_ensemble = check_self_ensemble(args.self_ensemble)
+    except ValueError as e:
+        raise SystemExit(f"--self_ensemble: {e}")
     if not 0 <= args.alpha_bleed <= ALPHA_BLEED_MAX:
         raise SystemExit(f"--alpha_bleed: N must be in 0 .. {ALPHA_BLEED_MAX}, got {args.alpha_bleed}")
     if args.alpha_bleed and args.alpha != "keep":
@@ -636,8 +651,20 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
                            ensemble_name="ensemble.json", consistency=False, consistency_name="consistency.json", back_project=0,
                            consistency_guidance=0.0, consistency_guidance_start_steps=0, sampler="ddpm", eta=None,
                            step_spacing="time", outscale=None, outscale_filter="bicubic", alpha="drop", alpha_bleed=0,
-                           dynamic_threshold=0.0):
-    """``dynamic_threshold`` (``--dynamic_threshold P``): P > 0 is handed by keyword to whichever ``sr_target_image*`` function samples
+                           dynamic_threshold=0.0, self_ensemble=1):
+    """``self_ensemble`` (``--self_ensemble N``, N in 1, 2, 4, 8): with N > 1 every planned entry (file, sample seed) becomes N
+    consecutive entries of the grouping, one per op of ``srgd_amd.selfens.OPS[N]`` in that order, all with the entry's seed and label;
+    their inputs are ``dihedral_on_device`` of the opened input (after ``alpha_bleed``), transformed once per opened file.  The
+    variants are ordinary images of their lock-step group (with neither lock-step argument they group as ``lockstep = N * samples``;
+    a transposed half of another size is split off by the flush at a size change), so ``color_fix``, ``back_project``,
+    ``consistency_guidance`` and ``dynamic_threshold`` act on each variant against its own transformed input; ``reference=`` is not
+    handed to the ``sr_target_image*`` functions.  The 8-bit outputs of an entry's variants are held, across ``flush()`` calls where
+    they straddle them, until the N-th arrives; all entries completed in one ``flush()`` are merged in one
+    ``self_ensemble_on_device`` call (every output turned back, the N averaged, halves up), and everything below - ``reference_dir``
+    (``metrics_on_device`` on the merged image's ``mean01``), ``consistency`` against the original input, ``outscale``, ``alpha``,
+    saving, ``ensemble`` - acts on the merged image of each completed entry.  With 1 (the default) the library is not loaded and
+    nothing is launched.  Any other N, and N > 1 with an EDM model, is a ``ValueError`` before anything is sampled.
+    ``dynamic_threshold`` (``--dynamic_threshold P``): P > 0 is handed by keyword to whichever ``sr_target_image*`` function samples
     a group (``tiled_sample(dynamic_threshold=P)``: percentile clipping of the predicted clean image inside the sampling loop); with 0
     the keyword is not passed at all.  A P outside [0, 1] is a ``ValueError`` before anything is sampled.
     ``alpha`` / ``alpha_bleed`` (``--alpha keep``, ``--alpha_bleed N``): with "keep" every input is opened with its alpha plane
@@ -687,9 +714,15 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
     entries of the grouping, each counts as an image of its group, and with neither lock-step argument they group as
     ``lockstep=samples``."""
     from .lockstep import even_step_tiles, plan_lockstep_groups
+    self_ensemble = check_self_ensemble(self_ensemble)
+    if self_ensemble > 1 and isinstance(sr_model, ConditionalElucidatedDiffusionSR):
+        raise ValueError("self_ensemble: the orientations of an image are sampled in lock-step with per-image noise seeds, which is "
+                         "built for the DDPM sampler only; this model samples with EDM")
     print(f"save images at: {output_dir}")
     os.makedirs(output_dir, exist_ok=True)
     labels = labels or {}
+    if self_ensemble > 1 and lockstep_tiles is None and lockstep <= 1:
+        lockstep = self_ensemble * samples
     if samples > 1 and lockstep_tiles is None and lockstep <= 1:
         lockstep = samples
     kw = dict(scale=scale, batch_size=batch_size, cond_scale=cond_scale,
@@ -726,6 +759,7 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
     ens_open = {}                                        # --ensemble: input file -> [its K samples (PIL image of this run) or None (on disk)], samples still to draw
     ens_ready, ens_records, ens_quality = [], [], []     # files whose last sample is handled; ensemble.json rows; metrics.json rows
     cons_records, cons_ensemble = [], []                 # --consistency: consistency.json rows of the files written; of the mean images
+    held = {}                                            # --self_ensemble: save path -> [(entry, 8-bit output)] of the variants sampled so far
 
     def measure_consistency(names, outputs, inputs):
         """One batched ``consistency_on_device`` call: ``outputs`` uint8 [4h,4w,3] tensors, ``inputs`` the PIL inputs ->
@@ -770,7 +804,7 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
             one_label = group_labels[0] if len(set(group_labels)) == 1 else group_labels
             group_images = [e[0] for e in pending]
             ref_kw = {}
-            if reference_dir is not None:                # the decoded references of the group (one future per input file)
+            if reference_dir is not None and self_ensemble == 1:         # the decoded references of the group (one future per input file)
                 ref_kw = {"reference": [e[4].result() for e in pending], "crop_border": crop_border}
             if len(pending) == 1:                        # a solo run with that seed: what every sample of a group is identical to
                 solo_kw = dict(ref_kw, reference=ref_kw["reference"][0]) if ref_kw else {}
@@ -785,6 +819,25 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
             if ref_kw:
                 outs, quality = outs
                 file_records.extend((e[5], os.path.basename(e[1]), q) for e, q in zip(pending, quality))
+            if self_ensemble > 1:                        # the entries whose last variant arrived are merged; the rest is held
+                for e, sr in zip(pending, outs):
+                    held.setdefault(e[1], []).append((e, sr))
+                complete = [held.pop(path) for path in [path for path, parts in held.items() if len(parts) == self_ensemble]]
+                pending.clear()
+                if not complete:
+                    return
+                device = getattr(sr_model, "device", None)
+                place = (lambda t: t.to(device)) if device is not None else (lambda t: t)        # noqa: E731
+                merged = self_ensemble_on_device([[(place(pil_to_u8_tensor(sr)), e[8]) for e, sr in parts] for parts in complete],
+                                                 return_mean01=reference_dir is not None)
+                # from here on the group is the completed entries, each with its original input and its merged image
+                pending.extend((parts[0][0][9],) + parts[0][0][1:] for parts in complete)
+                group_images = [e[0] for e in pending]
+                if reference_dir is not None:
+                    quality = metrics_on_device([m[1] for m in merged], [e[4].result() for e in pending], crop_border)
+                    file_records.extend((e[5], os.path.basename(e[1]), q) for e, q in zip(pending, quality))
+                    merged = [m[0] for m in merged]
+                outs = [Image.fromarray(m.cpu().numpy(), "RGB") for m in merged]
             if consistency:                              # the images as saved against the inputs the group was given
                 written = [os.path.basename(e[1]) for e in pending]
                 source = dict(zip(written, (e[5] for e in pending)))
@@ -873,6 +926,7 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
 
         opened = (None, None, None)                      # the K samples of a file share one decoded image and one reference
         plane = None                                     # --alpha keep: the alpha plane of the opened file, or None
+        variants = (None, None)                          # --self_ensemble: (the opened input, its N orientations)
         for filename, save_path, noise_seed in plan_sample_entries(file_names, output_dir, samples, seed):
             if opened[0] != filename:
                 if alpha == "keep":
@@ -889,23 +943,30 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
                     print("Invalid image or unable to open image:", filename)
                 elif reference_dir is not None:          # decoded on the pool while the groups before this one sample
                     opened = opened[:2] + (pool.submit(load_reference, os.path.join(reference_dir, os.path.basename(filename))),)
-            image, ref = opened[1], opened[2]
-            if image is None:
+            original, ref = opened[1], opened[2]
+            if original is None:
                 continue
+            if self_ensemble > 1 and variants[0] is not original:          # once per opened file: the input in every orientation
+                device = getattr(sr_model, "device", None)
+                low = pil_to_u8_tensor(original)
+                turned = dihedral_on_device([low.to(device) if device is not None else low] * self_ensemble,
+                                            list(SELF_ENSEMBLE_OPS[self_ensemble]))
+                variants = (original, [Image.fromarray(t.cpu().numpy(), "RGB") for t in turned])
             label = labels.get(os.path.basename(filename), test_label)
-            if pending and (label is None) != (pending[0][2] is None):     # an unlabelled image does not join a labelled group
-                flush()
-            if lockstep_tiles is not None:
-                hr = [(h * scale, w * scale) for (w, h) in [e[0].size for e in pending] + [image.size]]
-                if len(plan_lockstep_groups(hr, lockstep_tiles)) > 1:      # the image would push the group over the budget
+            for op, image in zip(SELF_ENSEMBLE_OPS[self_ensemble], variants[1] if self_ensemble > 1 else [original]):
+                if pending and (label is None) != (pending[0][2] is None): # an unlabelled image does not join a labelled group
                     flush()
-                pending.append((image, save_path, label, noise_seed, ref, os.path.basename(filename), filename, plane))
-                continue
-            if pending and (len(pending) >= max(1, lockstep) or pending[0][0].size != image.size):
-                flush()
-            pending.append((image, save_path, label, noise_seed, ref, os.path.basename(filename), filename, plane))
-            if len(pending) >= max(1, lockstep):
-                flush()
+                if lockstep_tiles is not None:
+                    hr = [(h * scale, w * scale) for (w, h) in [e[0].size for e in pending] + [image.size]]
+                    if len(plan_lockstep_groups(hr, lockstep_tiles)) > 1:  # the image would push the group over the budget
+                        flush()
+                    pending.append((image, save_path, label, noise_seed, ref, os.path.basename(filename), filename, plane, op, original))
+                    continue
+                if pending and (len(pending) >= max(1, lockstep) or pending[0][0].size != image.size):
+                    flush()
+                pending.append((image, save_path, label, noise_seed, ref, os.path.basename(filename), filename, plane, op, original))
+                if len(pending) >= max(1, lockstep):
+                    flush()
         flush()
         if ensemble:
             flush_ensembles()
@@ -946,6 +1007,10 @@ def main(argv=None):
         check_references(sorted(glob.glob(f"{args.input_dir}/*"))[args.start_index:args.end_index], args.reference_dir, 4,
                          args.crop_border)
     conf = load_config(args.conf)
+    if args.self_ensemble > 1 and conf.model == "conditional_elucidated":     # before the model is built
+        raise SystemExit("--self_ensemble: the orientations of an image are sampled in lock-step with per-image noise seeds, which is "
+                         "built for the DDPM sampler (model: conditional_continuous) only; this config samples with EDM - run "
+                         "without it")
     conf.num_sample_steps = args.num_sample_steps
     conf.ckpt_path = args.ckpt_path
     ema_model = get_model(conf, logger)
@@ -999,6 +1064,7 @@ def main(argv=None):
                            sampler=args.sampler, eta=args.eta, step_spacing=args.step_spacing,
                            outscale=args.outscale, outscale_filter=args.outscale_filter, alpha=args.alpha,
                            alpha_bleed=args.alpha_bleed, dynamic_threshold=args.dynamic_threshold,
+                           **({"self_ensemble": args.self_ensemble} if args.self_ensemble > 1 else {}),
                            consistency_name="consistency.json" if world == 1 else f"consistency_rank{rank}.json")
 
 
