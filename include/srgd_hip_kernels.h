@@ -102,6 +102,15 @@ int srgd_k_full_attention(const void* qkv, void* out, int B, int N, int heads, i
 int srgd_k_linattn_block_fused(const void* x, void* y, int B, int N, int C, const float* to_qkv_host,
                                const float* norm_g_host, const float* to_out_w_host, const float* to_out_b_host,
                                const float* out_g_host, void* stream);
+/* The same call with the block's intermediates exposed for tests; every output below is optional (NULL: skipped).
+ *   ctxn_out  device fp32 [B*4][32 d][32 e]: the normalised context * dim_head^-0.5 that the second kernel consumes
+ *   rinv_out  device fp32 [B][N]: 1 / max(||x_n||, 1e-12)
+ *   y_q, y_s  device bytes [B*N][C] and [B*N][C/32]: the MX-fp8 twin of y that fp8 mode writes alongside (both or neither)
+ *   strip_out, tiles_per_wg_out  host ints: pixels per first-kernel workgroup and tiles per second-kernel workgroup of this launch */
+int srgd_k_linattn_block_fused_probe(const void* x, void* y, int B, int N, int C, const float* to_qkv_host,
+                                     const float* norm_g_host, const float* to_out_w_host, const float* to_out_b_host,
+                                     const float* out_g_host, float* ctxn_out, float* rinv_out, void* y_q, void* y_s,
+                                     int* strip_out, int* tiles_per_wg_out, void* stream);
 
 /* f16x3 mode: a pointwise projection with an RMSNorm folded into its kernel (conv1x1_split.hip), fp32 NHWC tensors, N % 256 == 0.
  *   pre_norm_g_host  != NULL:  out = W . RMSNorm_g(x)                      replaces: self.norm(x) -> self.to_qkv (model.py:311-312, :348-349)

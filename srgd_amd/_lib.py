@@ -137,6 +137,9 @@ PROTOTYPES = {
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "srgd_k_linattn_block_fused": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "srgd_k_linattn_block_fused_probe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
 }
 
 _lib = None

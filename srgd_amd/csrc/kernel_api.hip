@@ -208,11 +208,13 @@ int srgd_k_linear_attention(const void* qkv, void* out, int B, int N, int heads,
   return 0;
 }
 
-int srgd_k_linattn_block_fused(const void* x, void* y, int B, int N, int C, const float* to_qkv_host,
-                               const float* norm_g_host, const float* to_out_w_host, const float* to_out_b_host,
-                               const float* out_g_host, void* stream) {
+int srgd_k_linattn_block_fused_probe(const void* x, void* y, int B, int N, int C, const float* to_qkv_host,
+                                     const float* norm_g_host, const float* to_out_w_host, const float* to_out_b_host,
+                                     const float* out_g_host, float* ctxn_out, float* rinv_out, void* y_q, void* y_s,
+                                     int* strip_out, int* tiles_per_wg_out, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   if (!linattn_fused_eligible(C, 4, 32, N, true)) SRGD_FAIL("linattn_block_fused: needs C = 128 or 256, N % 64 == 0");
+  if ((y_q == nullptr) != (y_s == nullptr)) SRGD_FAIL("linattn_block_fused: y_q and y_s come together");
   std::vector<unsigned short> wkv, wq, wo;
   linattn_fused_pack(to_qkv_host, norm_g_host, to_out_w_host, C, wkv, wq, wo);
   std::vector<float> g2(C);
@@ -225,9 +227,23 @@ int srgd_k_linattn_block_fused(const void* x, void* y, int B, int N, int C, cons
   SRGD_HIP(hipMemcpy(dout.p, wo.data(), wo.size() * 2, hipMemcpyHostToDevice));
   SRGD_HIP(hipMemcpy(db.p, to_out_b_host, C * 4, hipMemcpyHostToDevice));
   SRGD_HIP(hipMemcpy(dg.p, g2.data(), C * 4, hipMemcpyHostToDevice));
-  SRGD_TRY(linattn_fused(x, y, B, N, C, dkv.p, dq.p, dout.p, (const float*)db.p, (const float*)dg.p, (float*)ws.p, st));
+  int tpw = 0;
+  SRGD_TRY(linattn_fused(x, y, B, N, C, dkv.p, dq.p, dout.p, (const float*)db.p, (const float*)dg.p, (float*)ws.p, st, y_q, y_s,
+                         &tpw));
+  const LinattnLayout lay = linattn_fused_layout(B, N, (float*)ws.p);
+  if (ctxn_out) SRGD_HIP(hipMemcpyAsync(ctxn_out, lay.ctxn, (size_t)B * 4 * 1024 * sizeof(float), hipMemcpyDeviceToDevice, st));
+  if (rinv_out) SRGD_HIP(hipMemcpyAsync(rinv_out, lay.rinv, (size_t)B * N * sizeof(float), hipMemcpyDeviceToDevice, st));
   SRGD_HIP(hipStreamSynchronize(st));
+  if (strip_out) *strip_out = lay.strip;
+  if (tiles_per_wg_out) *tiles_per_wg_out = tpw;
   return 0;
+}
+
+int srgd_k_linattn_block_fused(const void* x, void* y, int B, int N, int C, const float* to_qkv_host,
+                               const float* norm_g_host, const float* to_out_w_host, const float* to_out_b_host,
+                               const float* out_g_host, void* stream) {
+  return srgd_k_linattn_block_fused_probe(x, y, B, N, C, to_qkv_host, norm_g_host, to_out_w_host, to_out_b_host, out_g_host,
+                                          nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 int srgd_k_conv1x1_split_rms(const void* x, int Cin, int B, int N, const float* weight_oi_host, const float* bias_host, int Cout,

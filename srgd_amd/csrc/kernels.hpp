@@ -204,20 +204,30 @@ int linear_attention_combine(const float* pm, const float* pl, const float* pctx
 // ---------------------------------------------------------------- linattn_fused.hip
 // Whole LinearAttention block + residual (model.py:306-324, :703) in two kernels; bf16, C = 128 or 256, 4 heads x 32.
 bool linattn_fused_eligible(int C, int heads, int dh, int N, bool is_bf16);
+// the workspace of one call, laid out in one place: la1's per-strip partials (pm, pl, pctx), the normalised context the combine
+// step leaves for la2, and la1's row norms.  `base` may be null (sizes only).
+struct LinattnLayout {
+  int strip, nstrips;                 // pixels per la1 workgroup, workgroups per image
+  float *pm, *pl, *pctx;              // [B*4][nstrips][32], [B*4][nstrips][32], [B*4][nstrips][32 d][32 e]
+  float *ctxn, *rinv;                 // [B*4][32 d][32 e], [B][N]
+  size_t floats;                      // total length
+};
+LinattnLayout linattn_fused_layout(int B, int N, float* base);
 size_t linattn_fused_workspace(int B, int N);
 void linattn_fused_pack(const float* to_qkv, const float* norm_g, const float* to_out, int C,
                         std::vector<unsigned short>& wkv_img, std::vector<unsigned short>& wq,
                         std::vector<unsigned short>& wout);
 int linattn_fused(const void* x, void* y, int B, int N, int C, const void* wkv_img, const void* wq, const void* wout,
                   const float* bout, const float* g2_scaled, float* ws, hipStream_t st, void* y_q = nullptr,
-                  void* y_s = nullptr);          // y_q / y_s: optional MX-fp8 twin of y (see ConvArgs::out_q)
+                  void* y_s = nullptr,           // y_q / y_s: optional MX-fp8 twin of y (see ConvArgs::out_q)
+                  int* tiles_per_wg = nullptr);  // optional: the la2 tiles per workgroup this launch chose
 // linattn_fused256.hip: the 32-pixel-tile kernels (C = 256) behind the entry points above
 bool linattn_fused256_eligible(int C, int heads, int dh, int N, bool is_bf16);
 void linattn_fused256_pack(const float* to_qkv, const float* norm_g, const float* to_out, int C, std::vector<unsigned short>& wkv,
                            std::vector<unsigned short>& wq, std::vector<unsigned short>& wout);
 int linattn_fused256(const void* x, void* y, int B, int N, int C, const void* wkv, const void* wq, const void* wout,
                      const float* bout, const float* g2_scaled, float* pm, float* pl, float* pctx, float* ctxn, float* rinv,
-                     int strip, hipStream_t st, void* y_q, void* y_s);
+                     int strip, hipStream_t st, void* y_q, void* y_s, int* tiles_per_wg = nullptr);
 
 // ---------------------------------------------------------------- cond.hip
 // feat[r] = [x, sin(2 pi x w_i), cos(2 pi x w_i)]   (reference model.py:233-238)

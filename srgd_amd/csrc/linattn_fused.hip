@@ -476,10 +476,22 @@ bool linattn_fused_eligible(int C, int heads, int dh, int N, bool is_bf16) {
 
 static int la1_strip(int N) { return N >= 65536 ? 2048 : (N >= 16384 ? 1024 : (N >= 2048 ? 512 : 256)); }
 
-size_t linattn_fused_workspace(int B, int N) {
-  const size_t nch = (size_t)cdiv(N, la1_strip(N));
-  return ((size_t)B * 4 * nch * (64 + 1024) + (size_t)B * 4 * 1024 + (size_t)B * N) * sizeof(float);
+LinattnLayout linattn_fused_layout(int B, int N, float* base) {
+  LinattnLayout w;
+  w.strip = la1_strip(N);
+  w.nstrips = cdiv(N, w.strip);
+  const size_t bh = (size_t)B * 4, nch = (size_t)w.nstrips;
+  const size_t o_pl = bh * nch * 32, o_pctx = o_pl + bh * nch * 32, o_ctxn = o_pctx + bh * nch * 1024, o_rinv = o_ctxn + bh * 1024;
+  w.floats = o_rinv + (size_t)B * N;
+  w.pm = base;
+  w.pl = base ? base + o_pl : nullptr;
+  w.pctx = base ? base + o_pctx : nullptr;
+  w.ctxn = base ? base + o_ctxn : nullptr;
+  w.rinv = base ? base + o_rinv : nullptr;
+  return w;
 }
+
+size_t linattn_fused_workspace(int B, int N) { return linattn_fused_layout(B, N, nullptr).floats * sizeof(float); }
 
 // host-side operand preparation
 //   wkv_img: [256 rows = k(128) | v(128)][128 c] bf16, rows XOR-swizzled into the LDS image, gains folded
@@ -505,18 +517,15 @@ void linattn_fused_pack(const float* to_qkv /*[384][C]*/, const float* norm_g /*
 }
 
 int linattn_fused(const void* x, void* y, int B, int N, int C, const void* wkv_img, const void* wq, const void* wout,
-                  const float* bout, const float* g2_scaled, float* ws, hipStream_t st, void* y_q, void* y_s) {
-  const int strip = la1_strip(N);
-  const int nstrips = cdiv(N, strip);
-  const int nch = nstrips;
+                  const float* bout, const float* g2_scaled, float* ws, hipStream_t st, void* y_q, void* y_s,
+                  int* tiles_per_wg) {
+  const LinattnLayout lay = linattn_fused_layout(B, N, ws);
+  const int strip = lay.strip, nstrips = lay.nstrips, nch = nstrips;
   const size_t bh = (size_t)B * 4;
-  float* pm = ws;
-  float* pl = pm + bh * nch * 32;
-  float* pctx = pl + bh * nch * 32;
-  float* ctxn = pctx + bh * nch * 1024;
-  float* rinv = ctxn + bh * 1024;
+  float *const pm = lay.pm, *const pl = lay.pl, *const pctx = lay.pctx, *const ctxn = lay.ctxn, *const rinv = lay.rinv;
   if (C == 256)
-    return linattn_fused256(x, y, B, N, C, wkv_img, wq, wout, bout, g2_scaled, pm, pl, pctx, ctxn, rinv, strip, st, y_q, y_s);
+    return linattn_fused256(x, y, B, N, C, wkv_img, wq, wout, bout, g2_scaled, pm, pl, pctx, ctxn, rinv, strip, st, y_q, y_s,
+                            tiles_per_wg);
   if (C != 128) SRGD_FAIL("linattn_fused: C must be 128 or 256");
   static bool attr[64] = {};
   const int lds1 = RING * TILE_BYTES + 2 * TM * 4;
@@ -555,6 +564,7 @@ int linattn_fused(const void* x, void* y, int B, int N, int C, const void* wkv_i
   int tpw = 1;
   while (tpw < 16 && (long)B * cdiv(ntiles, tpw * 2) >= 1024) tpw *= 2;
   a.tiles_per_wg = tpw;
+  if (tiles_per_wg) *tiles_per_wg = tpw;
   hipLaunchKernelGGL(la2_kernel, dim3(cdiv(ntiles, tpw), B), dim3(NTH), lds2, st, a);
   SRGD_HIP(hipGetLastError());
   return 0;

@@ -410,7 +410,7 @@ bool linattn_fused256_eligible(int C, int heads, int dh, int N, bool is_bf16) {
 template <int C>
 static int launch_la_t(const void* x, void* y, int B, int N, const void* wkv, const void* wq, const void* wout, const float* bout,
                        const float* g2_scaled, float* pm, float* pl, float* pctx, float* ctxn, float* rinv, int strip,
-                       hipStream_t st, void* y_q, void* y_s) {
+                       hipStream_t st, void* y_q, void* y_s, int* tiles_per_wg) {
   const int nstrips = cdiv(N, strip);
   const size_t bh = (size_t)B * 4;
   static bool attr[64] = {};
@@ -434,6 +434,7 @@ static int launch_la_t(const void* x, void* y, int B, int N, const void* wkv, co
   int tpw = 1;
   while (tpw < 32 && (long)B * cdiv(ntiles, tpw * 2) >= 1024) tpw *= 2;
   a.tiles_per_wg = tpw;
+  if (tiles_per_wg) *tiles_per_wg = tpw;
   hipLaunchKernelGGL(la2_t_kernel<C>, dim3(cdiv(ntiles, tpw), B), dim3(NTH2), lds2, st, a);
   SRGD_HIP(hipGetLastError());
   return 0;
@@ -441,8 +442,9 @@ static int launch_la_t(const void* x, void* y, int B, int N, const void* wkv, co
 
 int linattn_fused256(const void* x, void* y, int B, int N, int C, const void* wkv, const void* wq, const void* wout,
                      const float* bout, const float* g2_scaled, float* pm, float* pl, float* pctx, float* ctxn, float* rinv,
-                     int strip, hipStream_t st, void* y_q, void* y_s) {
-  if (C == 256) return launch_la_t<256>(x, y, B, N, wkv, wq, wout, bout, g2_scaled, pm, pl, pctx, ctxn, rinv, strip, st, y_q, y_s);
+                     int strip, hipStream_t st, void* y_q, void* y_s, int* tiles_per_wg) {
+  if (C == 256)
+    return launch_la_t<256>(x, y, B, N, wkv, wq, wout, bout, g2_scaled, pm, pl, pctx, ctxn, rinv, strip, st, y_q, y_s, tiles_per_wg);
   // (the C = 128 instance of these 32-pixel-tile kernels measured 0.4 % slower end to end than linattn_fused.hip's 64-pixel
   // kernels and is no longer instantiated: DESIGN 4.3)
   SRGD_FAIL("linattn_fused256: C must be 256");
