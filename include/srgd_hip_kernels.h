@@ -77,6 +77,34 @@ int srgd_k_conv3x3_mxfp8(const void* in0, const void* in1, int C0, int C1, int B
                          const float* weight_oihw_host, const float* bias_host, int Cout, void* out, float* gn_partial,
                          int groups, int iters, float* avg_ms, int* stats_slots, void* stream);
 
+/* ---- test / probe interfaces of the MX-fp8 quantisation sites (tests/test_mxfp8_exact_gpu.py); the engine calls none of them.
+ * Every q / out_q is [pixels][C] e4m3 bytes, every s / out_s [pixels][C/32] E8M0 bytes, of the bf16 tensor the same call stores
+ * ("twin": identical to srgd_k_quant_mxfp8 of that tensor).
+ *
+ * y = silu(coefA[b][c] * x + coefB[b][c]) quantised straight to MX-fp8, no bf16 store in between (quant_mxfp8.hip's GroupNorm
+ * variant: the input of the second 3x3 convolution of an fp8 ResnetBlock).  x: bf16 [B][hw][C]; coefA / coefB: device fp32 [B][C],
+ * 16-byte aligned.  C % 32 == 0.  Asynchronous on `stream`. */
+int srgd_k_gn_apply_silu_mxfp8(const void* x_bf16, void* q, void* s, const float* coefA, const float* coefB, int B, int hw,
+                               int C, void* stream);
+/* srgd_k_conv2d_timed without the timing, with the MX-fp8 twin of `out` (pixel-shuffle: of the shuffled [B][2H][2W][Cout/4] tensor).
+ * Fails unless the selected kernel writes twins: impl 3 (conv1x1_bf16) or 4 (conv1x1_mxfp8).
+ * ps0 > 0 (impl 3, one source, kind 0, stride 1, pad 0): the overlapping-window form in which the engine runs the 7x7 input
+ * convolution - a KS x 1 kernel over C0 "channels" whose consecutive pixels lie ps0 elements apart in in0 ([B][Hin][Win][ps0]);
+ * Wout is then given by the caller (Hout = Hin - KS + 1) and weight_oihw_host is [Cout][C0][KS][1].  ps0 = 0, Wout = 0 otherwise. */
+int srgd_k_conv2d_twin(const void* in0, const void* in1, int C0, int C1, int B, int Hin, int Win, int KS, int stride,
+                       int pad, int kind, const float* weight_oihw_host, const float* bias_host, int Cout, void* out,
+                       const void* residual, float* gn_partial, int groups, int is_bf16, int impl, int* stats_slots,
+                       const void* gn_tail_src, const float* gn_tail_a, const float* gn_tail_b, void* out_q, void* out_s,
+                       int ps0, int Wout, void* stream);
+/* srgd_k_conv3x3_mxfp8 with the MX-fp8 twin of `out`. */
+int srgd_k_conv3x3_mxfp8_twin(const void* in0, const void* in1, int C0, int C1, int B, int H, int W,
+                              const float* weight_oihw_host, const float* bias_host, int Cout, void* out, float* gn_partial,
+                              int groups, int iters, float* avg_ms, int* stats_slots, void* out_q, void* out_s, void* stream);
+/* srgd_k_groupnorm_silu (below) with the MX-fp8 twin of y; bf16 only, C % 32 == 0. */
+int srgd_k_groupnorm_silu_twin(const void* x, void* y, const void* residual, const float* gn_partial, int B, int hw,
+                               int C, int groups, const float* gamma, const float* beta, const float* scale_shift,
+                               int nslots, int is_bf16, void* out_q, void* out_s, void* stream);
+
 /* GroupNorm (from the conv's partial statistics) -> x*(scale+1)+shift -> SiLU (+ residual).
  * replaces: Block.forward after the conv (model.py:250-259) and the ResnetBlock residual add (:285).
  * gamma, beta: device [C]; scale_shift: device [B][2C] (scale | shift) or NULL; in place if y == x.

@@ -34,7 +34,10 @@ def quantize(x: torch.Tensor, block: int = 32, rule: str = "engine"):
     x = x.float()
     shape = x.shape
     xb = x.reshape(-1, shape[-1] // block, block)
-    sb = block_exponent(xb.abs().amax(dim=-1), rule)
+    # include/srgd_hip.h, non-finite values: a NaN becomes the e4m3 NaN byte and takes no part in its block's maximum (the scale
+    # comes from the other elements, as fmaxf gives it on the device); an infinity is a maximum like any other (biased exponent
+    # 255 -> byte 247) and saturates to +-448
+    sb = block_exponent(torch.where(torch.isnan(xb), torch.zeros_like(xb), xb.abs()).amax(dim=-1), rule)
     inv = torch.ldexp(torch.ones_like(sb, dtype=torch.float32), (127 - sb.int()))             # 2^(127 - byte)
     scaled = (xb * inv[..., None]).clamp(-448.0, 448.0)
     q8 = scaled.to(torch.float8_e4m3fn)                                                         # RNE (inputs already saturated)

@@ -21,19 +21,30 @@ __global__ void iota_rows(int* r, int n) {
 }
 }  // namespace
 
-extern "C" {
-
-int srgd_k_conv2d_timed(const void* in0, const void* in1, int C0, int C1, int B, int Hin, int Win, int KS, int stride,
-                        int pad, int kind, const float* weight_oihw_host, const float* bias_host, int Cout, void* out,
-                        const void* residual, float* gn_partial, int groups, int is_bf16, int impl, int iters,
-                        float* avg_ms, int* stats_slots, const void* gn_tail_src, const float* gn_tail_a,
-                        const float* gn_tail_b, void* stream) {
+// The body behind srgd_k_conv2d_timed and srgd_k_conv2d_twin.  out_q / out_s: optional MX-fp8 twin of the output (ConvArgs::out_q).
+// in_ps0 > 0: the overlapping-window view of the 7x7 input convolution as engine.hip's run_init7 builds it - a KS x 1 kernel over
+// C0 "channels" whose pixels lie in_ps0 elements apart, Wout given by the caller (weights [Cout][C0][KS][1]); conv1x1_bf16 only.
+static int conv2d_body(const void* in0, const void* in1, int C0, int C1, int B, int Hin, int Win, int KS, int stride,
+                       int pad, int kind, const float* weight_oihw_host, const float* bias_host, int Cout, void* out,
+                       const void* residual, float* gn_partial, int groups, int is_bf16, int impl, int iters,
+                       float* avg_ms, int* stats_slots, const void* gn_tail_src, const float* gn_tail_a,
+                       const float* gn_tail_b, void* out_q, void* out_s, int in_ps0, int in_Wout, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const int Cin = C0 + C1;
   const int CoutPad = cdiv(Cout, conv_tile_n()) * conv_tile_n();
+  const bool window = in_ps0 > 0;
+  if (window && (impl != 3 || C1 || kind != 0 || stride != 1 || pad != 0 || in_Wout < 1 || Cout != CoutPad))
+    SRGD_FAIL("srgd_k_conv2d_twin: the overlapping-window form takes impl 3, one source, kind 0, stride 1, pad 0");
+  if ((out_q == nullptr) != (out_s == nullptr)) SRGD_FAIL("srgd_k_conv2d_twin: out_q and out_s come together");
   std::vector<unsigned char> packed;
   std::vector<float> bias;
-  pack_conv_weights(weight_oihw_host, bias_host, kind, Cin, Cout, CoutPad, KS, is_bf16 != 0, packed, bias);
+  if (window) {
+    bias.assign(Cout, 0.f);
+    if (bias_host) bias.assign(bias_host, bias_host + Cout);
+    packed.resize(16);
+  } else {
+    pack_conv_weights(weight_oihw_host, bias_host, kind, Cin, Cout, CoutPad, KS, is_bf16 != 0, packed, bias);
+  }
   DevBuf dw, db, dw3, dw1;
   SRGD_TRY(dw.alloc(packed.size()));
   SRGD_HIP(hipMemcpy(dw.p, packed.data(), packed.size(), hipMemcpyHostToDevice));
@@ -47,7 +58,8 @@ int srgd_k_conv2d_timed(const void* in0, const void* in1, int C0, int C1, int B,
   a.Wout = (Win + 2 * pad - KS) / stride + 1;
   a.KH = KS; a.KW = KS; a.stride = stride; a.pad = pad; a.w = dw.p; a.bias = (const float*)db.p; a.Cout = Cout; a.CoutPad = CoutPad;
   a.out = out; a.residual = residual; a.mode = kind == 2 ? CONV_PIXEL_SHUFFLE_SILU : CONV_PLAIN;
-  a.gn_partial = gn_partial; a.groups = groups;
+  a.gn_partial = gn_partial; a.groups = groups; a.out_q = out_q; a.out_s = out_s;
+  if (window) { a.ps0 = in_ps0; a.KW = 1; a.Wout = in_Wout; }
   a.gn_res_src = gn_tail_src; a.gn_res_a = gn_tail_src ? gn_tail_a : nullptr; a.gn_res_b = gn_tail_src ? gn_tail_b : nullptr;
   if (gn_tail_src && (!gn_tail_a || !gn_tail_b)) SRGD_FAIL("srgd_k_conv2d: gn_tail_src needs gn_tail_a and gn_tail_b");
   // impl 5: conv3x3_bf16 with the producer's GroupNorm + SiLU applied while the input is staged (GNIN): gn_tail_a / gn_tail_b
@@ -62,12 +74,21 @@ int srgd_k_conv2d_timed(const void* in0, const void* in1, int C0, int C1, int B,
   if (impl == 2 && !fast) SRGD_FAIL("srgd_k_conv2d: the conv3x3_bf16 fast path does not cover this shape");
   const bool fast1 = !fast && (impl == 0 || impl == 3) && is_bf16 && conv1x1_bf16_eligible(a);
   if (impl == 3 && !fast1) SRGD_FAIL("srgd_k_conv2d: the conv1x1_bf16 fast path does not cover this shape");
+  if (out_q && !(fast1 || impl == 4)) SRGD_FAIL("srgd_k_conv2d_twin: the selected kernel writes no MX-fp8 twin (impl 3 or 4 does)");
   if (fast1) {
     std::vector<unsigned char> f32p;
     std::vector<float> unused;
-    pack_conv_weights(weight_oihw_host, bias_host, kind, Cin, Cout, CoutPad, KS, false, f32p, unused);
+    if (window) {                                  // [Cout][C0][KS][1] -> [tap][Cout][C0]
+      f32p.resize((size_t)KS * Cout * C0 * 4);
+      float* d = reinterpret_cast<float*>(f32p.data());
+      for (int t = 0; t < KS; ++t)
+        for (int o = 0; o < Cout; ++o)
+          for (int c = 0; c < C0; ++c) d[((size_t)t * Cout + o) * C0 + c] = weight_oihw_host[((size_t)o * C0 + c) * KS + t];
+    } else {
+      pack_conv_weights(weight_oihw_host, bias_host, kind, Cin, Cout, CoutPad, KS, false, f32p, unused);
+    }
     std::vector<unsigned short> p1;
-    pack_conv1x1_bf16(reinterpret_cast<const float*>(f32p.data()), KS * KS, Cin, Cout, p1, f32_to_bf16_host);
+    pack_conv1x1_bf16(reinterpret_cast<const float*>(f32p.data()), window ? KS : KS * KS, Cin, Cout, p1, f32_to_bf16_host);
     SRGD_TRY(dw1.alloc(p1.size() * 2));
     SRGD_HIP(hipMemcpy(dw1.p, p1.data(), p1.size() * 2, hipMemcpyHostToDevice));
   }
@@ -165,6 +186,29 @@ int srgd_k_conv2d_timed(const void* in0, const void* in1, int C0, int C1, int B,
   return 0;
 }
 
+extern "C" {
+
+int srgd_k_conv2d_timed(const void* in0, const void* in1, int C0, int C1, int B, int Hin, int Win, int KS, int stride,
+                        int pad, int kind, const float* weight_oihw_host, const float* bias_host, int Cout, void* out,
+                        const void* residual, float* gn_partial, int groups, int is_bf16, int impl, int iters,
+                        float* avg_ms, int* stats_slots, const void* gn_tail_src, const float* gn_tail_a,
+                        const float* gn_tail_b, void* stream) {
+  return conv2d_body(in0, in1, C0, C1, B, Hin, Win, KS, stride, pad, kind, weight_oihw_host, bias_host, Cout, out, residual,
+                     gn_partial, groups, is_bf16, impl, iters, avg_ms, stats_slots, gn_tail_src, gn_tail_a, gn_tail_b, nullptr,
+                     nullptr, 0, 0, stream);
+}
+
+int srgd_k_conv2d_twin(const void* in0, const void* in1, int C0, int C1, int B, int Hin, int Win, int KS, int stride,
+                       int pad, int kind, const float* weight_oihw_host, const float* bias_host, int Cout, void* out,
+                       const void* residual, float* gn_partial, int groups, int is_bf16, int impl, int* stats_slots,
+                       const void* gn_tail_src, const float* gn_tail_a, const float* gn_tail_b, void* out_q, void* out_s,
+                       int ps0, int Wout, void* stream) {
+  if (!out_q || !out_s) SRGD_FAIL("srgd_k_conv2d_twin: out_q and out_s are required");
+  return conv2d_body(in0, in1, C0, C1, B, Hin, Win, KS, stride, pad, kind, weight_oihw_host, bias_host, Cout, out, residual,
+                     gn_partial, groups, is_bf16, impl, 0, nullptr, stats_slots, gn_tail_src, gn_tail_a, gn_tail_b, out_q, out_s,
+                     ps0, Wout, stream);
+}
+
 int srgd_k_conv2d(const void* in0, const void* in1, int C0, int C1, int B, int Hin, int Win, int KS, int stride,
                   int pad, int kind, const float* weight_oihw_host, const float* bias_host, int Cout, void* out,
                   const void* residual, float* gn_partial, int groups, int is_bf16, void* stream) {
@@ -173,9 +217,9 @@ int srgd_k_conv2d(const void* in0, const void* in1, int C0, int C1, int B, int H
                              stream);
 }
 
-int srgd_k_groupnorm_silu(const void* x, void* y, const void* residual, const float* gn_partial, int B, int hw,
-                          int C, int groups, const float* gamma, const float* beta, const float* scale_shift,
-                          int nslots, int is_bf16, void* stream) {
+static int groupnorm_silu_body(const void* x, void* y, const void* residual, const float* gn_partial, int B, int hw,
+                               int C, int groups, const float* gamma, const float* beta, const float* scale_shift,
+                               int nslots, int is_bf16, void* out_q, void* out_s, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   if (nslots <= 0) SRGD_FAIL("groupnorm: nslots must be the slot count the producing conv reported");
   DevBuf cA, cB, rows;
@@ -189,9 +233,24 @@ int srgd_k_groupnorm_silu(const void* x, void* y, const void* residual, const fl
   f.step_mul = 0; f.ss_stride = 2 * C; f.ss_offset = 0; f.eps = 1e-5f; f.coefA = (float*)cA.p; f.coefB = (float*)cB.p;
   f.x = x; f.x_is_bf16 = is_bf16 != 0;
   SRGD_TRY(gn_finalize(f, st));
-  SRGD_TRY(gn_apply_silu(x, y, residual, (const float*)cA.p, (const float*)cB.p, B, hw, C, is_bf16 != 0, st));
+  SRGD_TRY(gn_apply_silu(x, y, residual, (const float*)cA.p, (const float*)cB.p, B, hw, C, is_bf16 != 0, st, out_q, out_s));
   SRGD_HIP(hipStreamSynchronize(st));
   return 0;
+}
+
+int srgd_k_groupnorm_silu(const void* x, void* y, const void* residual, const float* gn_partial, int B, int hw,
+                          int C, int groups, const float* gamma, const float* beta, const float* scale_shift,
+                          int nslots, int is_bf16, void* stream) {
+  return groupnorm_silu_body(x, y, residual, gn_partial, B, hw, C, groups, gamma, beta, scale_shift, nslots, is_bf16, nullptr,
+                             nullptr, stream);
+}
+
+int srgd_k_groupnorm_silu_twin(const void* x, void* y, const void* residual, const float* gn_partial, int B, int hw,
+                               int C, int groups, const float* gamma, const float* beta, const float* scale_shift,
+                               int nslots, int is_bf16, void* out_q, void* out_s, void* stream) {
+  if (!out_q || !out_s) SRGD_FAIL("srgd_k_groupnorm_silu_twin: out_q and out_s are required");
+  return groupnorm_silu_body(x, y, residual, gn_partial, B, hw, C, groups, gamma, beta, scale_shift, nslots, is_bf16, out_q, out_s,
+                             stream);
 }
 
 int srgd_k_rmsnorm(const void* x, void* y, const void* residual, const float* g, int64_t npix, int C, int is_bf16,
@@ -290,12 +349,20 @@ int srgd_k_quant_mxfp8(const void* x_bf16, void* q, void* s, int64_t npix, int C
   return quant_mxfp8(x_bf16, q, s, (long)npix, C, (hipStream_t)stream);
 }
 
-int srgd_k_conv3x3_mxfp8(const void* in0, const void* in1, int C0, int C1, int B, int H, int W,
-                         const float* weight_oihw_host, const float* bias_host, int Cout, void* out, float* gn_partial,
-                         int groups, int iters, float* avg_ms, int* stats_slots, void* stream) {
+int srgd_k_gn_apply_silu_mxfp8(const void* x_bf16, void* q, void* s, const float* coefA, const float* coefB, int B, int hw,
+                               int C, void* stream) {
+  if (!x_bf16 || !q || !s) SRGD_FAIL("srgd_k_gn_apply_silu_mxfp8: null argument");
+  if (B < 1 || hw < 1) SRGD_FAIL("srgd_k_gn_apply_silu_mxfp8: empty tensor");
+  return gn_apply_silu_mxfp8(x_bf16, q, s, coefA, coefB, B, hw, C, (hipStream_t)stream);
+}
+
+static int conv3x3_mxfp8_body(const void* in0, const void* in1, int C0, int C1, int B, int H, int W,
+                              const float* weight_oihw_host, const float* bias_host, int Cout, void* out, float* gn_partial,
+                              int groups, int iters, float* avg_ms, int* stats_slots, void* out_q, void* out_s, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   if (!in0 || !weight_oihw_host || !out) SRGD_FAIL("srgd_k_conv3x3_mxfp8: null argument");
   ConvArgs a{};
+  a.out_q = out_q; a.out_s = out_s;
   a.C0 = C0; a.C1 = in1 ? C1 : 0; a.ps0 = C0; a.ps1 = a.C1; a.B = B; a.Hin = H; a.Win = W; a.Hout = H; a.Wout = W;
   a.KH = a.KW = 3; a.stride = 1; a.pad = 1; a.Cout = Cout; a.CoutPad = Cout; a.out = out; a.mode = CONV_PLAIN;
   a.gn_partial = gn_partial; a.groups = groups;
@@ -333,6 +400,21 @@ int srgd_k_conv3x3_mxfp8(const void* in0, const void* in1, int C0, int C1, int B
   }
   SRGD_HIP(hipStreamSynchronize(st));
   return 0;
+}
+
+int srgd_k_conv3x3_mxfp8(const void* in0, const void* in1, int C0, int C1, int B, int H, int W,
+                         const float* weight_oihw_host, const float* bias_host, int Cout, void* out, float* gn_partial,
+                         int groups, int iters, float* avg_ms, int* stats_slots, void* stream) {
+  return conv3x3_mxfp8_body(in0, in1, C0, C1, B, H, W, weight_oihw_host, bias_host, Cout, out, gn_partial, groups, iters, avg_ms,
+                            stats_slots, nullptr, nullptr, stream);
+}
+
+int srgd_k_conv3x3_mxfp8_twin(const void* in0, const void* in1, int C0, int C1, int B, int H, int W,
+                              const float* weight_oihw_host, const float* bias_host, int Cout, void* out, float* gn_partial,
+                              int groups, int iters, float* avg_ms, int* stats_slots, void* out_q, void* out_s, void* stream) {
+  if (!out_q || !out_s) SRGD_FAIL("srgd_k_conv3x3_mxfp8_twin: out_q and out_s are required");
+  return conv3x3_mxfp8_body(in0, in1, C0, C1, B, H, W, weight_oihw_host, bias_host, Cout, out, gn_partial, groups, iters, avg_ms,
+                            stats_slots, out_q, out_s, stream);
 }
 
 int srgd_k_full_attention(const void* qkv, void* out, int B, int N, int heads, int is_bf16, void* stream) {

@@ -516,6 +516,7 @@ def test_kernel_chains_match_reference_submodules_fp32():
 # ------------------------------------------------------------------ MX-fp8 (BASELINE configs[4] compute path)
 def test_quant_mxfp8_is_bit_exact_with_the_format_emulation():
     # quant_mxfp8.hip vs oracle/mxfp8.py (OCP MX format; E8M0 = floor(log2 amax) - 8, + 1 when the block maximum would saturate; e4m3 RNE): every byte equal.
+    # (one random tensor, one launch shape; the designed value sweep and every launch branch are in tests/test_mxfp8_exact_gpu.py)
     from oracle import mxfp8 as MX
     lib = L().lib()
     g = torch.Generator().manual_seed(31)
@@ -559,11 +560,16 @@ def test_quant_mxfp8_keeps_a_nan_visible():
     wq, ws, _ = MX.quantize(clean)
     keep = torch.ones(npix, C, dtype=torch.bool)
     keep[3, 5] = False
-    keep[9, 32:] = False                                   # the infinity's block: its scale byte saturates, checked below
+    keep[9, 32:] = False                                   # the infinity's block: its scale byte is 247, checked at the end
     assert torch.equal(s[:, 0], ws[:, 0]) and torch.equal(s[torch.arange(npix) != 9, 1], ws[torch.arange(npix) != 9, 1])
     assert torch.equal(q[keep], wq[keep])
     assert q[9, 40] == 0x7e                                # +448, the largest finite e4m3 value
     assert torch.isfinite(q.view(torch.float8_e4m3fn).float()[keep]).all()
+    # the infinity's block: the scale byte comes from the infinity's exponent field (255 - 8) and the finite elements beside it
+    # are scaled by 2^-120 like those of any block; the oracle follows the same rule (tests/test_mxfp8_exact_gpu.py sweeps it)
+    iq, isc, _ = MX.quantize(x.float())
+    assert int(s[9, 1]) == 247 == int(isc[9, 1])
+    assert torch.equal(q[9, 32:], iq[9, 32:])
 
 
 def _mx_conv_reference(x0, x1, w, b):
