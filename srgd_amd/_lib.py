@@ -162,24 +162,34 @@ class SrgdHipError(RuntimeError):
     pass
 
 
+def load(path: str, prototypes: dict, what: str) -> C.CDLL:
+    """Open the built library ``path`` and bind ``prototypes`` (name -> (restype, argtypes)).  Raises if it has not been built:
+    ``what`` says what runs there only - there is no CPU fallback."""
+    if not os.path.exists(path):
+        raise SrgdHipError(f"{path} is missing: build it with `python -m srgd_amd.build` (hipcc, gfx950). "
+                           f"{what}; there is no CPU fallback.")
+    handle = C.CDLL(path)
+    for name, (res, args) in prototypes.items():
+        fn = getattr(handle, name)            # AttributeError if the library lacks a declared symbol
+        fn.restype = res
+        fn.argtypes = args
+    return handle
+
+
+def error_of(handle: C.CDLL, symbol: str, what: str = "") -> SrgdHipError:
+    """The ``SrgdHipError`` of a failed call: the message of the library's last-error function ``symbol``."""
+    msg = getattr(handle, symbol)().decode(errors="replace")
+    return SrgdHipError(f"{what}: {msg}" if what else msg)
+
+
 def lib() -> C.CDLL:
     """Load the engine library (once).  Raises if it has not been built - no CPU fallback."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise SrgdHipError(
-                f"{LIB_PATH} is missing: build it with `python -m srgd_amd.build` (hipcc, gfx950). "
-                "The MI355X engine is the only implementation of this path; there is no CPU fallback.")
-        handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in PROTOTYPES.items():
-            fn = getattr(handle, name)            # AttributeError if the library lacks a declared symbol
-            fn.restype = res
-            fn.argtypes = args
-        _lib = handle
+        _lib = load(LIB_PATH, PROTOTYPES, "The MI355X engine is the only implementation of this path")
     return _lib
 
 
 def check(rc: int, what: str = "") -> None:
     if rc != 0:
-        msg = lib().srgd_last_error().decode(errors="replace")
-        raise SrgdHipError(f"{what}: {msg}" if what else msg)
+        raise error_of(lib(), "srgd_last_error", what)

@@ -49,20 +49,12 @@ def lib() -> C.CDLL:
     """Load the alpha library (once).  Raises if it has not been built - no CPU fallback."""
     global _handle
     if _handle is None:
-        if not os.path.exists(LIB_PATH):
-            raise _lib.SrgdHipError(f"{LIB_PATH} is missing: build it with `python -m srgd_amd.build` (hipcc, gfx950). "
-                                    "The alpha kernels run on the MI355X only; there is no CPU fallback.")
-        handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in PROTOTYPES.items():
-            fn = getattr(handle, name)
-            fn.restype = res
-            fn.argtypes = args
-        _handle = handle
+        _handle = _lib.load(LIB_PATH, PROTOTYPES, "The alpha kernels run on the MI355X only")
     return _handle
 
 
-def _last_error():
-    return lib().srgd_alpha_last_error().decode(errors="replace")
+def _error():
+    return _lib.error_of(lib(), "srgd_alpha_last_error")
 
 
 def check_mode(mode):
@@ -169,7 +161,7 @@ def resize_planes_flat(src, src_offsets, dst, dst_offsets, sizes, filter="bicubi
                                             C.c_void_p(tables.data_ptr()), 4 * tables.numel(), C.c_void_p(scratch.data_ptr()),
                                             scratch.numel(), C.c_void_p(torch.cuda.current_stream().cuda_stream))
     if rc != 0:
-        raise _lib.SrgdHipError(_last_error())
+        raise _error()
     return dst
 
 
@@ -187,7 +179,7 @@ def pack_rgba_flat(rgb, rgb_offsets, alpha, alpha_offsets, rgba, rgba_offsets, s
         rc = lib().srgd_alpha_pack_rgba(C.c_void_p(rgb.data_ptr()), C.c_void_p(alpha.data_ptr()), C.c_void_p(rgba.data_ptr()), images, n,
                                         C.c_void_p(torch.cuda.current_stream().cuda_stream))
     if rc != 0:
-        raise _lib.SrgdHipError(_last_error())
+        raise _error()
     return rgba
 
 
@@ -207,7 +199,7 @@ def bleed_flat(rgba, rgba_offsets, rgb, rgb_offsets, sizes, passes):
         rc = lib().srgd_alpha_bleed(C.c_void_p(rgba.data_ptr()), C.c_void_p(rgb.data_ptr()), images, n, passes,
                                     C.c_void_p(scratch.data_ptr()), scratch.numel(), C.c_void_p(torch.cuda.current_stream().cuda_stream))
     if rc != 0:
-        raise _lib.SrgdHipError(_last_error())
+        raise _error()
     return rgb
 
 

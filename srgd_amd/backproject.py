@@ -34,15 +34,7 @@ def lib() -> C.CDLL:
     """Load the back-projection library (once).  Raises if it has not been built - no CPU fallback."""
     global _handle
     if _handle is None:
-        if not os.path.exists(LIB_PATH):
-            raise _lib.SrgdHipError(f"{LIB_PATH} is missing: build it with `python -m srgd_amd.build` (hipcc, gfx950). "
-                                    "The back-projection runs on the MI355X only; there is no CPU fallback.")
-        handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in PROTOTYPES.items():
-            fn = getattr(handle, name)
-            fn.restype = res
-            fn.argtypes = args
-        _handle = handle
+        _handle = _lib.load(LIB_PATH, PROTOTYPES, "The back-projection runs on the MI355X only")
     return _handle
 
 
@@ -51,7 +43,7 @@ def coeffs():
     indices 0 .. 5, the four phases of the interior, output indices 4n-6 .. 4n-1 - each from its first tap on, zero beyond its last."""
     out = ((C.c_int32 * 4) * 16)()
     if lib().srgd_image_backproject_coeffs(C.cast(out, C.c_void_p)) != 0:
-        raise _lib.SrgdHipError(lib().srgd_image_backproject_last_error().decode(errors="replace"))
+        raise _lib.error_of(lib(), "srgd_image_backproject_last_error")
     return [list(row) for row in out]
 
 
@@ -115,7 +107,7 @@ def back_project_flat(out, cond, offsets, sizes, iterations, dst=None):
                                                  C.c_void_p(dst.data_ptr()), C.c_void_p(scratch.data_ptr()),
                                                  C.c_void_p(torch.cuda.current_stream().cuda_stream))
     if rc != 0:
-        raise _lib.SrgdHipError(lib().srgd_image_backproject_last_error().decode(errors="replace"))
+        raise _lib.error_of(lib(), "srgd_image_backproject_last_error")
     return dst
 
 

@@ -36,15 +36,7 @@ def lib() -> C.CDLL:
     """Load the consistency library (once).  Raises if it has not been built - no CPU fallback."""
     global _handle
     if _handle is None:
-        if not os.path.exists(LIB_PATH):
-            raise _lib.SrgdHipError(f"{LIB_PATH} is missing: build it with `python -m srgd_amd.build` (hipcc, gfx950). "
-                                    "The consistency runs on the MI355X only; there is no CPU fallback.")
-        handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in PROTOTYPES.items():
-            fn = getattr(handle, name)
-            fn.restype = res
-            fn.argtypes = args
-        _handle = handle
+        _handle = _lib.load(LIB_PATH, PROTOTYPES, "The consistency runs on the MI355X only")
     return _handle
 
 
@@ -58,7 +50,7 @@ def coeffs():
     interior, n-2, n-1, each from its first tap on, zero beyond its last."""
     out = ((C.c_int32 * 16) * 5)()
     if lib().srgd_image_consistency_coeffs(C.cast(out, C.c_void_p)) != 0:
-        raise _lib.SrgdHipError(lib().srgd_image_consistency_last_error().decode(errors="replace"))
+        raise _lib.error_of(lib(), "srgd_image_consistency_last_error")
     return [list(row) for row in out]
 
 
@@ -105,7 +97,7 @@ def consistency_flat_device(hr_u8, hr_offsets, lr_u8, lr_offsets, sizes, down_u8
                                                  C.c_void_p(stats.data_ptr()), C.c_void_p(scratch.data_ptr()),
                                                  C.c_void_p(torch.cuda.current_stream().cuda_stream))
     if rc != 0:
-        raise _lib.SrgdHipError(lib().srgd_image_consistency_last_error().decode(errors="replace"))
+        raise _lib.error_of(lib(), "srgd_image_consistency_last_error")
     return stats
 
 

@@ -30,19 +30,13 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/srgd_alpha.h"
+#include "ext_common.hpp"
 
-// This file is a library of its own (libsrgd_alpha.so, include/srgd_alpha.h): it shares no symbol with the other eight.
+// This file is a library of its own (libsrgd_alpha.so, include/srgd_alpha.h): it shares no symbol with the engine or the other nine
+// extension libraries; ext_common.hpp is their common host plumbing.
 namespace srgd {
 namespace {
 
-thread_local std::string g_err;
-#define AL_FAIL(msg)             \
-  do {                           \
-    g_err = std::string(msg);    \
-    return -1;                   \
-  } while (0)
-
-constexpr int AL_PREC_BITS = 32 - 8 - 2;
 constexpr int AL_THREADS = 256;
 constexpr int AL_MAX_IMAGES = 128;                   // records travel as a kernel argument
 constexpr int AL_MAX_TAPS = SRGD_ALPHA_MAX_TAPS;
@@ -67,11 +61,6 @@ struct AlImage {                                     // pack: colour, plane, RGB
 };
 struct AlImageTable { AlImage im[AL_MAX_IMAGES]; };
 static_assert(sizeof(AlPlaneTable) <= 3584 && sizeof(AlImageTable) <= 3584, "the records and the pointers stay below 4 KiB of kernel arguments");
-
-__device__ __forceinline__ int al_clip8(int acc) {
-  const int v = acc >> AL_PREC_BITS;                 // arithmetic shift, as Pillow's clip8 lookup index
-  return v < 0 ? 0 : (v > 255 ? 255 : v);
-}
 
 // Horizontal pass: src -> scratch (-> dst where the vertical pass is skipped).
 __global__ __launch_bounds__(AL_THREADS) void alpha_plane_horizontal_kernel(AlPlaneTable tab, const unsigned char* __restrict__ src,
@@ -128,14 +117,14 @@ __global__ __launch_bounds__(AL_THREADS) void alpha_plane_horizontal_kernel(AlPl
       const int count = max(min(min(bnd[2 * x + 1], kh), span - off), 0);            // every tap lies inside the staged span
       const unsigned char* p = rows + rg * AL_HSPAN + off;
       const int* k = kk + x * kh;
-      int acc[4] = {1 << (AL_PREC_BITS - 1), 1 << (AL_PREC_BITS - 1), 1 << (AL_PREC_BITS - 1), 1 << (AL_PREC_BITS - 1)};
+      int acc[4] = {1 << (PILLOW_PREC_BITS - 1), 1 << (PILLOW_PREC_BITS - 1), 1 << (PILLOW_PREC_BITS - 1), 1 << (PILLOW_PREC_BITS - 1)};
       for (int t = 0; t < count; ++t) {
         const int kt = k[t];
 #pragma unroll
         for (int q = 0; q < 4; ++q) acc[q] += kt * (int)p[q * (AL_HR / 4) * AL_HSPAN + t];
       }
 #pragma unroll
-      for (int q = 0; q < 4; ++q) res[(rg + q * (AL_HR / 4)) * AL_HW + x] = (unsigned char)al_clip8(acc[q]);
+      for (int q = 0; q < 4; ++q) res[(rg + q * (AL_HR / 4)) * AL_HW + x] = (unsigned char)clip8(acc[q]);
     }
   }
   __syncthreads();
@@ -190,10 +179,10 @@ __global__ __launch_bounds__(AL_THREADS) void alpha_plane_vertical_kernel(AlPlan
     const int ymin = kv != 0 ? min(max(bnd[2 * r], 0), h_in - 1) : yo;
     const int count = kv != 0 ? max(min(min(bnd[2 * r + 1], kv), h_in - ymin), 0) : 1;
     const int* k = kk + r * kv;
-    int acc[4] = {1 << (AL_PREC_BITS - 1), 1 << (AL_PREC_BITS - 1), 1 << (AL_PREC_BITS - 1), 1 << (AL_PREC_BITS - 1)};
+    int acc[4] = {1 << (PILLOW_PREC_BITS - 1), 1 << (PILLOW_PREC_BITS - 1), 1 << (PILLOW_PREC_BITS - 1), 1 << (PILLOW_PREC_BITS - 1)};
     const unsigned char* p = in + (size_t)ymin * (size_t)row_bytes + (size_t)gb;
     for (int t = 0; t < count; ++t, p += row_bytes) {
-      const int kt = kv != 0 ? k[t] : 1 << AL_PREC_BITS;
+      const int kt = kv != 0 ? k[t] : 1 << PILLOW_PREC_BITS;
       unsigned d = 0u;
       if (dwords) {
         d = *reinterpret_cast<const unsigned*>(p);
@@ -208,12 +197,12 @@ __global__ __launch_bounds__(AL_THREADS) void alpha_plane_vertical_kernel(AlPlan
     }
     unsigned char* o = out + (size_t)yo * (size_t)row_bytes + (size_t)gb;
     if (dwords) {
-      *reinterpret_cast<unsigned*>(o) = (unsigned)al_clip8(acc[0]) | (unsigned)al_clip8(acc[1]) << 8 | (unsigned)al_clip8(acc[2]) << 16 |
-                                        (unsigned)al_clip8(acc[3]) << 24;
+      *reinterpret_cast<unsigned*>(o) = (unsigned)clip8(acc[0]) | (unsigned)clip8(acc[1]) << 8 | (unsigned)clip8(acc[2]) << 16 |
+                                        (unsigned)clip8(acc[3]) << 24;
     } else {
 #pragma unroll
       for (int b = 0; b < 4; ++b) {
-        if (b < nbytes) o[b] = (unsigned char)al_clip8(acc[b]);
+        if (b < nbytes) o[b] = (unsigned char)clip8(acc[b]);
       }
     }
   }
@@ -314,8 +303,6 @@ __global__ __launch_bounds__(AL_THREADS) void alpha_bleed_store_kernel(AlImageTa
 }
 
 // ------------------------------------------------------------------------------------------------ host
-inline long long round16(long long n) { return (n + 15) & ~15ll; }
-
 const char* size_problem(long long a, long long b) {
   if (a < 1 || b < 1 || a > SRGD_ALPHA_MAX_SIDE || b > SRGD_ALPHA_MAX_SIDE) return "bad size (every size is in 1 .. 16384)";
   return nullptr;
@@ -333,53 +320,37 @@ const char* offset_problem(long long off) {
   return nullptr;
 }
 
-// the byte range that a set of images covers in a buffer, and whether two such ranges meet
-struct Range {
-  long long lo = 0, hi = 0;
-  bool any = false;
-  void add(long long off, long long bytes) {
-    lo = any ? std::min(lo, off) : off;
-    hi = any ? std::max(hi, off + bytes) : off + bytes;
-    any = true;
-  }
-  bool meets(const void* base, const Range& other, const void* other_base) const {
-    const long long a0 = (long long)(intptr_t)base + lo, a1 = (long long)(intptr_t)base + hi;
-    const long long b0 = (long long)(intptr_t)other_base + other.lo, b1 = (long long)(intptr_t)other_base + other.hi;
-    return a0 < b1 && b0 < a1;
-  }
-};
-
 int resize_planes(const void* src, void* dst, const srgd_alpha_plane* planes, int n_planes, const void* tables, long long tables_bytes,
                   void* scratch, long long scratch_bytes, hipStream_t st) {
   const std::string name("srgd_alpha_resize_planes");
-  if (n_planes < 1) AL_FAIL(name + ": n_planes must be >= 1");
-  if (!src || !dst || !planes || !tables || !scratch) AL_FAIL(name + ": null argument");
-  if (((uintptr_t)scratch & 15u) != 0) AL_FAIL(name + ": scratch must be 16-byte aligned");
-  if (((uintptr_t)tables & 15u) != 0) AL_FAIL(name + ": tables must be 16-byte aligned");
-  if ((((uintptr_t)src | (uintptr_t)dst) & 15u) != 0) AL_FAIL(name + ": src and dst must be 16-byte aligned");
+  if (n_planes < 1) SRGD_EXT_FAIL(name + ": n_planes must be >= 1");
+  if (!src || !dst || !planes || !tables || !scratch) SRGD_EXT_FAIL(name + ": null argument");
+  if (((uintptr_t)scratch & 15u) != 0) SRGD_EXT_FAIL(name + ": scratch must be 16-byte aligned");
+  if (((uintptr_t)tables & 15u) != 0) SRGD_EXT_FAIL(name + ": tables must be 16-byte aligned");
+  if ((((uintptr_t)src | (uintptr_t)dst) & 15u) != 0) SRGD_EXT_FAIL(name + ": src and dst must be 16-byte aligned");
   long long scr = 0;
   Range s, d;
   for (int i = 0; i < n_planes; ++i) {                   // every plane is checked before the first launch
     const srgd_alpha_plane& im = planes[i];
     const char* problem = axis_problem(im.h_in, im.h_out);
     if (!problem) problem = axis_problem(im.w_in, im.w_out);
-    if (problem) AL_FAIL(name + ": " + problem);
+    if (problem) SRGD_EXT_FAIL(name + ": " + problem);
     for (const long long off : {(long long)im.src_off, (long long)im.dst_off, (long long)im.tab_off}) {
-      if (const char* p = offset_problem(off)) AL_FAIL(name + ": " + p);
+      if (const char* p = offset_problem(off)) SRGD_EXT_FAIL(name + ": " + p);
     }
     if ((im.w_in != im.w_out && (im.k_h < 1 || im.k_h > AL_MAX_TAPS)) || (im.h_in != im.h_out && (im.k_v < 1 || im.k_v > AL_MAX_TAPS)))
-      AL_FAIL(name + ": ksize outside 1 .. 49 (k_h, k_v: srgd_resize_ksize of the two tables)");
+      SRGD_EXT_FAIL(name + ": ksize outside 1 .. 49 (k_h, k_v: srgd_resize_ksize of the two tables)");
     long long need = 0;                                  // bytes of the plane's tables
     if (im.w_in != im.w_out) need += 4ll * im.w_out * (2 + im.k_h);
     if (im.h_in != im.h_out) need += 4ll * im.h_out * (2 + im.k_v);
-    if (im.tab_off + need > tables_bytes) AL_FAIL(name + ": tables_bytes is too small for the planes' tables");
-    scr += round16((long long)im.h_in * im.w_out);
+    if (im.tab_off + need > tables_bytes) SRGD_EXT_FAIL(name + ": tables_bytes is too small for the planes' tables");
+    scr += round_up((long long)im.h_in * im.w_out, 16ll);
     s.add(im.src_off, (long long)im.h_in * im.w_in);
     d.add(im.dst_off, (long long)im.h_out * im.w_out);
   }
-  if (scr > scratch_bytes) AL_FAIL(name + ": scratch_bytes is too small (sum of h_in * w_out, each rounded up to 16)");
-  if (scr > (1ll << 36)) AL_FAIL(name + ": scratch beyond 2^36 bytes");
-  if (s.meets(src, d, dst)) AL_FAIL(name + ": the source planes and the destination planes overlap");
+  if (scr > scratch_bytes) SRGD_EXT_FAIL(name + ": scratch_bytes is too small (sum of h_in * w_out, each rounded up to 16)");
+  if (scr > (1ll << 36)) SRGD_EXT_FAIL(name + ": scratch beyond 2^36 bytes");
+  if (s.meets(src, d, dst)) SRGD_EXT_FAIL(name + ": the source planes and the destination planes overlap");
   scr = 0;                                               // the planes' scratch, packed in plane order
   for (int first = 0; first < n_planes; first += AL_MAX_IMAGES) {     // one launch sequence per AL_MAX_IMAGES planes
     const int cnt = std::min(AL_MAX_IMAGES, n_planes - first);
@@ -392,7 +363,7 @@ int resize_planes(const void* src, void* dst, const srgd_alpha_plane* planes, in
       tab.im[k] = AlPlane{(unsigned)(im.src_off >> 4), (unsigned)(im.dst_off >> 4), (unsigned)(scr >> 4), (unsigned)(im.tab_off >> 4),
                           (unsigned short)im.h_in, (unsigned short)im.w_in, (unsigned short)im.h_out, (unsigned short)im.w_out,
                           (unsigned char)kh, (unsigned char)kv, 0, 0};
-      scr += round16((long long)im.h_in * im.w_out);
+      scr += round_up((long long)im.h_in * im.w_out, 16ll);
       if (kh != 0) h_tiles = std::max(h_tiles, (unsigned)((im.w_out + AL_HW - 1) / AL_HW) * (unsigned)((im.h_in + AL_HR - 1) / AL_HR));
       if (kv != 0 || kh == 0)
         v_tiles = std::max(v_tiles, (unsigned)((im.w_out + AL_VB - 1) / AL_VB) * (unsigned)((im.h_out + AL_VR - 1) / AL_VR));
@@ -404,29 +375,29 @@ int resize_planes(const void* src, void* dst, const srgd_alpha_plane* planes, in
       hipLaunchKernelGGL(alpha_plane_vertical_kernel, dim3(v_tiles, (unsigned)cnt), dim3(AL_THREADS), 0, st, tab, (const unsigned char*)src,
                          (const unsigned char*)scratch, (unsigned char*)dst, (const unsigned char*)tables);
     const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) AL_FAIL(name + ": " + hipGetErrorString(err));
+    if (err != hipSuccess) SRGD_EXT_FAIL(name + ": " + hipGetErrorString(err));
   }
   return 0;
 }
 
 int pack_rgba(const void* rgb, const void* alpha, void* rgba, const srgd_alpha_image* images, int n_images, hipStream_t st) {
   const std::string name("srgd_alpha_pack_rgba");
-  if (n_images < 1) AL_FAIL(name + ": n_images must be >= 1");
-  if (!rgb || !alpha || !rgba || !images) AL_FAIL(name + ": null argument");
-  if ((((uintptr_t)rgb | (uintptr_t)alpha | (uintptr_t)rgba) & 15u) != 0) AL_FAIL(name + ": rgb, alpha and rgba must be 16-byte aligned");
+  if (n_images < 1) SRGD_EXT_FAIL(name + ": n_images must be >= 1");
+  if (!rgb || !alpha || !rgba || !images) SRGD_EXT_FAIL(name + ": null argument");
+  if ((((uintptr_t)rgb | (uintptr_t)alpha | (uintptr_t)rgba) & 15u) != 0) SRGD_EXT_FAIL(name + ": rgb, alpha and rgba must be 16-byte aligned");
   Range c, a, d;
   for (int i = 0; i < n_images; ++i) {                   // every image is checked before the first launch
     const srgd_alpha_image& im = images[i];
-    if (const char* problem = size_problem(im.h, im.w)) AL_FAIL(name + ": " + problem);
+    if (const char* problem = size_problem(im.h, im.w)) SRGD_EXT_FAIL(name + ": " + problem);
     for (const long long off : {(long long)im.rgb_off, (long long)im.a_off, (long long)im.rgba_off}) {
-      if (const char* p = offset_problem(off)) AL_FAIL(name + ": " + p);
+      if (const char* p = offset_problem(off)) SRGD_EXT_FAIL(name + ": " + p);
     }
     const long long n = (long long)im.h * im.w;
     c.add(im.rgb_off, 3 * n);
     a.add(im.a_off, n);
     d.add(im.rgba_off, 4 * n);
   }
-  if (d.meets(rgba, c, rgb) || d.meets(rgba, a, alpha)) AL_FAIL(name + ": the destination images overlap the colour or the planes");
+  if (d.meets(rgba, c, rgb) || d.meets(rgba, a, alpha)) SRGD_EXT_FAIL(name + ": the destination images overlap the colour or the planes");
   for (int first = 0; first < n_images; first += AL_MAX_IMAGES) {
     const int cnt = std::min(AL_MAX_IMAGES, n_images - first);
     AlImageTable tab;
@@ -442,7 +413,7 @@ int pack_rgba(const void* rgb, const void* alpha, void* rgba, const srgd_alpha_i
     hipLaunchKernelGGL(alpha_pack_kernel, dim3(blocks, (unsigned)cnt), dim3(AL_THREADS), 0, st, tab, (const unsigned char*)rgb,
                        (const unsigned char*)alpha, (unsigned char*)rgba);
     const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) AL_FAIL(name + ": " + hipGetErrorString(err));
+    if (err != hipSuccess) SRGD_EXT_FAIL(name + ": " + hipGetErrorString(err));
   }
   return 0;
 }
@@ -450,27 +421,27 @@ int pack_rgba(const void* rgb, const void* alpha, void* rgba, const srgd_alpha_i
 int bleed(const void* rgba, void* rgb, const srgd_alpha_image* images, int n_images, int passes, void* scratch, long long scratch_bytes,
           hipStream_t st) {
   const std::string name("srgd_alpha_bleed");
-  if (n_images < 1) AL_FAIL(name + ": n_images must be >= 1");
-  if (!rgba || !rgb || !images || !scratch) AL_FAIL(name + ": null argument");
-  if (passes < 0 || passes > SRGD_ALPHA_MAX_BLEED) AL_FAIL(name + ": passes must be in 0 .. 64");
-  if (((uintptr_t)scratch & 15u) != 0) AL_FAIL(name + ": scratch must be 16-byte aligned");
-  if ((((uintptr_t)rgba | (uintptr_t)rgb) & 15u) != 0) AL_FAIL(name + ": rgba and rgb must be 16-byte aligned");
+  if (n_images < 1) SRGD_EXT_FAIL(name + ": n_images must be >= 1");
+  if (!rgba || !rgb || !images || !scratch) SRGD_EXT_FAIL(name + ": null argument");
+  if (passes < 0 || passes > SRGD_ALPHA_MAX_BLEED) SRGD_EXT_FAIL(name + ": passes must be in 0 .. 64");
+  if (((uintptr_t)scratch & 15u) != 0) SRGD_EXT_FAIL(name + ": scratch must be 16-byte aligned");
+  if ((((uintptr_t)rgba | (uintptr_t)rgb) & 15u) != 0) SRGD_EXT_FAIL(name + ": rgba and rgb must be 16-byte aligned");
   long long state = 0;                                   // bytes of one of the two state buffers
   Range s, d;
   for (int i = 0; i < n_images; ++i) {                   // every image is checked before the first launch
     const srgd_alpha_image& im = images[i];
-    if (const char* problem = size_problem(im.h, im.w)) AL_FAIL(name + ": " + problem);
+    if (const char* problem = size_problem(im.h, im.w)) SRGD_EXT_FAIL(name + ": " + problem);
     for (const long long off : {(long long)im.rgb_off, (long long)im.rgba_off}) {
-      if (const char* p = offset_problem(off)) AL_FAIL(name + ": " + p);
+      if (const char* p = offset_problem(off)) SRGD_EXT_FAIL(name + ": " + p);
     }
     const long long n = (long long)im.h * im.w;
-    state += round16(4 * n);
+    state += round_up(4 * n, 16ll);
     s.add(im.rgba_off, 4 * n);
     d.add(im.rgb_off, 3 * n);
   }
-  if (passes > 0 && 2 * state > scratch_bytes) AL_FAIL(name + ": scratch_bytes is too small (twice the sum of 4 * h * w, each rounded up to 16)");
-  if (2 * state > (1ll << 36)) AL_FAIL(name + ": scratch beyond 2^36 bytes");
-  if (s.meets(rgba, d, rgb)) AL_FAIL(name + ": the source images and the destination images overlap");
+  if (passes > 0 && 2 * state > scratch_bytes) SRGD_EXT_FAIL(name + ": scratch_bytes is too small (twice the sum of 4 * h * w, each rounded up to 16)");
+  if (2 * state > (1ll << 36)) SRGD_EXT_FAIL(name + ": scratch beyond 2^36 bytes");
+  if (s.meets(rgba, d, rgb)) SRGD_EXT_FAIL(name + ": the source images and the destination images overlap");
   const unsigned long long state16 = (unsigned long long)(state >> 4);
   long long scr = 0;                                     // the images' state, packed in image order in each of the two buffers
   for (int first = 0; first < n_images; first += AL_MAX_IMAGES) {
@@ -483,7 +454,7 @@ int bleed(const void* rgba, void* rgb, const srgd_alpha_image* images, int n_ima
       const long long n = (long long)im.h * im.w;
       tab.im[k] = AlImage{(unsigned)(im.rgba_off >> 4), (unsigned)(im.rgb_off >> 4), (unsigned)(scr >> 4), (unsigned short)im.h,
                           (unsigned short)im.w};
-      scr += round16(4 * n);
+      scr += round_up(4 * n, 16ll);
       pixel_blocks = std::max(pixel_blocks, (unsigned)((n + AL_THREADS - 1) / AL_THREADS));
       quad_blocks = std::max(quad_blocks, (unsigned)(((n + 3) / 4 + AL_THREADS - 1) / AL_THREADS));
     }
@@ -495,7 +466,7 @@ int bleed(const void* rgba, void* rgb, const srgd_alpha_image* images, int n_ima
                        passes == 0 ? (const unsigned char*)rgba : (const unsigned char*)scratch, passes == 0 ? 1 : 0,
                        ((passes - 1) & 1) ? state16 : 0ull, (unsigned char*)rgb);
     const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) AL_FAIL(name + ": " + hipGetErrorString(err));
+    if (err != hipSuccess) SRGD_EXT_FAIL(name + ": " + hipGetErrorString(err));
   }
   return 0;
 }
@@ -505,24 +476,22 @@ int bleed(const void* rgba, void* rgb, const srgd_alpha_image* images, int n_ima
 
 using namespace srgd;
 
-#define AL_EXPORT __attribute__((visibility("default")))
-
 extern "C" {
 
-AL_EXPORT const char* srgd_alpha_last_error(void) { return g_err.c_str(); }
+SRGD_EXT_EXPORT const char* srgd_alpha_last_error(void) { return g_err.c_str(); }
 
-AL_EXPORT int srgd_alpha_resize_planes(const void* src, void* dst, const srgd_alpha_plane* planes_host, int n_planes, const void* tables,
-                                       int64_t tables_bytes, void* scratch, int64_t scratch_bytes, void* stream) {
+SRGD_EXT_EXPORT int srgd_alpha_resize_planes(const void* src, void* dst, const srgd_alpha_plane* planes_host, int n_planes, const void* tables,
+                                             int64_t tables_bytes, void* scratch, int64_t scratch_bytes, void* stream) {
   return resize_planes(src, dst, planes_host, n_planes, tables, (long long)tables_bytes, scratch, (long long)scratch_bytes, (hipStream_t)stream);
 }
 
-AL_EXPORT int srgd_alpha_pack_rgba(const void* rgb, const void* alpha, void* rgba, const srgd_alpha_image* images_host, int n_images,
-                                   void* stream) {
+SRGD_EXT_EXPORT int srgd_alpha_pack_rgba(const void* rgb, const void* alpha, void* rgba, const srgd_alpha_image* images_host, int n_images,
+                                         void* stream) {
   return pack_rgba(rgb, alpha, rgba, images_host, n_images, (hipStream_t)stream);
 }
 
-AL_EXPORT int srgd_alpha_bleed(const void* rgba, void* rgb, const srgd_alpha_image* images_host, int n_images, int passes, void* scratch,
-                               int64_t scratch_bytes, void* stream) {
+SRGD_EXT_EXPORT int srgd_alpha_bleed(const void* rgba, void* rgb, const srgd_alpha_image* images_host, int n_images, int passes, void* scratch,
+                                     int64_t scratch_bytes, void* stream) {
   return bleed(rgba, rgb, images_host, n_images, passes, scratch, (long long)scratch_bytes, (hipStream_t)stream);
 }
 

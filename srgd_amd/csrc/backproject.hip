@@ -42,19 +42,13 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/srgd_backproject.h"
+#include "ext_common.hpp"
 
-// This file is a library of its own (libsrgd_backproject.so, include/srgd_backproject.h): it shares no symbol with the other four.
+// This file is a library of its own (libsrgd_backproject.so, include/srgd_backproject.h): it shares no symbol with the engine or the other nine
+// extension libraries; ext_common.hpp is their common host plumbing.
 namespace srgd {
 namespace {
 
-thread_local std::string g_err;
-#define BP_FAIL(msg)             \
-  do {                           \
-    g_err = std::string(msg);    \
-    return -1;                   \
-  } while (0)
-
-constexpr int BP_PREC_BITS = 32 - 8 - 2;
 constexpr int BP_THREADS = 256;
 constexpr int BP_TW = 32, BP_TH = 15;                // LR pixels of a tile
 constexpr int BP_MAX_IMAGES = 128;                   // records travel as a kernel argument (3 KiB)
@@ -92,17 +86,12 @@ struct BpUp { int k[16][BP_UTAPS]; };                // indices 0 .. 5, phases 0
 
 __host__ __device__ inline unsigned bp_tiles_x(int w) { return (unsigned)((w + BP_TW - 1) / BP_TW); }
 __host__ __device__ inline unsigned bp_tiles_y(int h) { return (unsigned)((h + BP_TH - 1) / BP_TH); }
-__host__ __device__ inline unsigned long long bp_round256(unsigned long long n) { return (n + 255ull) & ~255ull; }
 // the image's scratch: O at 0, C at bp_plane(h, w), D at 2 bp_plane(h, w)
-__host__ __device__ inline unsigned long long bp_plane(int h, int w) { return bp_round256(48ull * (unsigned)h * (unsigned)w); }
+__host__ __device__ inline unsigned long long bp_plane(int h, int w) { return round_up(48ull * (unsigned)h * (unsigned)w, 256ull); }
 __host__ __device__ inline unsigned long long bp_scratch(int h, int w) {
-  return 2ull * bp_plane(h, w) + bp_round256(3ull * (unsigned)h * (unsigned)w);
+  return 2ull * bp_plane(h, w) + round_up(3ull * (unsigned)h * (unsigned)w, 256ull);
 }
 
-__device__ __forceinline__ int bp_clip8(int acc) {
-  const int v = acc >> BP_PREC_BITS;                 // arithmetic shift, as Pillow's clip8 lookup index
-  return v < 0 ? 0 : (v > 255 ? 255 : v);
-}
 // the reduction's vector of output index i of n
 __device__ __forceinline__ int bp_down_vector(int i, int n) { return i == 0 ? 0 : (i == 1 ? 1 : (i == n - 2 ? 3 : (i == n - 1 ? 4 : 2))); }
 // the enlargement's vector of output index j of n4 = 4n (any vector for an index beyond the image: its result is never used)
@@ -242,7 +231,7 @@ __global__ __launch_bounds__(BP_THREADS) void backproject_reduce_kernel(BpTable 
       unsigned d[13];
 #pragma unroll
       for (int q = 0; q < 13; ++q) d[q] = p[q];
-      int acc[3] = {1 << (BP_PREC_BITS - 1), 1 << (BP_PREC_BITS - 1), 1 << (BP_PREC_BITS - 1)};
+      int acc[3] = {1 << (PILLOW_PREC_BITS - 1), 1 << (PILLOW_PREC_BITS - 1), 1 << (PILLOW_PREC_BITS - 1)};
 #pragma unroll
       for (int t = 0; t < BP_RTAPS; ++t) {
 #pragma unroll
@@ -250,7 +239,7 @@ __global__ __launch_bounds__(BP_THREADS) void backproject_reduce_kernel(BpTable 
       }
       unsigned char* o = hbuf + r * BP_HSTRIDE + 3 * x;
 #pragma unroll
-      for (int c = 0; c < 3; ++c) o[c] = (unsigned char)bp_clip8(acc[c]);
+      for (int c = 0; c < 3; ++c) o[c] = (unsigned char)clip8(acc[c]);
     }
   }
   __syncthreads();
@@ -268,7 +257,7 @@ __global__ __launch_bounds__(BP_THREADS) void backproject_reduce_kernel(BpTable 
       const int4 c = kv[q];
       ky[4 * q] = c.x, ky[4 * q + 1] = c.y, ky[4 * q + 2] = c.z, ky[4 * q + 3] = c.w;
     }
-    int acc[4] = {1 << (BP_PREC_BITS - 1), 1 << (BP_PREC_BITS - 1), 1 << (BP_PREC_BITS - 1), 1 << (BP_PREC_BITS - 1)};
+    int acc[4] = {1 << (PILLOW_PREC_BITS - 1), 1 << (PILLOW_PREC_BITS - 1), 1 << (PILLOW_PREC_BITS - 1), 1 << (PILLOW_PREC_BITS - 1)};
     const unsigned* p = reinterpret_cast<const unsigned*>(hbuf + 4 * yl * BP_HSTRIDE) + j;
 #pragma unroll
     for (int t = 0; t < BP_RTAPS; ++t) {
@@ -280,7 +269,7 @@ __global__ __launch_bounds__(BP_THREADS) void backproject_reduce_kernel(BpTable 
     for (int b = 0; b < 4; ++b) {
       const int e = 4 * j + b, px = e / 3, c = e - 3 * px;
       const int gx = tx0 + px;
-      if (gx < w) down[((unsigned)gy * (unsigned)w + (unsigned)gx) * 3u + (unsigned)c] = (unsigned char)bp_clip8(acc[b]);      // < 2^31 / 16
+      if (gx < w) down[((unsigned)gy * (unsigned)w + (unsigned)gx) * 3u + (unsigned)c] = (unsigned char)clip8(acc[b]);      // < 2^31 / 16
     }
   }
 }
@@ -321,7 +310,7 @@ __global__ __launch_bounds__(BP_THREADS) void backproject_update_kernel(BpTable 
     for (int r = tid / BP_UW; r < BP_DROWS; r += BP_THREADS / BP_UW) {
       const unsigned* p = reinterpret_cast<const unsigned*>(dpatch + r * BP_DSTRIDE + (first & ~3));
       const unsigned d[4] = {p[0], p[1], p[2], p[3]};
-      int acc[3] = {1 << (BP_PREC_BITS - 1), 1 << (BP_PREC_BITS - 1), 1 << (BP_PREC_BITS - 1)};
+      int acc[3] = {1 << (PILLOW_PREC_BITS - 1), 1 << (PILLOW_PREC_BITS - 1), 1 << (PILLOW_PREC_BITS - 1)};
 #pragma unroll
       for (int t = 0; t < BP_UTAPS; ++t) {
 #pragma unroll
@@ -329,7 +318,7 @@ __global__ __launch_bounds__(BP_THREADS) void backproject_update_kernel(BpTable 
       }
       unsigned char* o = ubuf + r * BP_USTRIDE + 3 * x;
 #pragma unroll
-      for (int c = 0; c < 3; ++c) o[c] = (unsigned char)bp_clip8(acc[c]);
+      for (int c = 0; c < 3; ++c) o[c] = (unsigned char)clip8(acc[c]);
     }
   }
   __syncthreads();
@@ -345,7 +334,7 @@ __global__ __launch_bounds__(BP_THREADS) void backproject_update_kernel(BpTable 
     if (gy >= 4 * h || gb >= row_bytes) continue;                    // 12 w is a multiple of 4: a dword never straddles a row's end
     const int4 ky4 = *reinterpret_cast<const int4*>(kk[bp_up_vector(gy, 4 * h)]);
     const int ky[BP_UTAPS] = {ky4.x, ky4.y, ky4.z, ky4.w};
-    int acc[4] = {1 << (BP_PREC_BITS - 1), 1 << (BP_PREC_BITS - 1), 1 << (BP_PREC_BITS - 1), 1 << (BP_PREC_BITS - 1)};
+    int acc[4] = {1 << (PILLOW_PREC_BITS - 1), 1 << (PILLOW_PREC_BITS - 1), 1 << (PILLOW_PREC_BITS - 1), 1 << (PILLOW_PREC_BITS - 1)};
     const unsigned* p = reinterpret_cast<const unsigned*>(ubuf + ((y + 2) >> 2) * BP_USTRIDE) + j;
 #pragma unroll
     for (int t = 0; t < BP_UTAPS; ++t) {
@@ -358,112 +347,44 @@ __global__ __launch_bounds__(BP_THREADS) void backproject_update_kernel(BpTable 
     unsigned res = 0u;
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
-      const int v = bp_byte(&ov, b) + bp_byte(&cv, b) - bp_clip8(acc[b]);
+      const int v = bp_byte(&ov, b) + bp_byte(&cv, b) - clip8(acc[b]);
       res |= (unsigned)(v < 0 ? 0 : (v > 255 ? 255 : v)) << (8 * b);
     }
     *reinterpret_cast<unsigned*>(o_u8 + g) = res;
   }
 }
 
-double bicubic_weight(double x) {
-  const double a = -0.5;
-  if (x < 0.0) x = -x;
-  if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
-  if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
-  return 0.0;
-}
-
-// Pillow's precompute_coeffs + normalize_coeffs_8bpc for output xx of out_size from in_size (a factor of 4 either way): the first
-// input index, the number of taps (<= 16) and the fixed-point coefficients from that index on (zero beyond the last tap).
-void pillow_row(int in_size, int out_size, int xx, int* first, int* count, int32_t k[BP_RTAPS]) {
-  const double scale = (double)in_size / (double)out_size;
-  const double filterscale = scale < 1.0 ? 1.0 : scale;
-  const double support = 2.0 * filterscale, ss = 1.0 / filterscale;
-  const double center = (xx + 0.5) * scale;
-  double w[BP_RTAPS + 1], ww = 0.0;
-  int xmin = (int)(center - support + 0.5);
-  if (xmin < 0) xmin = 0;
-  int xmax = (int)(center + support + 0.5);
-  if (xmax > in_size) xmax = in_size;
-  xmax -= xmin;
-  for (int x = 0; x < xmax; ++x) {
-    w[x] = bicubic_weight((x + xmin - center + 0.5) * ss);
-    ww += w[x];
-  }
-  for (int x = 0; x < BP_RTAPS; ++x) k[x] = 0;
-  for (int x = 0; x < xmax; ++x) {
-    if (ww != 0.0) w[x] /= ww;
-    k[x] = w[x] < 0 ? (int)(-0.5 + w[x] * (1 << BP_PREC_BITS)) : (int)(0.5 + w[x] * (1 << BP_PREC_BITS));
-  }
-  *first = xmin;
-  *count = xmax;
-}
-
-constexpr int BP_REF_N = 64;                         // the vectors are taken from 256 <-> 64 (any n >= 5 gives the same)
-
-// The reduction's five vectors (rows 0, 1, 10, 62, 63) laid on the frame [4i - 6, 4i + 10) of their output.
-BpDown framed_down_vectors() {
-  const int rows[5] = {0, 1, 10, BP_REF_N - 2, BP_REF_N - 1};
-  BpDown c;
-  for (int v = 0; v < 5; ++v) {
-    int first, count;
-    int32_t k[BP_RTAPS];
-    pillow_row(4 * BP_REF_N, BP_REF_N, rows[v], &first, &count, k);
-    const int shift = first - (4 * rows[v] - 6);                     // 6, 2, 0, 0, 0
-    for (int t = 0; t < BP_RTAPS; ++t) c.k[v][t] = (t >= shift && t - shift < count) ? k[t - shift] : 0;
-  }
-  return c;
-}
-
-// The enlargement's output index of vector v: 0 .. 5, 6 .. 9 (phases 0 .. 3), 4n-6 .. 4n-1.
-int up_index(int v) { return v < 10 ? v : 4 * BP_REF_N - 16 + v; }
-
-void sixteen_vectors(int32_t out[16][BP_UTAPS]) {
-  for (int v = 0; v < 16; ++v) {
-    int first, count;
-    int32_t k[BP_RTAPS];
-    pillow_row(BP_REF_N, 4 * BP_REF_N, up_index(v), &first, &count, k);
-    for (int t = 0; t < BP_UTAPS; ++t) out[v][t] = k[t];
-  }
-}
-
-// ... laid on the frame [floor((j - 6) / 4), + 4) of their output: taps in front of the image are zeros
-BpUp framed_up_vectors() {
-  BpUp c;
-  for (int v = 0; v < 16; ++v) {
-    int first, count;
-    int32_t k[BP_RTAPS];
-    const int j = up_index(v);
-    pillow_row(BP_REF_N, 4 * BP_REF_N, j, &first, &count, k);
-    const int shift = first - ((j + 2) / 4 - 2);                     // 2, 2, 1, 1, 1, 1, then zeros
-    for (int t = 0; t < BP_UTAPS; ++t) c.k[v][t] = (t >= shift && t - shift < count) ? k[t - shift] : 0;
-  }
-  return c;
-}
-
 int backproject_images(const char* who, const float* out01, const float* cond01, const int64_t* offsets, const int32_t* hw, int n_images,
                        int iterations, float* dst01, void* scratch, hipStream_t st) {
   const std::string name(who);
-  if (n_images < 1) BP_FAIL(name + ": n_images must be >= 1");
-  if (!out01 || !cond01 || !offsets || !hw || !dst01 || !scratch) BP_FAIL(name + ": null argument");
-  if (iterations < 1 || iterations > BP_MAX_ITERATIONS) BP_FAIL(name + ": iterations outside 1 .. 64");
-  if ((((uintptr_t)out01 | (uintptr_t)cond01 | (uintptr_t)dst01) & 3u) != 0) BP_FAIL(name + ": out01, cond01 and dst01 must be 4-byte aligned");
-  if (((uintptr_t)scratch & 255u) != 0) BP_FAIL(name + ": scratch must be 256-byte aligned");
+  if (n_images < 1) SRGD_EXT_FAIL(name + ": n_images must be >= 1");
+  if (!out01 || !cond01 || !offsets || !hw || !dst01 || !scratch) SRGD_EXT_FAIL(name + ": null argument");
+  if (iterations < 1 || iterations > BP_MAX_ITERATIONS) SRGD_EXT_FAIL(name + ": iterations outside 1 .. 64");
+  if ((((uintptr_t)out01 | (uintptr_t)cond01 | (uintptr_t)dst01) & 3u) != 0) SRGD_EXT_FAIL(name + ": out01, cond01 and dst01 must be 4-byte aligned");
+  if (((uintptr_t)scratch & 255u) != 0) SRGD_EXT_FAIL(name + ": scratch must be 256-byte aligned");
   long long lo = 0, hi = 0;                              // the elements the call covers in each of the three buffers: [lo, hi)
   for (int i = 0; i < n_images; ++i) {                   // every image is checked before the first launch
     const long long h = hw[2 * i], w = hw[2 * i + 1];
-    if (h < 5 || w < 5) BP_FAIL(name + ": bad size (h and w must be >= 5: smaller windows overlap and depend on the size)");
-    if (48 * h * w >= 0x7fffff00ll) BP_FAIL(name + ": output of 2^31 - 256 elements or more");
-    if (offsets[i] < 0 || offsets[i] >= (1ll << 40)) BP_FAIL(name + ": offset outside [0, 2^40)");
+    if (h < 5 || w < 5) SRGD_EXT_FAIL(name + ": bad size (h and w must be >= 5: smaller windows overlap and depend on the size)");
+    if (48 * h * w >= 0x7fffff00ll) SRGD_EXT_FAIL(name + ": output of 2^31 - 256 elements or more");
+    if (offsets[i] < 0 || offsets[i] >= (1ll << 40)) SRGD_EXT_FAIL(name + ": offset outside [0, 2^40)");
     lo = i == 0 ? offsets[i] : std::min<long long>(lo, offsets[i]);
     hi = i == 0 ? offsets[i] + 48 * h * w : std::max<long long>(hi, offsets[i] + 48 * h * w);
   }
   const long long span = 4 * (hi - lo);                  // bytes
   const long long to_out = (long long)((intptr_t)dst01 - (intptr_t)out01), to_cond = (long long)((intptr_t)dst01 - (intptr_t)cond01);
-  if (to_out != 0 && to_out < span && -to_out < span) BP_FAIL(name + ": partial overlap of dst01 and out01 (dst01 == out01 is in place)");
-  if (to_cond < span && -to_cond < span) BP_FAIL(name + ": overlap of dst01 and cond01");
-  static const BpDown down = framed_down_vectors();
-  static const BpUp up = framed_up_vectors();
+  if (to_out != 0 && to_out < span && -to_out < span) SRGD_EXT_FAIL(name + ": partial overlap of dst01 and out01 (dst01 == out01 is in place)");
+  if (to_cond < span && -to_cond < span) SRGD_EXT_FAIL(name + ": overlap of dst01 and cond01");
+  static const BpDown down = [] {                        // pillow_coeffs.hpp: the vectors on the frames of their outputs
+    BpDown c;
+    pillow::x4_reduce_vectors(c.k, true);
+    return c;
+  }();
+  static const BpUp up = [] {
+    BpUp c;
+    pillow::x4_enlarge_vectors(c.k, true);
+    return c;
+  }();
   unsigned long long scr = 0;                            // the images' scratch, packed in image order
   for (int first = 0; first < n_images; first += BP_MAX_IMAGES) {     // one launch sequence per BP_MAX_IMAGES images
     const int cnt = std::min(BP_MAX_IMAGES, n_images - first);
@@ -486,7 +407,7 @@ int backproject_images(const char* who, const float* out01, const float* cond01,
     }
     hipLaunchKernelGGL(backproject_end_kernel, flat, dim3(BP_THREADS), 0, st, tab, out01, dst01, (const unsigned char*)scratch);
     const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) BP_FAIL(name + ": " + hipGetErrorString(err));
+    if (err != hipSuccess) SRGD_EXT_FAIL(name + ": " + hipGetErrorString(err));
   }
   return 0;
 }
@@ -496,27 +417,25 @@ int backproject_images(const char* who, const float* out01, const float* cond01,
 
 using namespace srgd;
 
-#define BP_EXPORT __attribute__((visibility("default")))
-
 extern "C" {
 
-BP_EXPORT const char* srgd_image_backproject_last_error(void) { return g_err.c_str(); }
+SRGD_EXT_EXPORT const char* srgd_image_backproject_last_error(void) { return g_err.c_str(); }
 
-BP_EXPORT int srgd_image_backproject_coeffs(int32_t out[16][4]) {
-  if (!out) BP_FAIL("srgd_image_backproject_coeffs: null argument");
-  sixteen_vectors(out);
+SRGD_EXT_EXPORT int srgd_image_backproject_coeffs(int32_t out[16][4]) {
+  if (!out) SRGD_EXT_FAIL("srgd_image_backproject_coeffs: null argument");
+  pillow::x4_enlarge_vectors(out, false);
   return 0;
 }
 
-BP_EXPORT int srgd_image_backproject(const float* out01, const float* cond01, int h, int w, int iterations, float* dst01, void* scratch,
-                                     void* stream) {
+SRGD_EXT_EXPORT int srgd_image_backproject(const float* out01, const float* cond01, int h, int w, int iterations, float* dst01, void* scratch,
+                                           void* stream) {
   const int64_t off = 0;
   const int32_t hw[2] = {h, w};
   return backproject_images("srgd_image_backproject", out01, cond01, &off, hw, 1, iterations, dst01, scratch, (hipStream_t)stream);
 }
 
-BP_EXPORT int srgd_image_backproject_images(const float* out01, const float* cond01, const int64_t* offsets_host, const int32_t* hw_host,
-                                            int n_images, int iterations, float* dst01, void* scratch, void* stream) {
+SRGD_EXT_EXPORT int srgd_image_backproject_images(const float* out01, const float* cond01, const int64_t* offsets_host, const int32_t* hw_host,
+                                                  int n_images, int iterations, float* dst01, void* scratch, void* stream) {
   return backproject_images("srgd_image_backproject_images", out01, cond01, offsets_host, hw_host, n_images, iterations, dst01, scratch,
                             (hipStream_t)stream);
 }

@@ -39,19 +39,13 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/srgd_consistency.h"
+#include "ext_common.hpp"
 
-// This file is a library of its own (libsrgd_consistency.so, include/srgd_consistency.h): it shares no symbol with the other three.
+// This file is a library of its own (libsrgd_consistency.so, include/srgd_consistency.h): it shares no symbol with the engine or the other nine
+// extension libraries; ext_common.hpp is their common host plumbing.
 namespace srgd {
 namespace {
 
-thread_local std::string g_err;
-#define CS_FAIL(msg)             \
-  do {                           \
-    g_err = std::string(msg);    \
-    return -1;                   \
-  } while (0)
-
-constexpr int CS_PREC_BITS = 32 - 8 - 2;
 constexpr int CS_TAPS = 16;
 constexpr int CS_THREADS = 256;
 constexpr int CS_TW = 32, CS_TH = 15;                // LR pixels of a tile
@@ -76,10 +70,6 @@ struct CsRecord { unsigned long long sse[3], max_abs; };
 __host__ __device__ inline unsigned cs_tiles_x(int w) { return (unsigned)((w + CS_TW - 1) / CS_TW); }
 __host__ __device__ inline unsigned cs_tiles_y(int h) { return (unsigned)((h + CS_TH - 1) / CS_TH); }
 
-__device__ __forceinline__ int cs_clip8(int acc) {
-  const int v = acc >> CS_PREC_BITS;                 // arithmetic shift, as Pillow's clip8 lookup index
-  return v < 0 ? 0 : (v > 255 ? 255 : v);
-}
 // the coefficient vector of output index i of n
 __device__ __forceinline__ int cs_vector(int i, int n) { return i == 0 ? 0 : (i == 1 ? 1 : (i == n - 2 ? 3 : (i == n - 1 ? 4 : 2))); }
 __device__ __forceinline__ int cs_byte(const unsigned* d, int k) { return (int)((d[k >> 2] >> (8 * (k & 3))) & 0xffu); }
@@ -138,7 +128,7 @@ __global__ __launch_bounds__(CS_THREADS) void consistency_tile_kernel(CsTable ta
       unsigned d[13];
 #pragma unroll
       for (int q = 0; q < 13; ++q) d[q] = p[q];
-      int acc[3] = {1 << (CS_PREC_BITS - 1), 1 << (CS_PREC_BITS - 1), 1 << (CS_PREC_BITS - 1)};
+      int acc[3] = {1 << (PILLOW_PREC_BITS - 1), 1 << (PILLOW_PREC_BITS - 1), 1 << (PILLOW_PREC_BITS - 1)};
 #pragma unroll
       for (int t = 0; t < CS_TAPS; ++t) {
 #pragma unroll
@@ -146,7 +136,7 @@ __global__ __launch_bounds__(CS_THREADS) void consistency_tile_kernel(CsTable ta
       }
       unsigned char* o = hbuf + r * CS_HSTRIDE + 3 * x;
 #pragma unroll
-      for (int c = 0; c < 3; ++c) o[c] = (unsigned char)cs_clip8(acc[c]);
+      for (int c = 0; c < 3; ++c) o[c] = (unsigned char)clip8(acc[c]);
     }
   }
   __syncthreads();
@@ -166,7 +156,7 @@ __global__ __launch_bounds__(CS_THREADS) void consistency_tile_kernel(CsTable ta
       const int4 c = kv[q];
       ky[4 * q] = c.x, ky[4 * q + 1] = c.y, ky[4 * q + 2] = c.z, ky[4 * q + 3] = c.w;
     }
-    int acc[4] = {1 << (CS_PREC_BITS - 1), 1 << (CS_PREC_BITS - 1), 1 << (CS_PREC_BITS - 1), 1 << (CS_PREC_BITS - 1)};
+    int acc[4] = {1 << (PILLOW_PREC_BITS - 1), 1 << (PILLOW_PREC_BITS - 1), 1 << (PILLOW_PREC_BITS - 1), 1 << (PILLOW_PREC_BITS - 1)};
     const unsigned* p = reinterpret_cast<const unsigned*>(hbuf + 4 * yl * CS_HSTRIDE) + j;
 #pragma unroll
     for (int t = 0; t < CS_TAPS; ++t) {
@@ -180,7 +170,7 @@ __global__ __launch_bounds__(CS_THREADS) void consistency_tile_kernel(CsTable ta
       const int gx = tx0 + px;
       if (gx < w) {
         const unsigned g = ((unsigned)gy * (unsigned)w + (unsigned)gx) * 3u + (unsigned)c;      // < 2^31 / 16
-        const int dv = cs_clip8(acc[b]);
+        const int dv = clip8(acc[b]);
         if (down != nullptr) down[g] = (unsigned char)dv;
         const int err = dv - (int)lr[g];
         const unsigned a = (unsigned)(err < 0 ? -err : err), sq = a * a;
@@ -246,86 +236,32 @@ __global__ __launch_bounds__(CS_THREADS) void consistency_finish_kernel(CsTable 
   }
 }
 
-double bicubic_weight(double x) {
-  const double a = -0.5;
-  if (x < 0.0) x = -x;
-  if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
-  if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
-  return 0.0;
-}
-
-// Pillow's precompute_coeffs + normalize_coeffs_8bpc for output xx of out_size from in_size = 4 * out_size: the first input index,
-// the number of taps (<= 16) and the fixed-point coefficients from that index on (zero beyond the last tap).
-void pillow_row(int in_size, int out_size, int xx, int* first, int* count, int32_t k[CS_TAPS]) {
-  const double scale = (double)in_size / (double)out_size;
-  const double filterscale = scale < 1.0 ? 1.0 : scale;
-  const double support = 2.0 * filterscale, ss = 1.0 / filterscale;
-  const double center = (xx + 0.5) * scale;
-  double w[CS_TAPS + 1], ww = 0.0;
-  int xmin = (int)(center - support + 0.5);
-  if (xmin < 0) xmin = 0;
-  int xmax = (int)(center + support + 0.5);
-  if (xmax > in_size) xmax = in_size;
-  xmax -= xmin;
-  for (int x = 0; x < xmax; ++x) {
-    w[x] = bicubic_weight((x + xmin - center + 0.5) * ss);
-    ww += w[x];
-  }
-  for (int x = 0; x < CS_TAPS; ++x) k[x] = 0;
-  for (int x = 0; x < xmax; ++x) {
-    if (ww != 0.0) w[x] /= ww;
-    k[x] = w[x] < 0 ? (int)(-0.5 + w[x] * (1 << CS_PREC_BITS)) : (int)(0.5 + w[x] * (1 << CS_PREC_BITS));
-  }
-  *first = xmin;
-  *count = xmax;
-}
-
-// The five vectors from a reduction 256 -> 64 (any n >= 5 gives the same): rows 0, 1, 10, 62, 63.
-constexpr int CS_REF_N = 64;
-constexpr int CS_REF_ROWS[5] = {0, 1, 10, CS_REF_N - 2, CS_REF_N - 1};
-
-void five_vectors(int32_t out[5][CS_TAPS]) {
-  for (int v = 0; v < 5; ++v) {
-    int first, count;
-    pillow_row(4 * CS_REF_N, CS_REF_N, CS_REF_ROWS[v], &first, &count, out[v]);
-  }
-}
-
-// ... laid on the frame [4i - 6, 4i + 10) of their output: taps in front of the image are zeros
-CsCoeffs framed_vectors() {
-  CsCoeffs c;
-  for (int v = 0; v < 5; ++v) {
-    int first, count;
-    int32_t k[CS_TAPS];
-    pillow_row(4 * CS_REF_N, CS_REF_N, CS_REF_ROWS[v], &first, &count, k);
-    const int shift = first - (4 * CS_REF_ROWS[v] - 6);              // 6, 2, 0, 0, 0
-    for (int t = 0; t < CS_TAPS; ++t) c.k[v][t] = (t >= shift && t - shift < count) ? k[t - shift] : 0;
-  }
-  return c;
-}
-
 int consistency_images(const char* who, const uint8_t* hr_u8, const int64_t* hr_offsets, const uint8_t* lr_u8, const int64_t* lr_offsets,
                        const int32_t* hw, int n_images, uint8_t* down_u8, const int64_t* down_offsets, int64_t* stats, void* scratch,
                        hipStream_t st) {
   const std::string name(who);
-  if (n_images < 1) CS_FAIL(name + ": n_images must be >= 1");
-  if (!hr_u8 || !hr_offsets || !lr_u8 || !lr_offsets || !hw || !stats || !scratch) CS_FAIL(name + ": null argument");
-  if ((down_u8 == nullptr) != (down_offsets == nullptr)) CS_FAIL(name + ": down_u8 and its offsets are given together or not at all");
-  if (((uintptr_t)hr_u8 & 15u) != 0) CS_FAIL(name + ": hr_u8 must be 16-byte aligned");
-  if ((((uintptr_t)stats | (uintptr_t)scratch) & 7u) != 0) CS_FAIL(name + ": stats and scratch must be 8-byte aligned");
+  if (n_images < 1) SRGD_EXT_FAIL(name + ": n_images must be >= 1");
+  if (!hr_u8 || !hr_offsets || !lr_u8 || !lr_offsets || !hw || !stats || !scratch) SRGD_EXT_FAIL(name + ": null argument");
+  if ((down_u8 == nullptr) != (down_offsets == nullptr)) SRGD_EXT_FAIL(name + ": down_u8 and its offsets are given together or not at all");
+  if (((uintptr_t)hr_u8 & 15u) != 0) SRGD_EXT_FAIL(name + ": hr_u8 must be 16-byte aligned");
+  if ((((uintptr_t)stats | (uintptr_t)scratch) & 7u) != 0) SRGD_EXT_FAIL(name + ": stats and scratch must be 8-byte aligned");
   unsigned long long total = 0;
   for (int i = 0; i < n_images; ++i) {                   // every image is checked before the first launch
     const long long h = hw[2 * i], w = hw[2 * i + 1];
-    if (h < 5 || w < 5) CS_FAIL(name + ": bad size (h and w must be >= 5: smaller windows overlap and depend on the size)");
-    if (48 * h * w >= 0x7fffff00ll) CS_FAIL(name + ": output of 2^31 - 256 elements or more");
+    if (h < 5 || w < 5) SRGD_EXT_FAIL(name + ": bad size (h and w must be >= 5: smaller windows overlap and depend on the size)");
+    if (48 * h * w >= 0x7fffff00ll) SRGD_EXT_FAIL(name + ": output of 2^31 - 256 elements or more");
     for (const int64_t off : {hr_offsets[i], lr_offsets[i], down_offsets ? down_offsets[i] : (int64_t)0}) {
-      if (off < 0 || off >= (1ll << 36)) CS_FAIL(name + ": offset outside [0, 2^36)");
-      if ((off & 15) != 0) CS_FAIL(name + ": misaligned offset (offsets are multiples of 16)");
+      if (off < 0 || off >= (1ll << 36)) SRGD_EXT_FAIL(name + ": offset outside [0, 2^36)");
+      if ((off & 15) != 0) SRGD_EXT_FAIL(name + ": misaligned offset (offsets are multiples of 16)");
     }
     total += (unsigned long long)cs_tiles_x((int)w) * cs_tiles_y((int)h);
   }
-  if (total > 0xffffffffull) CS_FAIL(name + ": more than 2^32 tiles in one call");
-  static const CsCoeffs coeffs = framed_vectors();
+  if (total > 0xffffffffull) SRGD_EXT_FAIL(name + ": more than 2^32 tiles in one call");
+  static const CsCoeffs coeffs = [] {                    // pillow_coeffs.hpp: the five vectors on the frames of their outputs
+    CsCoeffs c;
+    pillow::x4_reduce_vectors(c.k, true);
+    return c;
+  }();
   unsigned part = 0;                                     // records, packed in image order
   for (int first = 0; first < n_images; first += CS_MAX_IMAGES) {     // one launch sequence per CS_MAX_IMAGES images
     const int cnt = std::min(CS_MAX_IMAGES, n_images - first);
@@ -345,7 +281,7 @@ int consistency_images(const char* who, const uint8_t* hr_u8, const int64_t* hr_
     hipLaunchKernelGGL(consistency_finish_kernel, dim3((unsigned)cnt), dim3(CS_THREADS), 0, st, tab, (const CsRecord*)scratch,
                        (long long*)stats + (size_t)first * 4);
     const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) CS_FAIL(name + ": " + hipGetErrorString(err));
+    if (err != hipSuccess) SRGD_EXT_FAIL(name + ": " + hipGetErrorString(err));
   }
   return 0;
 }
@@ -355,29 +291,27 @@ int consistency_images(const char* who, const uint8_t* hr_u8, const int64_t* hr_
 
 using namespace srgd;
 
-#define CS_EXPORT __attribute__((visibility("default")))
-
 extern "C" {
 
-CS_EXPORT const char* srgd_image_consistency_last_error(void) { return g_err.c_str(); }
+SRGD_EXT_EXPORT const char* srgd_image_consistency_last_error(void) { return g_err.c_str(); }
 
-CS_EXPORT int srgd_image_consistency_coeffs(int32_t out[5][16]) {
-  if (!out) CS_FAIL("srgd_image_consistency_coeffs: null argument");
-  five_vectors(out);
+SRGD_EXT_EXPORT int srgd_image_consistency_coeffs(int32_t out[5][16]) {
+  if (!out) SRGD_EXT_FAIL("srgd_image_consistency_coeffs: null argument");
+  pillow::x4_reduce_vectors(out, false);
   return 0;
 }
 
-CS_EXPORT int srgd_image_consistency(const uint8_t* hr_u8, const uint8_t* lr_u8, int h, int w, uint8_t* down_u8, int64_t* stats,
-                                     void* scratch, void* stream) {
+SRGD_EXT_EXPORT int srgd_image_consistency(const uint8_t* hr_u8, const uint8_t* lr_u8, int h, int w, uint8_t* down_u8, int64_t* stats,
+                                           void* scratch, void* stream) {
   const int64_t off = 0;
   const int32_t hw[2] = {h, w};
   return consistency_images("srgd_image_consistency", hr_u8, &off, lr_u8, &off, hw, 1, down_u8, down_u8 ? &off : nullptr, stats, scratch,
                             (hipStream_t)stream);
 }
 
-CS_EXPORT int srgd_image_consistency_images(const uint8_t* hr_u8, const int64_t* hr_offsets_host, const uint8_t* lr_u8,
-                                            const int64_t* lr_offsets_host, const int32_t* hw_host, int n_images, uint8_t* down_u8,
-                                            const int64_t* down_offsets_host, int64_t* stats, void* scratch, void* stream) {
+SRGD_EXT_EXPORT int srgd_image_consistency_images(const uint8_t* hr_u8, const int64_t* hr_offsets_host, const uint8_t* lr_u8,
+                                                  const int64_t* lr_offsets_host, const int32_t* hw_host, int n_images, uint8_t* down_u8,
+                                                  const int64_t* down_offsets_host, int64_t* stats, void* scratch, void* stream) {
   return consistency_images("srgd_image_consistency_images", hr_u8, hr_offsets_host, lr_u8, lr_offsets_host, hw_host, n_images, down_u8,
                             down_offsets_host, stats, scratch, (hipStream_t)stream);
 }

@@ -30,17 +30,12 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/srgd_ensemble.h"
+#include "ext_common.hpp"
 
-// This file is a library of its own (libsrgd_ensemble.so, include/srgd_ensemble.h): it shares no symbol with the engine or the metrics.
+// This file is a library of its own (libsrgd_ensemble.so, include/srgd_ensemble.h): it shares no symbol with the engine or the other nine
+// extension libraries; ext_common.hpp is their common host plumbing.
 namespace srgd {
 namespace {
-
-thread_local std::string g_err;
-#define EN_FAIL(msg)             \
-  do {                           \
-    g_err = std::string(msg);    \
-    return -1;                   \
-  } while (0)
 
 constexpr int EN_VEC = 16;                           // bytes of a lane per sample: one 16-byte load
 constexpr int EN_THREADS = 256;
@@ -213,27 +208,27 @@ int ensemble_images(const char* who, const uint8_t* samples, const int64_t* samp
                     uint8_t* mean_u8, uint8_t* std_u8, const int64_t* out_offsets, float* mean01, const int64_t* m01_offsets,
                     double* stats, double* scratch, hipStream_t st) {
   const std::string name(who);
-  if (n_images < 1) EN_FAIL(name + ": n_images must be >= 1");
-  if (!samples || !sample_offsets || !hw || !mean_u8 || !std_u8 || !out_offsets || !stats || !scratch) EN_FAIL(name + ": null argument");
-  if ((mean01 == nullptr) != (m01_offsets == nullptr)) EN_FAIL(name + ": mean01 and its offsets are given together or not at all");
-  if (K < 2 || K > 256) EN_FAIL(name + ": n_samples must be in 2..256");
+  if (n_images < 1) SRGD_EXT_FAIL(name + ": n_images must be >= 1");
+  if (!samples || !sample_offsets || !hw || !mean_u8 || !std_u8 || !out_offsets || !stats || !scratch) SRGD_EXT_FAIL(name + ": null argument");
+  if ((mean01 == nullptr) != (m01_offsets == nullptr)) SRGD_EXT_FAIL(name + ": mean01 and its offsets are given together or not at all");
+  if (K < 2 || K > 256) SRGD_EXT_FAIL(name + ": n_samples must be in 2..256");
   if ((((uintptr_t)samples | (uintptr_t)mean_u8 | (uintptr_t)std_u8) & (uintptr_t)(EN_VEC - 1)) != 0)
-    EN_FAIL(name + ": samples, mean_u8 and std_u8 must be 16-byte aligned");
+    SRGD_EXT_FAIL(name + ": samples, mean_u8 and std_u8 must be 16-byte aligned");
   if ((((uintptr_t)stats | (uintptr_t)scratch) & 7u) != 0 || ((uintptr_t)mean01 & 3u) != 0)
-    EN_FAIL(name + ": stats and scratch must be 8-byte aligned, mean01 4-byte aligned");
+    SRGD_EXT_FAIL(name + ": stats and scratch must be 8-byte aligned, mean01 4-byte aligned");
   unsigned long long total = 0;
   for (int i = 0; i < n_images; ++i) {                   // every image is checked before the first launch
     const long long h = hw[2 * i], w = hw[2 * i + 1];
-    if (h < 1 || w < 1) EN_FAIL(name + ": bad size");
-    if (3 * h * w >= 0x7fffff00ll) EN_FAIL(name + ": image of 2^31 - 256 elements or more");
+    if (h < 1 || w < 1) SRGD_EXT_FAIL(name + ": bad size");
+    if (3 * h * w >= 0x7fffff00ll) SRGD_EXT_FAIL(name + ": image of 2^31 - 256 elements or more");
     for (const int64_t off : {sample_offsets[i], out_offsets[i]}) {
-      if (off < 0 || off >= (1ll << 36)) EN_FAIL(name + ": offset outside [0, 2^36)");
-      if ((off & (EN_VEC - 1)) != 0) EN_FAIL(name + ": misaligned offset (sample and output offsets are multiples of 16)");
+      if (off < 0 || off >= (1ll << 36)) SRGD_EXT_FAIL(name + ": offset outside [0, 2^36)");
+      if ((off & (EN_VEC - 1)) != 0) SRGD_EXT_FAIL(name + ": misaligned offset (sample and output offsets are multiples of 16)");
     }
-    if (m01_offsets && m01_offsets[i] < 0) EN_FAIL(name + ": negative mean01 offset");
+    if (m01_offsets && m01_offsets[i] < 0) SRGD_EXT_FAIL(name + ": negative mean01 offset");
     total += (unsigned long long)((3 * h * w + EN_CHUNK - 1) / EN_CHUNK);
   }
-  if (total > 0xffffffffull) EN_FAIL(name + ": more than 2^32 chunks in one call");
+  if (total > 0xffffffffull) SRGD_EXT_FAIL(name + ": more than 2^32 chunks in one call");
   const unsigned magic = (unsigned)((1ull << 32) / (unsigned)(2 * K)) + 1u;
   unsigned part = 0;                                     // records, packed in image order
   for (int first = 0; first < n_images; first += EN_MAX_IMAGES) {     // one launch sequence per EN_MAX_IMAGES images
@@ -254,7 +249,7 @@ int ensemble_images(const char* who, const uint8_t* samples, const int64_t* samp
                        K, magic, mean_u8, std_u8, mean01, scratch);
     hipLaunchKernelGGL(ensemble_finish_kernel, dim3((unsigned)cnt), dim3(EN_THREADS), 0, st, tab, K, scratch, stats + (size_t)first * 2);
     const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) EN_FAIL(name + ": " + hipGetErrorString(err));
+    if (err != hipSuccess) SRGD_EXT_FAIL(name + ": " + hipGetErrorString(err));
   }
   return 0;
 }
@@ -264,24 +259,22 @@ int ensemble_images(const char* who, const uint8_t* samples, const int64_t* samp
 
 using namespace srgd;
 
-#define EN_EXPORT __attribute__((visibility("default")))
-
 extern "C" {
 
-EN_EXPORT const char* srgd_image_ensemble_last_error(void) { return g_err.c_str(); }
+SRGD_EXT_EXPORT const char* srgd_image_ensemble_last_error(void) { return g_err.c_str(); }
 
-EN_EXPORT int srgd_image_ensemble(const uint8_t* samples, int n_samples, int h, int w, uint8_t* mean_u8, uint8_t* std_u8, float* mean01,
-                                  double* stats, double* scratch, void* stream) {
+SRGD_EXT_EXPORT int srgd_image_ensemble(const uint8_t* samples, int n_samples, int h, int w, uint8_t* mean_u8, uint8_t* std_u8, float* mean01,
+                                        double* stats, double* scratch, void* stream) {
   const int64_t off = 0;
   const int32_t hw[2] = {h, w};
   return ensemble_images("srgd_image_ensemble", samples, &off, hw, 1, n_samples, mean_u8, std_u8, &off, mean01, mean01 ? &off : nullptr,
                          stats, scratch, (hipStream_t)stream);
 }
 
-EN_EXPORT int srgd_image_ensemble_images(const uint8_t* samples, const int64_t* sample_offsets_host, const int32_t* hw_host, int n_images,
-                                         int n_samples, uint8_t* mean_u8, uint8_t* std_u8, const int64_t* out_offsets_host,
-                                         float* mean01, const int64_t* mean01_offsets_host, double* stats, double* scratch,
-                                         void* stream) {
+SRGD_EXT_EXPORT int srgd_image_ensemble_images(const uint8_t* samples, const int64_t* sample_offsets_host, const int32_t* hw_host, int n_images,
+                                               int n_samples, uint8_t* mean_u8, uint8_t* std_u8, const int64_t* out_offsets_host,
+                                               float* mean01, const int64_t* mean01_offsets_host, double* stats, double* scratch,
+                                               void* stream) {
   return ensemble_images("srgd_image_ensemble_images", samples, sample_offsets_host, hw_host, n_images, n_samples, mean_u8, std_u8,
                          out_offsets_host, mean01, mean01_offsets_host, stats, scratch, (hipStream_t)stream);
 }

@@ -33,19 +33,13 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/srgd_guidance.h"
+#include "ext_common.hpp"
 
-// This file is a library of its own (libsrgd_guidance.so, include/srgd_guidance.h): it shares no symbol with the other five.
+// This file is a library of its own (libsrgd_guidance.so, include/srgd_guidance.h): it shares no symbol with the engine or the other nine
+// extension libraries; ext_common.hpp is their common host plumbing.
 namespace srgd {
 namespace {
 
-thread_local std::string g_err;
-#define GD_FAIL(msg)             \
-  do {                           \
-    g_err = std::string(msg);    \
-    return -1;                   \
-  } while (0)
-
-constexpr int GD_PREC_BITS = 32 - 8 - 2;
 constexpr int GD_THREADS = 256;
 constexpr int GD_TW = 32, GD_TH = 15;                // LR pixels of a tile
 constexpr int GD_MAX_IMAGES = 128;                   // records travel as a kernel argument (5 KiB)
@@ -78,7 +72,7 @@ struct GdUp { float k[16][GD_UTAPS]; };              // indices 0 .. 5, phases 0
 
 __host__ __device__ inline unsigned gd_tiles_x(int w) { return (unsigned)((w + GD_TW - 1) / GD_TW); }
 __host__ __device__ inline unsigned gd_tiles_y(int h) { return (unsigned)((h + GD_TH - 1) / GD_TH); }
-inline unsigned long long gd_scratch(long long h, long long w) { return ((unsigned long long)(12 * h * w) + 255ull) & ~255ull; }
+inline unsigned long long gd_scratch(long long h, long long w) { return round_up((unsigned long long)(12 * h * w), 256ull); }
 
 // the reduction's vector of output index i of n
 __device__ __forceinline__ int gd_down_vector(int i, int n) { return i == 0 ? 0 : (i == 1 ? 1 : (i == n - 2 ? 3 : (i == n - 1 ? 4 : 2))); }
@@ -205,92 +199,45 @@ __global__ __launch_bounds__(GD_THREADS) void guidance_update_kernel(GdTable tab
   }
 }
 
-double bicubic_weight(double x) {
-  const double a = -0.5;
-  if (x < 0.0) x = -x;
-  if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
-  if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
-  return 0.0;
-}
+constexpr float GD_UNIT = 1.0f / (float)(1 << PILLOW_PREC_BITS);   // |k| < 2^23: k * 2^-22 is exact in fp32
 
-// Pillow's precompute_coeffs + normalize_coeffs_8bpc for output xx of out_size from in_size (a factor of 4 either way): the first
-// input index, the number of taps (<= 16) and the fixed-point coefficients from that index on (zero beyond the last tap).
-void pillow_row(int in_size, int out_size, int xx, int* first, int* count, int32_t k[GD_RTAPS]) {
-  const double scale = (double)in_size / (double)out_size;
-  const double filterscale = scale < 1.0 ? 1.0 : scale;
-  const double support = 2.0 * filterscale, ss = 1.0 / filterscale;
-  const double center = (xx + 0.5) * scale;
-  double w[GD_RTAPS + 1], ww = 0.0;
-  int xmin = (int)(center - support + 0.5);
-  if (xmin < 0) xmin = 0;
-  int xmax = (int)(center + support + 0.5);
-  if (xmax > in_size) xmax = in_size;
-  xmax -= xmin;
-  for (int x = 0; x < xmax; ++x) {
-    w[x] = bicubic_weight((x + xmin - center + 0.5) * ss);
-    ww += w[x];
-  }
-  for (int x = 0; x < GD_RTAPS; ++x) k[x] = 0;
-  for (int x = 0; x < xmax; ++x) {
-    if (ww != 0.0) w[x] /= ww;
-    k[x] = w[x] < 0 ? (int)(-0.5 + w[x] * (1 << GD_PREC_BITS)) : (int)(0.5 + w[x] * (1 << GD_PREC_BITS));
-  }
-  *first = xmin;
-  *count = xmax;
-}
-
-constexpr int GD_REF_N = 64;                         // the vectors are taken from 256 <-> 64 (any n >= 5 gives the same)
-constexpr float GD_UNIT = 1.0f / (float)(1 << GD_PREC_BITS);       // |k| < 2^23: k * 2^-22 is exact in fp32
-
-// The reduction's five vectors (rows 0, 1, 10, 62, 63) laid on the frame [4i - 6, 4i + 10) of their output.
+// The vectors of pillow_coeffs.hpp on the frames of their outputs, as floats
 GdDown framed_down_vectors() {
-  const int rows[5] = {0, 1, 10, GD_REF_N - 2, GD_REF_N - 1};
+  int32_t k[5][GD_RTAPS];
+  pillow::x4_reduce_vectors(k, true);
   GdDown c;
-  for (int v = 0; v < 5; ++v) {
-    int first, count;
-    int32_t k[GD_RTAPS];
-    pillow_row(4 * GD_REF_N, GD_REF_N, rows[v], &first, &count, k);
-    const int shift = first - (4 * rows[v] - 6);                     // 6, 2, 0, 0, 0
-    for (int t = 0; t < GD_RTAPS; ++t) c.k[v][t] = (t >= shift && t - shift < count) ? (float)k[t - shift] * GD_UNIT : 0.0f;
-  }
+  for (int v = 0; v < 5; ++v)
+    for (int t = 0; t < GD_RTAPS; ++t) c.k[v][t] = (float)k[v][t] * GD_UNIT;
   return c;
 }
 
-// The enlargement's sixteen vectors (output indices 0 .. 9 and 4n-6 .. 4n-1) laid on the frame [floor((j - 6) / 4), + 4) of their output.
 GdUp framed_up_vectors() {
+  int32_t k[16][GD_UTAPS];
+  pillow::x4_enlarge_vectors(k, true);
   GdUp c;
-  for (int v = 0; v < 16; ++v) {
-    int first, count;
-    int32_t k[GD_RTAPS];
-    const int j = v < 10 ? v : 4 * GD_REF_N - 16 + v;
-    pillow_row(GD_REF_N, 4 * GD_REF_N, j, &first, &count, k);
-    const int shift = first - ((j + 2) / 4 - 2);                     // 2, 2, 1, 1, 1, 1, then zeros
-    for (int t = 0; t < GD_UTAPS; ++t) c.k[v][t] = (t >= shift && t - shift < count) ? (float)k[t - shift] * GD_UNIT : 0.0f;
-  }
+  for (int v = 0; v < 16; ++v)
+    for (int t = 0; t < GD_UTAPS; ++t) c.k[v][t] = (float)k[v][t] * GD_UNIT;
   return c;
 }
-
-struct Range { long long lo, hi; };                  // bytes [lo, hi) of the address space
-inline bool meet(const Range& a, const Range& b) { return a.lo < b.hi && b.lo < a.hi; }
 
 int guidance_step(float* img, float* x_start, const float* cond01, const srgd_guidance_image* images, int n_images, float weight_x0,
                   float weight_img, void* scratch, hipStream_t st) {
   const std::string name("srgd_guidance_step");
-  if (n_images < 1) GD_FAIL(name + ": n_images must be >= 1");
-  if (!img || !x_start || !cond01 || !images || !scratch) GD_FAIL(name + ": null argument");
-  if (!std::isfinite(weight_x0) || !std::isfinite(weight_img)) GD_FAIL(name + ": weight_x0 and weight_img must be finite");
-  if ((((uintptr_t)img | (uintptr_t)x_start | (uintptr_t)cond01) & 3u) != 0) GD_FAIL(name + ": img, x_start and cond01 must be 4-byte aligned");
-  if (((uintptr_t)scratch & 255u) != 0) GD_FAIL(name + ": scratch must be 256-byte aligned");
+  if (n_images < 1) SRGD_EXT_FAIL(name + ": n_images must be >= 1");
+  if (!img || !x_start || !cond01 || !images || !scratch) SRGD_EXT_FAIL(name + ": null argument");
+  if (!std::isfinite(weight_x0) || !std::isfinite(weight_img)) SRGD_EXT_FAIL(name + ": weight_x0 and weight_img must be finite");
+  if ((((uintptr_t)img | (uintptr_t)x_start | (uintptr_t)cond01) & 3u) != 0) SRGD_EXT_FAIL(name + ": img, x_start and cond01 must be 4-byte aligned");
+  if (((uintptr_t)scratch & 255u) != 0) SRGD_EXT_FAIL(name + ": scratch must be 256-byte aligned");
   long long lo = 0, hi = 0, clo = 0, chi = 0;            // the elements the call covers in img / x_start and in cond01
   unsigned long long scr_bytes = 0;
   for (int i = 0; i < n_images; ++i) {                   // every image is checked before the first launch
     const srgd_guidance_image& m = images[i];
     const long long h = m.h, w = m.w;
-    if (h < 5 || w < 5) GD_FAIL(name + ": bad size (h and w must be >= 5: smaller windows overlap and depend on the size)");
-    if (m.Hp < 1 || m.Wp < 1 || 3ll * m.Hp * m.Wp >= (1ll << 31)) GD_FAIL(name + ": bad canvas (3*Hp*Wp must be in 1 .. 2^31 - 1)");
-    if (m.top < 0 || m.left < 0 || m.top + 4 * h > m.Hp || m.left + 4 * w > m.Wp) GD_FAIL(name + ": the crop box leaves its canvas");
+    if (h < 5 || w < 5) SRGD_EXT_FAIL(name + ": bad size (h and w must be >= 5: smaller windows overlap and depend on the size)");
+    if (m.Hp < 1 || m.Wp < 1 || 3ll * m.Hp * m.Wp >= (1ll << 31)) SRGD_EXT_FAIL(name + ": bad canvas (3*Hp*Wp must be in 1 .. 2^31 - 1)");
+    if (m.top < 0 || m.left < 0 || m.top + 4 * h > m.Hp || m.left + 4 * w > m.Wp) SRGD_EXT_FAIL(name + ": the crop box leaves its canvas");
     if (m.canvas_off < 0 || m.canvas_off >= (1ll << 40) || m.cond_off < 0 || m.cond_off >= (1ll << 40))
-      GD_FAIL(name + ": offset outside [0, 2^40)");
+      SRGD_EXT_FAIL(name + ": offset outside [0, 2^40)");
     const long long canvas = 3ll * m.Hp * m.Wp, planes = 48 * h * w;
     lo = i == 0 ? m.canvas_off : std::min<long long>(lo, m.canvas_off);
     hi = i == 0 ? m.canvas_off + canvas : std::max<long long>(hi, m.canvas_off + canvas);
@@ -302,14 +249,14 @@ int guidance_step(float* img, float* x_start, const float* cond01, const srgd_gu
     for (int j = i + 1; j < n_images; ++j) {
       const Range a{images[i].canvas_off, images[i].canvas_off + 3ll * images[i].Hp * images[i].Wp};
       const Range b{images[j].canvas_off, images[j].canvas_off + 3ll * images[j].Hp * images[j].Wp};
-      if (meet(a, b)) GD_FAIL(name + ": overlapping canvases");
+      if (a.meets(b)) SRGD_EXT_FAIL(name + ": overlapping canvases");
     }
   const Range r_img{(long long)(intptr_t)img + 4 * lo, (long long)(intptr_t)img + 4 * hi};
   const Range r_xs{(long long)(intptr_t)x_start + 4 * lo, (long long)(intptr_t)x_start + 4 * hi};
   const Range r_cond{(long long)(intptr_t)cond01 + 4 * clo, (long long)(intptr_t)cond01 + 4 * chi};
   const Range r_scr{(long long)(intptr_t)scratch, (long long)(intptr_t)scratch + (long long)scr_bytes};
-  if (meet(r_img, r_xs) || meet(r_img, r_cond) || meet(r_img, r_scr) || meet(r_xs, r_cond) || meet(r_xs, r_scr) || meet(r_cond, r_scr))
-    GD_FAIL(name + ": overlapping buffers (img, x_start, cond01 and scratch are disjoint)");
+  if (r_img.meets(r_xs) || r_img.meets(r_cond) || r_img.meets(r_scr) || r_xs.meets(r_cond) || r_xs.meets(r_scr) || r_cond.meets(r_scr))
+    SRGD_EXT_FAIL(name + ": overlapping buffers (img, x_start, cond01 and scratch are disjoint)");
   static const GdDown down = framed_down_vectors();
   static const GdUp up = framed_up_vectors();
   unsigned long long scr = 0;                            // the images' D, packed in image order (floats)
@@ -329,7 +276,7 @@ int guidance_step(float* img, float* x_start, const float* cond01, const srgd_gu
     hipLaunchKernelGGL(guidance_update_kernel, tiles, dim3(GD_THREADS), 0, st, tab, up, img, x_start, cond01, (const float*)scratch,
                        weight_x0, weight_img);
     const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) GD_FAIL(name + ": " + hipGetErrorString(err));
+    if (err != hipSuccess) SRGD_EXT_FAIL(name + ": " + hipGetErrorString(err));
   }
   return 0;
 }
@@ -339,14 +286,12 @@ int guidance_step(float* img, float* x_start, const float* cond01, const srgd_gu
 
 using namespace srgd;
 
-#define GD_EXPORT __attribute__((visibility("default")))
-
 extern "C" {
 
-GD_EXPORT const char* srgd_guidance_last_error(void) { return g_err.c_str(); }
+SRGD_EXT_EXPORT const char* srgd_guidance_last_error(void) { return g_err.c_str(); }
 
-GD_EXPORT int srgd_guidance_coeffs(float down[5][16], float up[16][4]) {
-  if (!down || !up) GD_FAIL("srgd_guidance_coeffs: null argument");
+SRGD_EXT_EXPORT int srgd_guidance_coeffs(float down[5][16], float up[16][4]) {
+  if (!down || !up) SRGD_EXT_FAIL("srgd_guidance_coeffs: null argument");
   const GdDown d = framed_down_vectors();
   const GdUp u = framed_up_vectors();
   for (int v = 0; v < 5; ++v)
@@ -356,8 +301,8 @@ GD_EXPORT int srgd_guidance_coeffs(float down[5][16], float up[16][4]) {
   return 0;
 }
 
-GD_EXPORT int srgd_guidance_step(float* img, float* x_start, const float* cond01, const srgd_guidance_image* images_host, int n_images,
-                                 float weight_x0, float weight_img, void* scratch, void* stream) {
+SRGD_EXT_EXPORT int srgd_guidance_step(float* img, float* x_start, const float* cond01, const srgd_guidance_image* images_host, int n_images,
+                                       float weight_x0, float weight_img, void* scratch, void* stream) {
   return guidance_step(img, x_start, cond01, images_host, n_images, weight_x0, weight_img, scratch, (hipStream_t)stream);
 }
 

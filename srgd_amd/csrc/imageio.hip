@@ -17,52 +17,22 @@
 
 #include "../../include/srgd_hip.h"
 #include "kernels.hpp"
+#include "pillow_coeffs.hpp"
 
 namespace srgd {
 namespace {
 
-constexpr int PREC_BITS = 32 - 8 - 2;
+constexpr int PREC_BITS = PILLOW_PREC_BITS;
 constexpr int KSIZE_MAX = 64;
+static_assert(KSIZE_MAX <= pillow::MAX_TAPS, "the widest table of pillow_coeffs.hpp");
 
-double bicubic_weight(double x) {
-  const double a = -0.5;
-  if (x < 0.0) x = -x;
-  if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
-  if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
-  return 0.0;
-}
-
-// bounds: [out][2] = (first input index, count); kk: [out][ksize] fixed-point weights
+// Pillow's bicubic table of an axis (pillow_coeffs.hpp).  bounds: [out][2] = (first input index, count); kk: [out][ksize] fixed-point weights
 int build_coeffs(int in_size, int out_size, std::vector<int>& bounds, std::vector<int>& kk, int* ksize_out) {
-  const double scale = (double)in_size / (double)out_size;
-  double filterscale = scale;
-  if (filterscale < 1.0) filterscale = 1.0;
-  const double support = 2.0 * filterscale;
-  const int ksize = (int)std::ceil(support) * 2 + 1;
+  const int ksize = pillow::ksize(in_size, out_size, pillow::BICUBIC);
   if (ksize > KSIZE_MAX) SRGD_FAIL("image resize: reduction factor too large for this build");
   bounds.assign((size_t)out_size * 2, 0);
   kk.assign((size_t)out_size * ksize, 0);
-  std::vector<double> w(ksize);
-  const double ss = 1.0 / filterscale;
-  for (int xx = 0; xx < out_size; ++xx) {
-    const double center = (xx + 0.5) * scale;
-    double ww = 0.0;
-    int xmin = (int)(center - support + 0.5);
-    if (xmin < 0) xmin = 0;
-    int xmax = (int)(center + support + 0.5);
-    if (xmax > in_size) xmax = in_size;
-    xmax -= xmin;
-    for (int x = 0; x < xmax; ++x) {
-      w[x] = bicubic_weight((x + xmin - center + 0.5) * ss);
-      ww += w[x];
-    }
-    for (int x = 0; x < xmax; ++x) {
-      if (ww != 0.0) w[x] /= ww;
-      kk[(size_t)xx * ksize + x] = w[x] < 0 ? (int)(-0.5 + w[x] * (1 << PREC_BITS)) : (int)(0.5 + w[x] * (1 << PREC_BITS));
-    }
-    bounds[2 * xx] = xmin;
-    bounds[2 * xx + 1] = xmax;
-  }
+  pillow::axis_table(in_size, out_size, pillow::BICUBIC, bounds.data(), kk.data());
   *ksize_out = ksize;
   return 0;
 }

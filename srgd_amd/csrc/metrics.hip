@@ -42,17 +42,12 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/srgd_metrics.h"
+#include "ext_common.hpp"
 
-// This file is a library of its own (libsrgd_metrics.so, include/srgd_metrics.h): it shares no symbol with the engine.
+// This file is a library of its own (libsrgd_metrics.so, include/srgd_metrics.h): it shares no symbol with the engine or the other nine
+// extension libraries; ext_common.hpp is their common host plumbing.
 namespace srgd {
 namespace {
-
-thread_local std::string g_err;
-#define MX_FAIL(msg)             \
-  do {                           \
-    g_err = std::string(msg);    \
-    return -1;                   \
-  } while (0)
 
 constexpr int MX_TW = 32, MX_TH = 8;                 // SSIM positions of a tile: one per thread
 constexpr int MX_TAPS = 11, MX_HALO = MX_TAPS - 1;
@@ -206,24 +201,24 @@ int metrics_images(const char* who, const float* out01, const uint8_t* ref_u8, c
                    const int32_t* hw, int n_images, int crop, double* results, double* scratch, hipStream_t st) {
   const std::string name(who);
   if (n_images == 0) return 0;
-  if (n_images < 0) MX_FAIL(name + ": n_images must be >= 0");
-  if (!out01 || !ref_u8 || !out_offsets || !ref_offsets || !hw || !results || !scratch) MX_FAIL(name + ": null argument");
-  if (crop < 0 || crop > (1 << 20)) MX_FAIL(name + ": bad crop");
-  if ((((uintptr_t)results | (uintptr_t)scratch) & 7u) != 0) MX_FAIL(name + ": results and scratch must be 8-byte aligned");
+  if (n_images < 0) SRGD_EXT_FAIL(name + ": n_images must be >= 0");
+  if (!out01 || !ref_u8 || !out_offsets || !ref_offsets || !hw || !results || !scratch) SRGD_EXT_FAIL(name + ": null argument");
+  if (crop < 0 || crop > (1 << 20)) SRGD_EXT_FAIL(name + ": bad crop");
+  if ((((uintptr_t)results | (uintptr_t)scratch) & 7u) != 0) SRGD_EXT_FAIL(name + ": results and scratch must be 8-byte aligned");
   auto tiles_of = [crop](long long h, long long w) {
     return ((w - 2 * crop - MX_HALO + MX_TW - 1) / MX_TW) * ((h - 2 * crop - MX_HALO + MX_TH - 1) / MX_TH);
   };
   unsigned long long total = 0;
   for (int i = 0; i < n_images; ++i) {                   // every image is checked before the first launch
     const long long h = hw[2 * i], w = hw[2 * i + 1];
-    if (h < 1 || w < 1) MX_FAIL(name + ": bad size");
-    if (out_offsets[i] < 0 || ref_offsets[i] < 0) MX_FAIL(name + ": negative offset");
-    if (3 * h * w > 0x7fffff00ll) MX_FAIL(name + ": image of more than 2^31 elements");
+    if (h < 1 || w < 1) SRGD_EXT_FAIL(name + ": bad size");
+    if (out_offsets[i] < 0 || ref_offsets[i] < 0) SRGD_EXT_FAIL(name + ": negative offset");
+    if (3 * h * w > 0x7fffff00ll) SRGD_EXT_FAIL(name + ": image of more than 2^31 elements");
     if (h - 2 * crop < MX_TAPS || w - 2 * crop < MX_TAPS)
-      MX_FAIL(name + ": an image needs at least 11 x 11 pixels inside the crop (no SSIM position otherwise)");
+      SRGD_EXT_FAIL(name + ": an image needs at least 11 x 11 pixels inside the crop (no SSIM position otherwise)");
     total += (unsigned long long)tiles_of(h, w);
   }
-  if (total > 0xffffffffull) MX_FAIL(name + ": more than 2^32 tiles in one call");
+  if (total > 0xffffffffull) SRGD_EXT_FAIL(name + ": more than 2^32 tiles in one call");
   MxWindow win;
   double sum = 0.0;
   for (int k = 0; k < MX_TAPS; ++k) {
@@ -256,7 +251,7 @@ int metrics_images(const char* who, const float* out01, const uint8_t* ref_u8, c
                        ref_u8, crop, scratch);
     hipLaunchKernelGGL(metrics_finish_kernel, dim3((unsigned)cnt), dim3(256), 0, st, tab, crop, scratch, results + (size_t)first * 4);
     const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) MX_FAIL(name + ": " + hipGetErrorString(err));
+    if (err != hipSuccess) SRGD_EXT_FAIL(name + ": " + hipGetErrorString(err));
   }
   return 0;
 }
@@ -266,22 +261,20 @@ int metrics_images(const char* who, const float* out01, const uint8_t* ref_u8, c
 
 using namespace srgd;
 
-#define MX_EXPORT __attribute__((visibility("default")))
-
 extern "C" {
 
-MX_EXPORT const char* srgd_image_metrics_last_error(void) { return g_err.c_str(); }
+SRGD_EXT_EXPORT const char* srgd_image_metrics_last_error(void) { return g_err.c_str(); }
 
-MX_EXPORT int srgd_image_metrics(const float* out01, const uint8_t* ref_u8, int h, int w, int crop, double* results, double* scratch,
-                       void* stream) {
+SRGD_EXT_EXPORT int srgd_image_metrics(const float* out01, const uint8_t* ref_u8, int h, int w, int crop, double* results, double* scratch,
+                             void* stream) {
   const int64_t off = 0;
   const int32_t hw[2] = {h, w};
   return metrics_images("srgd_image_metrics", out01, ref_u8, &off, &off, hw, 1, crop, results, scratch, (hipStream_t)stream);
 }
 
-MX_EXPORT int srgd_image_metrics_images(const float* out01, const uint8_t* ref_u8, const int64_t* out_offsets_host,
-                              const int64_t* ref_offsets_host, const int32_t* hw_host, int n_images, int crop, double* results,
-                              double* scratch, void* stream) {
+SRGD_EXT_EXPORT int srgd_image_metrics_images(const float* out01, const uint8_t* ref_u8, const int64_t* out_offsets_host,
+                                    const int64_t* ref_offsets_host, const int32_t* hw_host, int n_images, int crop, double* results,
+                                    double* scratch, void* stream) {
   return metrics_images("srgd_image_metrics_images", out01, ref_u8, out_offsets_host, ref_offsets_host, hw_host, n_images, crop,
                         results, scratch, (hipStream_t)stream);
 }

@@ -26,19 +26,13 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/srgd_resize.h"
+#include "ext_common.hpp"
 
-// This file is a library of its own (libsrgd_resize.so, include/srgd_resize.h): it shares no symbol with the other seven.
+// This file is a library of its own (libsrgd_resize.so, include/srgd_resize.h): it shares no symbol with the engine or the other nine
+// extension libraries; ext_common.hpp is their common host plumbing.
 namespace srgd {
 namespace {
 
-thread_local std::string g_err;
-#define RS_FAIL(msg)             \
-  do {                           \
-    g_err = std::string(msg);    \
-    return -1;                   \
-  } while (0)
-
-constexpr int RS_PREC_BITS = 32 - 8 - 2;
 constexpr int RS_THREADS = 256;
 constexpr int RS_MAX_IMAGES = 128;                   // records travel as a kernel argument (3.5 KiB)
 constexpr int RS_MAX_TAPS = SRGD_RESIZE_MAX_TAPS;
@@ -51,6 +45,8 @@ static_assert(3 * ((RS_HW - 1) * SRGD_RESIZE_MAX_RATIO + 2 * 3 * SRGD_RESIZE_MAX
 static_assert(RS_THREADS == RS_HW * (RS_HR / 2), "horizontal pass: a thread per output pixel and pair of rows");
 static_assert(RS_THREADS == (RS_VB / 4) * 4 && RS_VR % 4 == 0, "vertical pass: a thread per dword, four rows at a time");
 static_assert(2 * (int)(3 * SRGD_RESIZE_MAX_RATIO) + 1 == RS_MAX_TAPS, "lanczos at 8 : 1 is the widest table");
+static_assert(SRGD_RESIZE_LANCZOS == pillow::LANCZOS && SRGD_RESIZE_BILINEAR == pillow::BILINEAR && SRGD_RESIZE_BICUBIC == pillow::BICUBIC &&
+              RS_MAX_TAPS <= pillow::MAX_TAPS, "the filters and the widest table of pillow_coeffs.hpp");
 
 struct RsImage {                                     // offsets in units of 16 bytes: [0, 2^36) bytes
   unsigned src16, dst16, scr16, tab16;
@@ -59,11 +55,6 @@ struct RsImage {                                     // offsets in units of 16 b
 };
 struct RsTable { RsImage im[RS_MAX_IMAGES]; };
 static_assert(sizeof(RsTable) <= 3584, "the records and five pointers stay below 4 KiB of kernel arguments");
-
-__device__ __forceinline__ int rs_clip8(int acc) {
-  const int v = acc >> RS_PREC_BITS;                 // arithmetic shift, as Pillow's clip8 lookup index
-  return v < 0 ? 0 : (v > 255 ? 255 : v);
-}
 
 // Horizontal pass: src -> scratch (-> dst where the vertical pass is skipped).
 __global__ __launch_bounds__(RS_THREADS) void resize_horizontal_kernel(RsTable tab, const unsigned char* __restrict__ src,
@@ -122,8 +113,8 @@ __global__ __launch_bounds__(RS_THREADS) void resize_horizontal_kernel(RsTable t
       const unsigned char* p0 = rows + rg * RS_HSPAN + off;
       const unsigned char* p1 = p0 + (RS_HR / 2) * RS_HSPAN;
       const int* k = kk + x * kh;
-      int acc0[3] = {1 << (RS_PREC_BITS - 1), 1 << (RS_PREC_BITS - 1), 1 << (RS_PREC_BITS - 1)};
-      int acc1[3] = {1 << (RS_PREC_BITS - 1), 1 << (RS_PREC_BITS - 1), 1 << (RS_PREC_BITS - 1)};
+      int acc0[3] = {1 << (PILLOW_PREC_BITS - 1), 1 << (PILLOW_PREC_BITS - 1), 1 << (PILLOW_PREC_BITS - 1)};
+      int acc1[3] = {1 << (PILLOW_PREC_BITS - 1), 1 << (PILLOW_PREC_BITS - 1), 1 << (PILLOW_PREC_BITS - 1)};
       for (int t = 0; t < count; ++t) {
         const int kt = k[t];
 #pragma unroll
@@ -134,8 +125,8 @@ __global__ __launch_bounds__(RS_THREADS) void resize_horizontal_kernel(RsTable t
       }
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
-        res[rg * RS_HOUT + 3 * x + c] = (unsigned char)rs_clip8(acc0[c]);
-        res[(rg + RS_HR / 2) * RS_HOUT + 3 * x + c] = (unsigned char)rs_clip8(acc1[c]);
+        res[rg * RS_HOUT + 3 * x + c] = (unsigned char)clip8(acc0[c]);
+        res[(rg + RS_HR / 2) * RS_HOUT + 3 * x + c] = (unsigned char)clip8(acc1[c]);
       }
     }
   }
@@ -192,10 +183,10 @@ __global__ __launch_bounds__(RS_THREADS) void resize_vertical_kernel(RsTable tab
     const int ymin = kv != 0 ? min(max(bnd[2 * r], 0), h_in - 1) : yo;
     const int count = kv != 0 ? max(min(min(bnd[2 * r + 1], kv), h_in - ymin), 0) : 1;
     const int* k = kk + r * kv;
-    int acc[4] = {1 << (RS_PREC_BITS - 1), 1 << (RS_PREC_BITS - 1), 1 << (RS_PREC_BITS - 1), 1 << (RS_PREC_BITS - 1)};
+    int acc[4] = {1 << (PILLOW_PREC_BITS - 1), 1 << (PILLOW_PREC_BITS - 1), 1 << (PILLOW_PREC_BITS - 1), 1 << (PILLOW_PREC_BITS - 1)};
     const unsigned char* p = in + (size_t)ymin * (size_t)row_bytes + (size_t)gb;
     for (int t = 0; t < count; ++t, p += row_bytes) {
-      const int kt = kv != 0 ? k[t] : 1 << RS_PREC_BITS;
+      const int kt = kv != 0 ? k[t] : 1 << PILLOW_PREC_BITS;
       unsigned d = 0u;
       if (dwords) {
         d = *reinterpret_cast<const unsigned*>(p);
@@ -210,128 +201,58 @@ __global__ __launch_bounds__(RS_THREADS) void resize_vertical_kernel(RsTable tab
     }
     unsigned char* o = out + (size_t)yo * (size_t)row_bytes + (size_t)gb;
     if (dwords) {
-      *reinterpret_cast<unsigned*>(o) = (unsigned)rs_clip8(acc[0]) | (unsigned)rs_clip8(acc[1]) << 8 | (unsigned)rs_clip8(acc[2]) << 16 |
-                                        (unsigned)rs_clip8(acc[3]) << 24;
+      *reinterpret_cast<unsigned*>(o) = (unsigned)clip8(acc[0]) | (unsigned)clip8(acc[1]) << 8 | (unsigned)clip8(acc[2]) << 16 |
+                                        (unsigned)clip8(acc[3]) << 24;
     } else {
 #pragma unroll
       for (int b = 0; b < 4; ++b) {
-        if (b < nbytes) o[b] = (unsigned char)rs_clip8(acc[b]);
+        if (b < nbytes) o[b] = (unsigned char)clip8(acc[b]);
       }
     }
   }
 }
 
-// ------------------------------------------------------------------------------------------------ host: Pillow's tables
-double bicubic_weight(double x) {
-  const double a = -0.5;
-  if (x < 0.0) x = -x;
-  if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
-  if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
-  return 0.0;
-}
-
-double bilinear_weight(double x) {
-  if (x < 0.0) x = -x;
-  if (x < 1.0) return 1.0 - x;
-  return 0.0;
-}
-
-double sinc_weight(double x) {
-  if (x == 0.0) return 1.0;
-  x = x * M_PI;
-  return sin(x) / x;
-}
-
-double lanczos_weight(double x) {
-  if (-3.0 <= x && x < 3.0) return sinc_weight(x) * sinc_weight(x / 3);
-  return 0.0;
-}
-
-double filter_support(int filter) {
-  return filter == SRGD_RESIZE_BICUBIC ? 2.0 : (filter == SRGD_RESIZE_BILINEAR ? 1.0 : (filter == SRGD_RESIZE_LANCZOS ? 3.0 : 0.0));
-}
-
+// ------------------------------------------------------------------------------------------------ host (Pillow's tables: pillow_coeffs.hpp)
 const char* axis_problem(long long in_size, long long out_size) {
   if (in_size < 1 || out_size < 1 || in_size > SRGD_RESIZE_MAX_SIDE || out_size > SRGD_RESIZE_MAX_SIDE) return "bad size (every size is in 1 .. 16384)";
   if (in_size > SRGD_RESIZE_MAX_RATIO * out_size || out_size > SRGD_RESIZE_MAX_RATIO * in_size) return "ratio out of range (at most 8 either way, per axis)";
   return nullptr;
 }
 
-// Pillow's ksize of a checked axis
-int axis_ksize(int in_size, int out_size, int filter) {
-  const double scale = (double)in_size / (double)out_size;
-  const double filterscale = scale < 1.0 ? 1.0 : scale;
-  return (int)ceil(filter_support(filter) * filterscale) * 2 + 1;
-}
-
-// Pillow's precompute_coeffs + normalize_coeffs_8bpc of a checked axis
-void axis_table(int in_size, int out_size, int filter, int32_t* bounds, int32_t* coeffs) {
-  const double scale = (double)in_size / (double)out_size;
-  const double filterscale = scale < 1.0 ? 1.0 : scale;
-  const double support = filter_support(filter) * filterscale;
-  const int ksize = (int)ceil(support) * 2 + 1;
-  const double ss = 1.0 / filterscale;
-  for (int xx = 0; xx < out_size; ++xx) {
-    const double center = (xx + 0.5) * scale;
-    double w[RS_MAX_TAPS], ww = 0.0;
-    int xmin = (int)(center - support + 0.5);
-    if (xmin < 0) xmin = 0;
-    int xmax = (int)(center + support + 0.5);
-    if (xmax > in_size) xmax = in_size;
-    xmax -= xmin;
-    if (xmax > ksize) xmax = ksize;                                    // never taken: ksize bounds every window
-    for (int x = 0; x < xmax; ++x) {
-      const double arg = (x + xmin - center + 0.5) * ss;
-      w[x] = filter == SRGD_RESIZE_BICUBIC ? bicubic_weight(arg) : (filter == SRGD_RESIZE_BILINEAR ? bilinear_weight(arg) : lanczos_weight(arg));
-      ww += w[x];
-    }
-    int32_t* k = coeffs + (size_t)xx * (size_t)ksize;
-    for (int x = 0; x < ksize; ++x) k[x] = 0;
-    for (int x = 0; x < xmax; ++x) {
-      if (ww != 0.0) w[x] /= ww;
-      k[x] = w[x] < 0 ? (int)(-0.5 + w[x] * (1 << RS_PREC_BITS)) : (int)(0.5 + w[x] * (1 << RS_PREC_BITS));
-    }
-    bounds[2 * xx] = xmin;
-    bounds[2 * xx + 1] = xmax;
-  }
-}
-
-inline long long round16(long long n) { return (n + 15) & ~15ll; }
-
 int resize_images(const void* src, void* dst, const srgd_resize_image* images, int n_images, int filter, const void* tables,
                   long long tables_bytes, void* scratch, long long scratch_bytes, hipStream_t st) {
   const std::string name("srgd_resize_u8_images");
-  if (n_images < 1) RS_FAIL(name + ": n_images must be >= 1");
-  if (!src || !dst || !images || !tables || !scratch) RS_FAIL(name + ": null argument");
-  if (filter_support(filter) == 0.0) RS_FAIL(name + ": unknown filter (1 lanczos, 2 bilinear, 3 bicubic)");
-  if (((uintptr_t)scratch & 15u) != 0) RS_FAIL(name + ": scratch must be 16-byte aligned");
-  if (((uintptr_t)tables & 15u) != 0) RS_FAIL(name + ": tables must be 16-byte aligned");
+  if (n_images < 1) SRGD_EXT_FAIL(name + ": n_images must be >= 1");
+  if (!src || !dst || !images || !tables || !scratch) SRGD_EXT_FAIL(name + ": null argument");
+  if (pillow::filter_support(filter) == 0.0) SRGD_EXT_FAIL(name + ": unknown filter (1 lanczos, 2 bilinear, 3 bicubic)");
+  if (((uintptr_t)scratch & 15u) != 0) SRGD_EXT_FAIL(name + ": scratch must be 16-byte aligned");
+  if (((uintptr_t)tables & 15u) != 0) SRGD_EXT_FAIL(name + ": tables must be 16-byte aligned");
   long long scr = 0, src_lo = 0, src_hi = 0, dst_lo = 0, dst_hi = 0;
   for (int i = 0; i < n_images; ++i) {                   // every image is checked before the first launch
     const srgd_resize_image& im = images[i];
     const char* problem = axis_problem(im.h_in, im.h_out);
     if (!problem) problem = axis_problem(im.w_in, im.w_out);
-    if (problem) RS_FAIL(name + ": " + problem);
+    if (problem) SRGD_EXT_FAIL(name + ": " + problem);
     for (const long long off : {(long long)im.src_off, (long long)im.dst_off, (long long)im.tab_off}) {
-      if (off < 0 || off >= (1ll << 36)) RS_FAIL(name + ": offset outside [0, 2^36)");
-      if ((off & 15) != 0) RS_FAIL(name + ": offset is not a multiple of 16");
+      if (off < 0 || off >= (1ll << 36)) SRGD_EXT_FAIL(name + ": offset outside [0, 2^36)");
+      if ((off & 15) != 0) SRGD_EXT_FAIL(name + ": offset is not a multiple of 16");
     }
     long long need = 0;                                  // bytes of the image's tables
-    if (im.w_in != im.w_out) need += 4ll * im.w_out * (2 + axis_ksize(im.w_in, im.w_out, filter));
-    if (im.h_in != im.h_out) need += 4ll * im.h_out * (2 + axis_ksize(im.h_in, im.h_out, filter));
-    if (im.tab_off + need > tables_bytes) RS_FAIL(name + ": tables_bytes is too small for the images' tables");
-    scr += round16(3ll * im.h_in * im.w_out);
+    if (im.w_in != im.w_out) need += 4ll * im.w_out * (2 + pillow::ksize(im.w_in, im.w_out, filter));
+    if (im.h_in != im.h_out) need += 4ll * im.h_out * (2 + pillow::ksize(im.h_in, im.h_out, filter));
+    if (im.tab_off + need > tables_bytes) SRGD_EXT_FAIL(name + ": tables_bytes is too small for the images' tables");
+    scr += round_up(3ll * im.h_in * im.w_out, 16ll);
     const long long s_end = im.src_off + 3ll * im.h_in * im.w_in, d_end = im.dst_off + 3ll * im.h_out * im.w_out;
     src_lo = i == 0 ? (long long)im.src_off : std::min<long long>(src_lo, im.src_off);
     src_hi = i == 0 ? s_end : std::max(src_hi, s_end);
     dst_lo = i == 0 ? (long long)im.dst_off : std::min<long long>(dst_lo, im.dst_off);
     dst_hi = i == 0 ? d_end : std::max(dst_hi, d_end);
   }
-  if (scr > scratch_bytes) RS_FAIL(name + ": scratch_bytes is too small (sum of 3 * h_in * w_out, each rounded up to 16)");
-  if (scr > (1ll << 36)) RS_FAIL(name + ": scratch beyond 2^36 bytes");
+  if (scr > scratch_bytes) SRGD_EXT_FAIL(name + ": scratch_bytes is too small (sum of 3 * h_in * w_out, each rounded up to 16)");
+  if (scr > (1ll << 36)) SRGD_EXT_FAIL(name + ": scratch beyond 2^36 bytes");
   const long long s0 = (long long)(intptr_t)src + src_lo, s1 = (long long)(intptr_t)src + src_hi;
   const long long d0 = (long long)(intptr_t)dst + dst_lo, d1 = (long long)(intptr_t)dst + dst_hi;
-  if (s0 < d1 && d0 < s1) RS_FAIL(name + ": the source images and the destination images overlap");
+  if (s0 < d1 && d0 < s1) SRGD_EXT_FAIL(name + ": the source images and the destination images overlap");
   scr = 0;                                               // the images' scratch, packed in image order
   for (int first = 0; first < n_images; first += RS_MAX_IMAGES) {     // one launch sequence per RS_MAX_IMAGES images
     const int cnt = std::min(RS_MAX_IMAGES, n_images - first);
@@ -340,12 +261,12 @@ int resize_images(const void* src, void* dst, const srgd_resize_image* images, i
     for (int k = 0; k < RS_MAX_IMAGES; ++k) tab.im[k] = RsImage{0u, 0u, 0u, 0u, 1, 1, 1, 1, 0, 0, 0, 0};
     for (int k = 0; k < cnt; ++k) {
       const srgd_resize_image& im = images[first + k];
-      const int kh = im.w_in != im.w_out ? axis_ksize(im.w_in, im.w_out, filter) : 0;
-      const int kv = im.h_in != im.h_out ? axis_ksize(im.h_in, im.h_out, filter) : 0;
+      const int kh = im.w_in != im.w_out ? pillow::ksize(im.w_in, im.w_out, filter) : 0;
+      const int kv = im.h_in != im.h_out ? pillow::ksize(im.h_in, im.h_out, filter) : 0;
       tab.im[k] = RsImage{(unsigned)(im.src_off >> 4), (unsigned)(im.dst_off >> 4), (unsigned)(scr >> 4), (unsigned)(im.tab_off >> 4),
                           (unsigned short)im.h_in, (unsigned short)im.w_in, (unsigned short)im.h_out, (unsigned short)im.w_out,
                           (unsigned char)kh, (unsigned char)kv, 0, 0};
-      scr += round16(3ll * im.h_in * im.w_out);
+      scr += round_up(3ll * im.h_in * im.w_out, 16ll);
       if (kh != 0) h_tiles = std::max(h_tiles, (unsigned)((im.w_out + RS_HW - 1) / RS_HW) * (unsigned)((im.h_in + RS_HR - 1) / RS_HR));
       if (kv != 0 || kh == 0)
         v_tiles = std::max(v_tiles, (unsigned)((3 * im.w_out + RS_VB - 1) / RS_VB) * (unsigned)((im.h_out + RS_VR - 1) / RS_VR));
@@ -357,7 +278,7 @@ int resize_images(const void* src, void* dst, const srgd_resize_image* images, i
       hipLaunchKernelGGL(resize_vertical_kernel, dim3(v_tiles, (unsigned)cnt), dim3(RS_THREADS), 0, st, tab, (const unsigned char*)src,
                          (const unsigned char*)scratch, (unsigned char*)dst, (const unsigned char*)tables);
     const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) RS_FAIL(name + ": " + hipGetErrorString(err));
+    if (err != hipSuccess) SRGD_EXT_FAIL(name + ": " + hipGetErrorString(err));
   }
   return 0;
 }
@@ -367,28 +288,26 @@ int resize_images(const void* src, void* dst, const srgd_resize_image* images, i
 
 using namespace srgd;
 
-#define RS_EXPORT __attribute__((visibility("default")))
-
 extern "C" {
 
-RS_EXPORT const char* srgd_resize_last_error(void) { return g_err.c_str(); }
+SRGD_EXT_EXPORT const char* srgd_resize_last_error(void) { return g_err.c_str(); }
 
-RS_EXPORT int srgd_resize_ksize(int in_size, int out_size, int filter) {
-  if (filter_support(filter) == 0.0) RS_FAIL("srgd_resize_ksize: unknown filter (1 lanczos, 2 bilinear, 3 bicubic)");
-  if (const char* problem = axis_problem(in_size, out_size)) RS_FAIL(std::string("srgd_resize_ksize: ") + problem);
-  return axis_ksize(in_size, out_size, filter);
+SRGD_EXT_EXPORT int srgd_resize_ksize(int in_size, int out_size, int filter) {
+  if (pillow::filter_support(filter) == 0.0) SRGD_EXT_FAIL("srgd_resize_ksize: unknown filter (1 lanczos, 2 bilinear, 3 bicubic)");
+  if (const char* problem = axis_problem(in_size, out_size)) SRGD_EXT_FAIL(std::string("srgd_resize_ksize: ") + problem);
+  return pillow::ksize(in_size, out_size, filter);
 }
 
-RS_EXPORT int srgd_resize_coeffs(int in_size, int out_size, int filter, int32_t* bounds, int32_t* coeffs) {
-  if (!bounds || !coeffs) RS_FAIL("srgd_resize_coeffs: null argument");
-  if (filter_support(filter) == 0.0) RS_FAIL("srgd_resize_coeffs: unknown filter (1 lanczos, 2 bilinear, 3 bicubic)");
-  if (const char* problem = axis_problem(in_size, out_size)) RS_FAIL(std::string("srgd_resize_coeffs: ") + problem);
-  axis_table(in_size, out_size, filter, bounds, coeffs);
+SRGD_EXT_EXPORT int srgd_resize_coeffs(int in_size, int out_size, int filter, int32_t* bounds, int32_t* coeffs) {
+  if (!bounds || !coeffs) SRGD_EXT_FAIL("srgd_resize_coeffs: null argument");
+  if (pillow::filter_support(filter) == 0.0) SRGD_EXT_FAIL("srgd_resize_coeffs: unknown filter (1 lanczos, 2 bilinear, 3 bicubic)");
+  if (const char* problem = axis_problem(in_size, out_size)) SRGD_EXT_FAIL(std::string("srgd_resize_coeffs: ") + problem);
+  pillow::axis_table(in_size, out_size, filter, bounds, coeffs);
   return 0;
 }
 
-RS_EXPORT int srgd_resize_u8_images(const void* src, void* dst, const srgd_resize_image* images_host, int n_images, int filter,
-                                    const void* tables, int64_t tables_bytes, void* scratch, int64_t scratch_bytes, void* stream) {
+SRGD_EXT_EXPORT int srgd_resize_u8_images(const void* src, void* dst, const srgd_resize_image* images_host, int n_images, int filter,
+                                          const void* tables, int64_t tables_bytes, void* scratch, int64_t scratch_bytes, void* stream) {
   return resize_images(src, dst, images_host, n_images, filter, tables, (long long)tables_bytes, scratch, (long long)scratch_bytes,
                        (hipStream_t)stream);
 }

@@ -27,17 +27,12 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/srgd_selfens.h"
+#include "ext_common.hpp"
 
-// This file is a library of its own (libsrgd_selfens.so, include/srgd_selfens.h): it shares no symbol with the other ten.
+// This file is a library of its own (libsrgd_selfens.so, include/srgd_selfens.h): it shares no symbol with the engine or the other nine
+// extension libraries; ext_common.hpp is their common host plumbing.
 namespace srgd {
 namespace {
-
-thread_local std::string g_err;
-#define SE_FAIL(msg)             \
-  do {                           \
-    g_err = std::string(msg);    \
-    return -1;                   \
-  } while (0)
 
 constexpr int SE_THREADS = 256;
 constexpr int SE_MAX_IMAGES = SRGD_SELFENS_MAX_IMAGES;       // records travel as a kernel argument
@@ -260,41 +255,25 @@ const char* offset_problem(long long off) {
 
 constexpr int inverse_op(int op) { return op == 5 ? 6 : (op == 6 ? 5 : op); }
 
-// the byte range that a set of images covers in a buffer, and whether two such ranges meet
-struct Range {
-  long long lo = 0, hi = 0;
-  bool any = false;
-  void add(long long off, long long bytes) {
-    lo = any ? std::min(lo, off) : off;
-    hi = any ? std::max(hi, off + bytes) : off + bytes;
-    any = true;
-  }
-  bool meets(const void* base, const Range& other, const void* other_base) const {
-    const long long a0 = (long long)(intptr_t)base + lo, a1 = (long long)(intptr_t)base + hi;
-    const long long b0 = (long long)(intptr_t)other_base + other.lo, b1 = (long long)(intptr_t)other_base + other.hi;
-    return a0 < b1 && b0 < a1;
-  }
-};
-
 unsigned tiles_of(long long h, long long w) { return (unsigned)(((h + SE_TILE - 1) / SE_TILE) * ((w + SE_TILE - 1) / SE_TILE)); }
 
 int transform(const void* src, void* dst, const srgd_selfens_record* records, int n, hipStream_t st) {
   const std::string name("srgd_selfens_transform");
-  if (n < 1) SE_FAIL(name + ": n must be >= 1");
-  if (!src || !dst || !records) SE_FAIL(name + ": null argument");
-  if ((((uintptr_t)src | (uintptr_t)dst) & 15u) != 0) SE_FAIL(name + ": src and dst must be 16-byte aligned");
+  if (n < 1) SRGD_EXT_FAIL(name + ": n must be >= 1");
+  if (!src || !dst || !records) SRGD_EXT_FAIL(name + ": null argument");
+  if ((((uintptr_t)src | (uintptr_t)dst) & 15u) != 0) SRGD_EXT_FAIL(name + ": src and dst must be 16-byte aligned");
   Range s, d;
   for (int i = 0; i < n; ++i) {                          // every image is checked before the first launch
     const srgd_selfens_record& r = records[i];
-    if (const char* problem = size_problem(r.h, r.w)) SE_FAIL(name + ": " + problem);
-    if (r.op < 0 || r.op > 7) SE_FAIL(name + ": op outside 0 .. 7");
+    if (const char* problem = size_problem(r.h, r.w)) SRGD_EXT_FAIL(name + ": " + problem);
+    if (r.op < 0 || r.op > 7) SRGD_EXT_FAIL(name + ": op outside 0 .. 7");
     for (const long long off : {(long long)r.src_off, (long long)r.dst_off}) {
-      if (const char* p = offset_problem(off)) SE_FAIL(name + ": " + p);
+      if (const char* p = offset_problem(off)) SRGD_EXT_FAIL(name + ": " + p);
     }
     s.add(r.src_off, 3ll * r.h * r.w);
     d.add(r.dst_off, 3ll * r.h * r.w);
   }
-  if (s.meets(src, d, dst)) SE_FAIL(name + ": the source images and the destination images overlap");
+  if (s.meets(src, d, dst)) SRGD_EXT_FAIL(name + ": the source images and the destination images overlap");
   for (int first = 0; first < n; first += SE_MAX_IMAGES) {            // one launch per SE_MAX_IMAGES images
     const int cnt = std::min(SE_MAX_IMAGES, n - first);
     SeTable<1> tab;
@@ -310,34 +289,34 @@ int transform(const void* src, void* dst, const srgd_selfens_record* records, in
     hipLaunchKernelGGL(selfens_transform_kernel, dim3(blocks, (unsigned)cnt), dim3(SE_THREADS), 0, st, tab, (const unsigned char*)src,
                        (unsigned char*)dst);
     const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) SE_FAIL(name + ": " + hipGetErrorString(err));
+    if (err != hipSuccess) SRGD_EXT_FAIL(name + ": " + hipGetErrorString(err));
   }
   return 0;
 }
 
 int merge(const void* src, void* dst, float* mean01, const srgd_selfens_image* images, int n_images, hipStream_t st) {
   const std::string name("srgd_selfens_merge");
-  if (n_images < 1) SE_FAIL(name + ": n_images must be >= 1");
-  if (!src || !dst || !images) SE_FAIL(name + ": null argument");
-  if ((((uintptr_t)src | (uintptr_t)dst) & 15u) != 0) SE_FAIL(name + ": src and dst_u8 must be 16-byte aligned");
-  if (((uintptr_t)mean01 & 3u) != 0) SE_FAIL(name + ": mean01 must be 4-byte aligned");
+  if (n_images < 1) SRGD_EXT_FAIL(name + ": n_images must be >= 1");
+  if (!src || !dst || !images) SRGD_EXT_FAIL(name + ": null argument");
+  if ((((uintptr_t)src | (uintptr_t)dst) & 15u) != 0) SRGD_EXT_FAIL(name + ": src and dst_u8 must be 16-byte aligned");
+  if (((uintptr_t)mean01 & 3u) != 0) SRGD_EXT_FAIL(name + ": mean01 must be 4-byte aligned");
   Range s, d;
   for (int i = 0; i < n_images; ++i) {                   // every image is checked before the first launch
     const srgd_selfens_image& im = images[i];
-    if (im.n_src < 1 || im.n_src > SE_MAX_SOURCES) SE_FAIL(name + ": n_src outside 1 .. 8");
-    if (const char* problem = size_problem(im.H, im.W)) SE_FAIL(name + ": " + problem);
-    if (const char* p = offset_problem(im.dst_off)) SE_FAIL(name + ": " + p);
-    if (mean01 && im.mean01_off < 0) SE_FAIL(name + ": negative mean01 offset");
-    if (mean01 && im.mean01_off >= (1ll << 40)) SE_FAIL(name + ": mean01 offset beyond 2^40");
+    if (im.n_src < 1 || im.n_src > SE_MAX_SOURCES) SRGD_EXT_FAIL(name + ": n_src outside 1 .. 8");
+    if (const char* problem = size_problem(im.H, im.W)) SRGD_EXT_FAIL(name + ": " + problem);
+    if (const char* p = offset_problem(im.dst_off)) SRGD_EXT_FAIL(name + ": " + p);
+    if (mean01 && im.mean01_off < 0) SRGD_EXT_FAIL(name + ": negative mean01 offset");
+    if (mean01 && im.mean01_off >= (1ll << 40)) SRGD_EXT_FAIL(name + ": mean01 offset beyond 2^40");
     const long long bytes = 3ll * im.H * im.W;
     for (int j = 0; j < im.n_src; ++j) {
-      if (im.op[j] < 0 || im.op[j] > 7) SE_FAIL(name + ": op outside 0 .. 7");
-      if (const char* p = offset_problem(im.src_off[j])) SE_FAIL(name + ": " + p);
+      if (im.op[j] < 0 || im.op[j] > 7) SRGD_EXT_FAIL(name + ": op outside 0 .. 7");
+      if (const char* p = offset_problem(im.src_off[j])) SRGD_EXT_FAIL(name + ": " + p);
       s.add(im.src_off[j], bytes);
     }
     d.add(im.dst_off, bytes);
   }
-  if (s.meets(src, d, dst)) SE_FAIL(name + ": the source images and the destination images overlap");
+  if (s.meets(src, d, dst)) SRGD_EXT_FAIL(name + ": the source images and the destination images overlap");
   for (int first = 0; first < n_images; first += SE_MAX_IMAGES) {     // one launch per SE_MAX_IMAGES images
     const int cnt = std::min(SE_MAX_IMAGES, n_images - first);
     SeTable<SE_MAX_SOURCES> tab;
@@ -361,7 +340,7 @@ int merge(const void* src, void* dst, float* mean01, const srgd_selfens_image* i
     hipLaunchKernelGGL(selfens_merge_kernel, dim3(blocks, (unsigned)cnt), dim3(SE_THREADS), 0, st, tab, (const unsigned char*)src,
                        (unsigned char*)dst, mean01);
     const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) SE_FAIL(name + ": " + hipGetErrorString(err));
+    if (err != hipSuccess) SRGD_EXT_FAIL(name + ": " + hipGetErrorString(err));
   }
   return 0;
 }
@@ -371,18 +350,16 @@ int merge(const void* src, void* dst, float* mean01, const srgd_selfens_image* i
 
 using namespace srgd;
 
-#define SE_EXPORT __attribute__((visibility("default")))
-
 extern "C" {
 
-SE_EXPORT const char* srgd_selfens_last_error(void) { return g_err.c_str(); }
+SRGD_EXT_EXPORT const char* srgd_selfens_last_error(void) { return g_err.c_str(); }
 
-SE_EXPORT int srgd_selfens_transform(const void* src, void* dst, const srgd_selfens_record* records_host, int n, void* stream) {
+SRGD_EXT_EXPORT int srgd_selfens_transform(const void* src, void* dst, const srgd_selfens_record* records_host, int n, void* stream) {
   return transform(src, dst, records_host, n, (hipStream_t)stream);
 }
 
-SE_EXPORT int srgd_selfens_merge(const void* src, void* dst_u8, float* mean01, const srgd_selfens_image* images_host, int n_images,
-                                 void* stream) {
+SRGD_EXT_EXPORT int srgd_selfens_merge(const void* src, void* dst_u8, float* mean01, const srgd_selfens_image* images_host, int n_images,
+                                       void* stream) {
   return merge(src, dst_u8, mean01, images_host, n_images, (hipStream_t)stream);
 }
 

@@ -17,17 +17,12 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/srgd_solver.h"
+#include "ext_common.hpp"
 
-// This file is a library of its own (libsrgd_solver.so, include/srgd_solver.h): it shares no symbol with the other six.
+// This file is a library of its own (libsrgd_solver.so, include/srgd_solver.h): it shares no symbol with the engine or the other nine
+// extension libraries; ext_common.hpp is their common host plumbing.
 namespace srgd {
 namespace {
-
-thread_local std::string g_err;
-#define SV_FAIL(msg)             \
-  do {                           \
-    g_err = std::string(msg);    \
-    return -1;                   \
-  } while (0)
 
 constexpr int SV_THREADS = 256;
 constexpr int SV_ROWS = 8;                           // rows of a box per workgroup
@@ -86,22 +81,19 @@ __global__ __launch_bounds__(SV_THREADS) void solver_history_kernel(SvTable tab,
   }
 }
 
-struct Range { long long lo, hi; };                  // bytes [lo, hi) of the address space
-inline bool meet(const Range& a, const Range& b) { return a.lo < b.hi && b.lo < a.hi; }
-
 int history_step(float* img, const float* x_start, float* x_prev, const srgd_solver_image* recs, int n, float w, hipStream_t st) {
   const std::string name("srgd_solver_history_step");
-  if (n < 1) SV_FAIL(name + ": n must be >= 1");
-  if (!img || !x_start || !x_prev || !recs) SV_FAIL(name + ": null argument");
-  if (!std::isfinite(w)) SV_FAIL(name + ": w must be finite");
-  if ((((uintptr_t)img | (uintptr_t)x_start | (uintptr_t)x_prev) & 3u) != 0) SV_FAIL(name + ": img, x_start and x_prev must be 4-byte aligned");
+  if (n < 1) SRGD_EXT_FAIL(name + ": n must be >= 1");
+  if (!img || !x_start || !x_prev || !recs) SRGD_EXT_FAIL(name + ": null argument");
+  if (!std::isfinite(w)) SRGD_EXT_FAIL(name + ": w must be finite");
+  if ((((uintptr_t)img | (uintptr_t)x_start | (uintptr_t)x_prev) & 3u) != 0) SRGD_EXT_FAIL(name + ": img, x_start and x_prev must be 4-byte aligned");
   long long lo = 0, hi = 0;                              // the elements the call covers in the three buffers
   for (int i = 0; i < n; ++i) {                          // every image is checked before the first launch
     const srgd_solver_image& m = recs[i];
-    if (m.h < 1 || m.w < 1) SV_FAIL(name + ": bad size (h and w must be >= 1)");
-    if (m.Hp < 1 || m.Wp < 1 || (long long)m.Hp * m.Wp > ((1ll << 31) - 1) / 3) SV_FAIL(name + ": bad canvas (3*Hp*Wp must be in 1 .. 2^31 - 1)");
-    if (m.top < 0 || m.left < 0 || (long long)m.top + m.h > m.Hp || (long long)m.left + m.w > m.Wp) SV_FAIL(name + ": the box leaves its canvas");
-    if (m.canvas_off < 0 || m.canvas_off >= (1ll << 40)) SV_FAIL(name + ": offset outside [0, 2^40)");
+    if (m.h < 1 || m.w < 1) SRGD_EXT_FAIL(name + ": bad size (h and w must be >= 1)");
+    if (m.Hp < 1 || m.Wp < 1 || (long long)m.Hp * m.Wp > ((1ll << 31) - 1) / 3) SRGD_EXT_FAIL(name + ": bad canvas (3*Hp*Wp must be in 1 .. 2^31 - 1)");
+    if (m.top < 0 || m.left < 0 || (long long)m.top + m.h > m.Hp || (long long)m.left + m.w > m.Wp) SRGD_EXT_FAIL(name + ": the box leaves its canvas");
+    if (m.canvas_off < 0 || m.canvas_off >= (1ll << 40)) SRGD_EXT_FAIL(name + ": offset outside [0, 2^40)");
     const long long canvas = 3ll * m.Hp * m.Wp;
     lo = i == 0 ? m.canvas_off : std::min<long long>(lo, m.canvas_off);
     hi = i == 0 ? m.canvas_off + canvas : std::max<long long>(hi, m.canvas_off + canvas);
@@ -110,12 +102,12 @@ int history_step(float* img, const float* x_start, float* x_prev, const srgd_sol
     for (int j = i + 1; j < n; ++j) {
       const Range a{recs[i].canvas_off, recs[i].canvas_off + 3ll * recs[i].Hp * recs[i].Wp};
       const Range b{recs[j].canvas_off, recs[j].canvas_off + 3ll * recs[j].Hp * recs[j].Wp};
-      if (meet(a, b)) SV_FAIL(name + ": overlapping canvases");
+      if (a.meets(b)) SRGD_EXT_FAIL(name + ": overlapping canvases");
     }
   const Range r_img{(long long)(intptr_t)img + 4 * lo, (long long)(intptr_t)img + 4 * hi};
   const Range r_xs{(long long)(intptr_t)x_start + 4 * lo, (long long)(intptr_t)x_start + 4 * hi};
   const Range r_xp{(long long)(intptr_t)x_prev + 4 * lo, (long long)(intptr_t)x_prev + 4 * hi};
-  if (meet(r_img, r_xs) || meet(r_img, r_xp) || meet(r_xs, r_xp)) SV_FAIL(name + ": overlapping buffers (img, x_start and x_prev are disjoint)");
+  if (r_img.meets(r_xs) || r_img.meets(r_xp) || r_xs.meets(r_xp)) SRGD_EXT_FAIL(name + ": overlapping buffers (img, x_start and x_prev are disjoint)");
   const bool aligned16 = (((uintptr_t)img | (uintptr_t)x_start | (uintptr_t)x_prev) & 15u) == 0;
   for (int first = 0; first < n; first += SV_MAX_IMAGES) {            // one launch per SV_MAX_IMAGES images
     const int cnt = std::min(SV_MAX_IMAGES, n - first);
@@ -133,7 +125,7 @@ int history_step(float* img, const float* x_start, float* x_prev, const srgd_sol
     const dim3 grid((unsigned)((max_h + SV_ROWS - 1) / SV_ROWS), (unsigned)cnt, 3u);
     hipLaunchKernelGGL(solver_history_kernel, grid, dim3(SV_THREADS), 0, st, tab, img, x_start, x_prev, w);
     const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) SV_FAIL(name + ": " + hipGetErrorString(err));
+    if (err != hipSuccess) SRGD_EXT_FAIL(name + ": " + hipGetErrorString(err));
   }
   return 0;
 }
@@ -143,14 +135,12 @@ int history_step(float* img, const float* x_start, float* x_prev, const srgd_sol
 
 using namespace srgd;
 
-#define SV_EXPORT __attribute__((visibility("default")))
-
 extern "C" {
 
-SV_EXPORT const char* srgd_solver_last_error(void) { return g_err.c_str(); }
+SRGD_EXT_EXPORT const char* srgd_solver_last_error(void) { return g_err.c_str(); }
 
-SV_EXPORT int srgd_solver_history_step(float* img, const float* x_start, float* x_prev, const srgd_solver_image* recs, int n, float w,
-                                       void* stream) {
+SRGD_EXT_EXPORT int srgd_solver_history_step(float* img, const float* x_start, float* x_prev, const srgd_solver_image* recs, int n, float w,
+                                             void* stream) {
   return history_step(img, x_start, x_prev, recs, n, w, (hipStream_t)stream);
 }
 

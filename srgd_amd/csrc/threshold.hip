@@ -31,17 +31,12 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/srgd_threshold.h"
+#include "ext_common.hpp"
 
-// This file is a library of its own (libsrgd_threshold.so, include/srgd_threshold.h): it shares no symbol with the other nine.
+// This file is a library of its own (libsrgd_threshold.so, include/srgd_threshold.h): it shares no symbol with the engine or the other nine
+// extension libraries; ext_common.hpp is their common host plumbing.
 namespace srgd {
 namespace {
-
-thread_local std::string g_err;
-#define TH_FAIL(msg)             \
-  do {                           \
-    g_err = std::string(msg);    \
-    return -1;                   \
-  } while (0)
 
 constexpr int TH_THREADS = 256;
 constexpr int TH_PER_THREAD = 16;
@@ -228,9 +223,9 @@ __global__ __launch_bounds__(TH_THREADS) void threshold_apply_kernel(ThBoxes tab
 
 int position(int64_t n, float q, int64_t* lo, int64_t* hi, float* frac) {
   const std::string name("srgd_threshold_position");
-  if (!lo || !hi || !frac) TH_FAIL(name + ": null argument");
-  if (n < 1) TH_FAIL(name + ": n must be >= 1");
-  if (!(q > 0.0f && q <= 1.0f)) TH_FAIL(name + ": q must be in (0, 1]");
+  if (!lo || !hi || !frac) SRGD_EXT_FAIL(name + ": null argument");
+  if (n < 1) SRGD_EXT_FAIL(name + ": n must be >= 1");
+  if (!(q > 0.0f && q <= 1.0f)) SRGD_EXT_FAIL(name + ": q must be in (0, 1]");
   const double pos = (double)q * (double)(n - 1);
   const double fl = std::floor(pos);
   *lo = (int64_t)fl;
@@ -239,29 +234,26 @@ int position(int64_t n, float q, int64_t* lo, int64_t* hi, float* frac) {
   return 0;
 }
 
-struct Range { long long lo, hi; };                  // bytes [lo, hi) of the address space
-inline bool meet(const Range& a, const Range& b) { return a.lo < b.hi && b.lo < a.hi; }
-
 int threshold_step(float* img, float* x_start, const srgd_threshold_image* images, int n_images, float q, float weight_img,
                    float* s_out, void* scratch, hipStream_t st) {
   const std::string name("srgd_threshold_step");
-  if (n_images < 1) TH_FAIL(name + ": n_images must be >= 1");
-  if (!img || !x_start || !images || !s_out || !scratch) TH_FAIL(name + ": null argument");
-  if (!(q > 0.0f && q <= 1.0f)) TH_FAIL(name + ": q must be in (0, 1]");
-  if (!std::isfinite(weight_img)) TH_FAIL(name + ": weight_img must be finite");
-  if ((((uintptr_t)img | (uintptr_t)x_start | (uintptr_t)s_out) & 3u) != 0) TH_FAIL(name + ": img, x_start and s_out must be 4-byte aligned");
-  if (((uintptr_t)scratch & 255u) != 0) TH_FAIL(name + ": scratch must be 256-byte aligned");
+  if (n_images < 1) SRGD_EXT_FAIL(name + ": n_images must be >= 1");
+  if (!img || !x_start || !images || !s_out || !scratch) SRGD_EXT_FAIL(name + ": null argument");
+  if (!(q > 0.0f && q <= 1.0f)) SRGD_EXT_FAIL(name + ": q must be in (0, 1]");
+  if (!std::isfinite(weight_img)) SRGD_EXT_FAIL(name + ": weight_img must be finite");
+  if ((((uintptr_t)img | (uintptr_t)x_start | (uintptr_t)s_out) & 3u) != 0) SRGD_EXT_FAIL(name + ": img, x_start and s_out must be 4-byte aligned");
+  if (((uintptr_t)scratch & 255u) != 0) SRGD_EXT_FAIL(name + ": scratch must be 256-byte aligned");
   long long lo = 0, hi = 0;                              // the elements the call covers in img / x_start
   for (int i = 0; i < n_images; ++i) {                   // every image is checked before the first launch
     const srgd_threshold_image& m = images[i];
-    if (m.H < 1 || m.W < 1) TH_FAIL(name + ": bad size (H and W must be >= 1)");
-    if (m.Hp < 1 || m.Wp < 1 || 3ll * m.Hp * m.Wp >= (1ll << 31)) TH_FAIL(name + ": bad canvas (3*Hp*Wp must be in 1 .. 2^31 - 1)");
+    if (m.H < 1 || m.W < 1) SRGD_EXT_FAIL(name + ": bad size (H and W must be >= 1)");
+    if (m.Hp < 1 || m.Wp < 1 || 3ll * m.Hp * m.Wp >= (1ll << 31)) SRGD_EXT_FAIL(name + ": bad canvas (3*Hp*Wp must be in 1 .. 2^31 - 1)");
     if (m.box_t < 0 || m.box_l < 0 || m.box_h < 1 || m.box_w < 1 || (long long)m.box_t + m.box_h > m.Hp || (long long)m.box_l + m.box_w > m.Wp)
-      TH_FAIL(name + ": the update box leaves its canvas");
+      SRGD_EXT_FAIL(name + ": the update box leaves its canvas");
     if (m.top < m.box_t || m.left < m.box_l || (long long)m.top + m.H > (long long)m.box_t + m.box_h ||
         (long long)m.left + m.W > (long long)m.box_l + m.box_w)
-      TH_FAIL(name + ": the statistics box leaves the update box");
-    if (m.canvas_off < 0 || m.canvas_off >= (1ll << 40)) TH_FAIL(name + ": offset outside [0, 2^40)");
+      SRGD_EXT_FAIL(name + ": the statistics box leaves the update box");
+    if (m.canvas_off < 0 || m.canvas_off >= (1ll << 40)) SRGD_EXT_FAIL(name + ": offset outside [0, 2^40)");
     const long long canvas = 3ll * m.Hp * m.Wp;
     lo = i == 0 ? m.canvas_off : std::min<long long>(lo, m.canvas_off);
     hi = i == 0 ? m.canvas_off + canvas : std::max<long long>(hi, m.canvas_off + canvas);
@@ -270,18 +262,18 @@ int threshold_step(float* img, float* x_start, const srgd_threshold_image* image
     for (int j = i + 1; j < n_images; ++j) {
       const Range a{images[i].canvas_off, images[i].canvas_off + 3ll * images[i].Hp * images[i].Wp};
       const Range b{images[j].canvas_off, images[j].canvas_off + 3ll * images[j].Hp * images[j].Wp};
-      if (meet(a, b)) TH_FAIL(name + ": overlapping canvases");
+      if (a.meets(b)) SRGD_EXT_FAIL(name + ": overlapping canvases");
     }
   const long long scr_bytes = (long long)n_images * TH_WORDS * 4;
   const Range r_img{(long long)(intptr_t)img + 4 * lo, (long long)(intptr_t)img + 4 * hi};
   const Range r_xs{(long long)(intptr_t)x_start + 4 * lo, (long long)(intptr_t)x_start + 4 * hi};
   const Range r_s{(long long)(intptr_t)s_out, (long long)(intptr_t)s_out + 4ll * n_images};
   const Range r_scr{(long long)(intptr_t)scratch, (long long)(intptr_t)scratch + scr_bytes};
-  if (meet(r_img, r_xs) || meet(r_img, r_s) || meet(r_img, r_scr) || meet(r_xs, r_s) || meet(r_xs, r_scr) || meet(r_s, r_scr))
-    TH_FAIL(name + ": overlapping buffers (img, x_start, s_out and scratch are disjoint)");
+  if (r_img.meets(r_xs) || r_img.meets(r_s) || r_img.meets(r_scr) || r_xs.meets(r_s) || r_xs.meets(r_scr) || r_s.meets(r_scr))
+    SRGD_EXT_FAIL(name + ": overlapping buffers (img, x_start, s_out and scratch are disjoint)");
   if (hipMemsetAsync(scratch, 0, (size_t)scr_bytes, st) != hipSuccess) {
     const hipError_t err = hipGetLastError();
-    TH_FAIL(name + ": " + hipGetErrorString(err));
+    SRGD_EXT_FAIL(name + ": " + hipGetErrorString(err));
   }
   for (int first = 0; first < n_images; first += TH_MAX_IMAGES) {     // one launch sequence per TH_MAX_IMAGES images
     const int cnt = std::min(TH_MAX_IMAGES, n_images - first);
@@ -314,7 +306,7 @@ int threshold_step(float* img, float* x_start, const srgd_threshold_image* image
     hipLaunchKernelGGL(threshold_apply_kernel, dim3(max_apply, (unsigned)cnt, 3u), dim3(TH_THREADS), 0, st, update, img, x_start,
                        (const unsigned*)scratch, weight_img, first);
     const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) TH_FAIL(name + ": " + hipGetErrorString(err));
+    if (err != hipSuccess) SRGD_EXT_FAIL(name + ": " + hipGetErrorString(err));
   }
   return 0;
 }
@@ -324,20 +316,18 @@ int threshold_step(float* img, float* x_start, const srgd_threshold_image* image
 
 using namespace srgd;
 
-#define TH_EXPORT __attribute__((visibility("default")))
-
 extern "C" {
 
-TH_EXPORT const char* srgd_threshold_last_error(void) { return g_err.c_str(); }
+SRGD_EXT_EXPORT const char* srgd_threshold_last_error(void) { return g_err.c_str(); }
 
-TH_EXPORT int srgd_threshold_position(int64_t n, float q, int64_t* lo, int64_t* hi, float* frac) { return position(n, q, lo, hi, frac); }
+SRGD_EXT_EXPORT int srgd_threshold_position(int64_t n, float q, int64_t* lo, int64_t* hi, float* frac) { return position(n, q, lo, hi, frac); }
 
-TH_EXPORT uint64_t srgd_threshold_scratch_bytes(int n_images) { return n_images < 1 ? 0ull : (uint64_t)n_images * TH_WORDS * 4ull; }
+SRGD_EXT_EXPORT uint64_t srgd_threshold_scratch_bytes(int n_images) { return n_images < 1 ? 0ull : (uint64_t)n_images * TH_WORDS * 4ull; }
 
-TH_EXPORT int srgd_threshold_chunk_elems(void) { return TH_CHUNK; }
+SRGD_EXT_EXPORT int srgd_threshold_chunk_elems(void) { return TH_CHUNK; }
 
-TH_EXPORT int srgd_threshold_step(float* img, float* x_start, const srgd_threshold_image* images_host, int n_images, float q,
-                                  float weight_img, float* s_out, void* scratch, void* stream) {
+SRGD_EXT_EXPORT int srgd_threshold_step(float* img, float* x_start, const srgd_threshold_image* images_host, int n_images, float q,
+                                        float weight_img, float* s_out, void* scratch, void* stream) {
   return threshold_step(img, x_start, images_host, n_images, q, weight_img, s_out, scratch, (hipStream_t)stream);
 }
 

@@ -34,15 +34,7 @@ def lib() -> C.CDLL:
     """Load the ensemble library (once).  Raises if it has not been built - no CPU fallback."""
     global _handle
     if _handle is None:
-        if not os.path.exists(LIB_PATH):
-            raise _lib.SrgdHipError(f"{LIB_PATH} is missing: build it with `python -m srgd_amd.build` (hipcc, gfx950). "
-                                    "The ensemble runs on the MI355X only; there is no CPU fallback.")
-        handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in PROTOTYPES.items():
-            fn = getattr(handle, name)
-            fn.restype = res
-            fn.argtypes = args
-        _handle = handle
+        _handle = _lib.load(LIB_PATH, PROTOTYPES, "The ensemble runs on the MI355X only")
     return _handle
 
 
@@ -99,7 +91,7 @@ def ensemble_flat_device(samples, sample_offsets, sizes, n_samples, mean_u8, std
                                               C.c_void_p(stats.data_ptr()), C.c_void_p(scratch.data_ptr()),
                                               C.c_void_p(torch.cuda.current_stream().cuda_stream))
     if rc != 0:
-        raise _lib.SrgdHipError(lib().srgd_image_ensemble_last_error().decode(errors="replace"))
+        raise _lib.error_of(lib(), "srgd_image_ensemble_last_error")
     return stats
 
 

@@ -41,15 +41,7 @@ def lib() -> C.CDLL:
     """Load the guidance library (once).  Raises if it has not been built - no CPU fallback."""
     global _handle
     if _handle is None:
-        if not os.path.exists(LIB_PATH):
-            raise _lib.SrgdHipError(f"{LIB_PATH} is missing: build it with `python -m srgd_amd.build` (hipcc, gfx950). "
-                                    "The guidance runs on the MI355X only; there is no CPU fallback.")
-        handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in PROTOTYPES.items():
-            fn = getattr(handle, name)
-            fn.restype = res
-            fn.argtypes = args
-        _handle = handle
+        _handle = _lib.load(LIB_PATH, PROTOTYPES, "The guidance runs on the MI355X only")
     return _handle
 
 
@@ -58,7 +50,7 @@ def coeffs():
     the frame of its output (include/srgd_guidance.h)."""
     down, up = ((C.c_float * 16) * 5)(), ((C.c_float * 4) * 16)()
     if lib().srgd_guidance_coeffs(C.cast(down, C.c_void_p), C.cast(up, C.c_void_p)) != 0:
-        raise _lib.SrgdHipError(lib().srgd_guidance_last_error().decode(errors="replace"))
+        raise _lib.error_of(lib(), "srgd_guidance_last_error")
     return [list(row) for row in down], [list(row) for row in up]
 
 
@@ -149,4 +141,4 @@ def guide_step_flat(img, x_start, cond01, recs, weight_x0, weight_img, scratch):
                                       len(recs), float(weight_x0), float(weight_img), C.c_void_p(scratch.data_ptr()),
                                       C.c_void_p(torch.cuda.current_stream().cuda_stream))
     if rc != 0:
-        raise _lib.SrgdHipError(lib().srgd_guidance_last_error().decode(errors="replace"))
+        raise _lib.error_of(lib(), "srgd_guidance_last_error")

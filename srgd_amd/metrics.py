@@ -29,15 +29,7 @@ def lib() -> C.CDLL:
     """Load the metrics library (once).  Raises if it has not been built - no CPU fallback."""
     global _handle
     if _handle is None:
-        if not os.path.exists(LIB_PATH):
-            raise _lib.SrgdHipError(f"{LIB_PATH} is missing: build it with `python -m srgd_amd.build` (hipcc, gfx950). "
-                                    "The metrics run on the MI355X only; there is no CPU fallback.")
-        handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in PROTOTYPES.items():
-            fn = getattr(handle, name)
-            fn.restype = res
-            fn.argtypes = args
-        _handle = handle
+        _handle = _lib.load(LIB_PATH, PROTOTYPES, "The metrics run on the MI355X only")
     return _handle
 
 
@@ -88,7 +80,7 @@ def metrics_flat_device(out, ref_u8, out_offsets, ref_offsets, sizes, crop_borde
                                              C.c_void_p(results.data_ptr()), C.c_void_p(scratch.data_ptr()),
                                              C.c_void_p(torch.cuda.current_stream().cuda_stream))
     if rc != 0:
-        raise _lib.SrgdHipError(lib().srgd_image_metrics_last_error().decode(errors="replace"))
+        raise _lib.error_of(lib(), "srgd_image_metrics_last_error")
     return results
 
 

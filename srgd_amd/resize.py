@@ -47,20 +47,12 @@ def lib() -> C.CDLL:
     """Load the resize library (once).  Raises if it has not been built - no CPU fallback."""
     global _handle
     if _handle is None:
-        if not os.path.exists(LIB_PATH):
-            raise _lib.SrgdHipError(f"{LIB_PATH} is missing: build it with `python -m srgd_amd.build` (hipcc, gfx950). "
-                                    "The resize runs on the MI355X only; there is no CPU fallback.")
-        handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in PROTOTYPES.items():
-            fn = getattr(handle, name)
-            fn.restype = res
-            fn.argtypes = args
-        _handle = handle
+        _handle = _lib.load(LIB_PATH, PROTOTYPES, "The resize runs on the MI355X only")
     return _handle
 
 
-def _last_error():
-    return lib().srgd_resize_last_error().decode(errors="replace")
+def _error():
+    return _lib.error_of(lib(), "srgd_resize_last_error")
 
 
 def check_filter(name):
@@ -92,7 +84,7 @@ def ksize(in_size, out_size, filter="bicubic"):
     """Taps of a row of the table ``in_size`` -> ``out_size`` (host only).  ``ValueError`` for what the library refuses."""
     k = lib().srgd_resize_ksize(int(in_size), int(out_size), FILTERS[check_filter(filter)])
     if k < 0:
-        raise ValueError(_last_error())
+        raise ValueError(str(_error()))
     return k
 
 
@@ -102,7 +94,7 @@ def _table(in_size, out_size, filter):
     tab = np.zeros(out_size * (2 + k), np.int32)          # bounds[out][2], then coeffs[out][ksize]: the layout the kernels read
     if lib().srgd_resize_coeffs(in_size, out_size, FILTERS[filter], C.c_void_p(tab.ctypes.data),
                                 C.c_void_p(tab[2 * out_size:].ctypes.data)) != 0:
-        raise ValueError(_last_error())
+        raise ValueError(str(_error()))
     tab.setflags(write=False)
     return tab
 
@@ -185,7 +177,7 @@ def resize_flat(src, src_offsets, dst, dst_offsets, sizes, filter="bicubic"):
                                          C.c_void_p(tables.data_ptr()), 4 * tables.numel(), C.c_void_p(scratch.data_ptr()),
                                          scratch.numel(), C.c_void_p(torch.cuda.current_stream().cuda_stream))
     if rc != 0:
-        raise _lib.SrgdHipError(_last_error())
+        raise _error()
     return dst
 
 

@@ -46,20 +46,12 @@ def lib() -> C.CDLL:
     """Load the self-ensemble library (once).  Raises if it has not been built - no CPU fallback."""
     global _handle
     if _handle is None:
-        if not os.path.exists(LIB_PATH):
-            raise _lib.SrgdHipError(f"{LIB_PATH} is missing: build it with `python -m srgd_amd.build` (hipcc, gfx950). "
-                                    "The self-ensemble kernels run on the MI355X only; there is no CPU fallback.")
-        handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in PROTOTYPES.items():
-            fn = getattr(handle, name)
-            fn.restype = res
-            fn.argtypes = args
-        _handle = handle
+        _handle = _lib.load(LIB_PATH, PROTOTYPES, "The self-ensemble kernels run on the MI355X only")
     return _handle
 
 
-def _last_error():
-    return lib().srgd_selfens_last_error().decode(errors="replace")
+def _error():
+    return _lib.error_of(lib(), "srgd_selfens_last_error")
 
 
 def check_self_ensemble(n):
@@ -129,7 +121,7 @@ def transform_flat(src, src_offsets, dst, dst_offsets, sizes, ops):
         rc = lib().srgd_selfens_transform(C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()), recs, n,
                                           C.c_void_p(torch.cuda.current_stream().cuda_stream))
     if rc != 0:
-        raise _lib.SrgdHipError(_last_error())
+        raise _error()
     return dst
 
 
@@ -166,7 +158,7 @@ def merge_flat(src, src_offsets, ops, dst, dst_offsets, sizes, mean01=None, mean
                                       C.c_void_p(mean01.data_ptr()) if mean01 is not None else None, images, n,
                                       C.c_void_p(torch.cuda.current_stream().cuda_stream))
     if rc != 0:
-        raise _lib.SrgdHipError(_last_error())
+        raise _error()
     return dst
 
 

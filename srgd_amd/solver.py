@@ -38,15 +38,7 @@ def lib() -> C.CDLL:
     """Load the solver library (once).  Raises if it has not been built - no CPU fallback."""
     global _handle
     if _handle is None:
-        if not os.path.exists(LIB_PATH):
-            raise _lib.SrgdHipError(f"{LIB_PATH} is missing: build it with `python -m srgd_amd.build` (hipcc, gfx950). "
-                                    "The solver's history step runs on the MI355X only; there is no CPU fallback.")
-        handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in PROTOTYPES.items():
-            fn = getattr(handle, name)
-            fn.restype = res
-            fn.argtypes = args
-        _handle = handle
+        _handle = _lib.load(LIB_PATH, PROTOTYPES, "The solver's history step runs on the MI355X only")
     return _handle
 
 
@@ -134,4 +126,4 @@ def history_step_flat(img, x_start, x_prev, recs, w):
         rc = lib().srgd_solver_history_step(C.c_void_p(img.data_ptr()), C.c_void_p(x_start.data_ptr()), C.c_void_p(x_prev.data_ptr()),
                                             recs, len(recs), float(w), C.c_void_p(torch.cuda.current_stream().cuda_stream))
     if rc != 0:
-        raise _lib.SrgdHipError(lib().srgd_solver_last_error().decode(errors="replace"))
+        raise _lib.error_of(lib(), "srgd_solver_last_error")

@@ -43,20 +43,12 @@ def lib() -> C.CDLL:
     """Load the threshold library (once).  Raises if it has not been built - no CPU fallback."""
     global _handle
     if _handle is None:
-        if not os.path.exists(LIB_PATH):
-            raise _lib.SrgdHipError(f"{LIB_PATH} is missing: build it with `python -m srgd_amd.build` (hipcc, gfx950). "
-                                    "The dynamic threshold runs on the MI355X only; there is no CPU fallback.")
-        handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in PROTOTYPES.items():
-            fn = getattr(handle, name)
-            fn.restype = res
-            fn.argtypes = args
-        _handle = handle
+        _handle = _lib.load(LIB_PATH, PROTOTYPES, "The dynamic threshold runs on the MI355X only")
     return _handle
 
 
 def _error():
-    return _lib.SrgdHipError(lib().srgd_threshold_last_error().decode(errors="replace"))
+    return _lib.error_of(lib(), "srgd_threshold_last_error")
 
 
 def fp32(v) -> float:

@@ -7,7 +7,6 @@ import io
 import os
 import re
 import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -29,6 +28,7 @@ from srgd_amd import inference as INF  # noqa: E402
 from srgd_amd.inference import parse_args  # noqa: E402
 from tests import alpha_cases as AC  # noqa: E402
 from tests import resize_cases as RC  # noqa: E402
+from tests.lib_exports import exports as _exports  # noqa: E402
 from tools.kernel_resources import kernel_table  # noqa: E402
 
 ENTRIES = {"srgd_alpha_last_error", "srgd_alpha_resize_planes", "srgd_alpha_pack_rgba", "srgd_alpha_bleed"}
@@ -225,12 +225,6 @@ def test_argument_parsing(tmp_path):
 
 
 # ------------------------------------------------------------------------------------------- (e) C ABI, refusals, resources
-def _exports(path):
-    nm = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    exported = {ln.split()[-1] for ln in nm.splitlines() if len(ln.split()) >= 3 and ln.split()[-2] in "TtWw"}
-    return {n for n in exported if not n.startswith(("_init", "_fini", "__"))}
-
-
 def test_entries_are_declared_prototyped_and_exported_by_a_library_of_their_own():
     header = open(os.path.join(ROOT, "include", "srgd_alpha.h")).read()
     flat = re.sub(r"/\*.*?\*/", "", header, flags=re.S)

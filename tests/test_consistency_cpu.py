@@ -8,7 +8,6 @@ import json
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -23,6 +22,7 @@ from srgd_amd import inference as INF
 from srgd_amd import metrics as MX
 from tests import consistency_cases as K
 from tests import ensemble_cases as E
+from tests.lib_exports import exports as _exports
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CONF = os.path.join(ROOT, "conf", "conditional_continuous_linear_df8kost_dim128.yaml")
@@ -103,12 +103,6 @@ def test_the_five_vector_fact(n):
 
 
 # ------------------------------------------------------------------------------------------- C ABI, refusals, resources
-def _exports(path):
-    nm = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    exported = {ln.split()[-1] for ln in nm.splitlines() if len(ln.split()) >= 3 and ln.split()[-2] in "TtWw"}
-    return {n for n in exported if not n.startswith(("_init", "_fini", "__"))}
-
-
 def test_entries_are_declared_prototyped_and_exported_by_a_library_of_their_own():
     header = open(os.path.join(ROOT, "include", "srgd_consistency.h")).read()
     flat = re.sub(r"/\*.*?\*/", "", header, flags=re.S)

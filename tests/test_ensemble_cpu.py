@@ -7,7 +7,6 @@ import json
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -19,6 +18,7 @@ from srgd_amd import ensemble as EN
 from srgd_amd import inference as INF
 from srgd_amd import metrics as MX
 from tests import ensemble_cases as E
+from tests.lib_exports import exports as _exports
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CONF = os.path.join(ROOT, "conf", "conditional_continuous_linear_df8kost_dim128.yaml")
@@ -299,12 +299,6 @@ def test_host_side_checks_of_the_module():
     for fn in ("ensemble_flat", "ensemble_flat_device"):
         assert list(inspect.signature(getattr(EN, fn)).parameters) == ["samples", "sample_offsets", "sizes", "n_samples", "mean_u8", "std_u8",
                                                                         "out_offsets", "mean01", "mean01_offsets"]
-
-
-def _exports(path):
-    nm = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    exported = {ln.split()[-1] for ln in nm.splitlines() if len(ln.split()) >= 3 and ln.split()[-2] in "TtWw"}
-    return {n for n in exported if not n.startswith(("_init", "_fini", "__"))}
 
 
 def test_entries_are_declared_prototyped_and_exported_by_a_library_of_their_own():

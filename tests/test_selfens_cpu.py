@@ -8,7 +8,6 @@ import json
 import os
 import re
 import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -33,6 +32,7 @@ from srgd_amd import inference as INF  # noqa: E402
 from srgd_amd.inference import parse_args  # noqa: E402
 from srgd_amd.lockstep import even_step_tiles  # noqa: E402
 from tests import selfens_cases as SC  # noqa: E402
+from tests.lib_exports import exports as _exports  # noqa: E402
 from tools.kernel_resources import kernel_table  # noqa: E402
 
 ENTRIES = {"srgd_selfens_last_error", "srgd_selfens_transform", "srgd_selfens_merge"}
@@ -138,12 +138,6 @@ def test_argument_parsing_and_the_refusals(tmp_path, monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------- (c) C ABI, refusals, resources
-def _exports(path):
-    nm = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    exported = {ln.split()[-1] for ln in nm.splitlines() if len(ln.split()) >= 3 and ln.split()[-2] in "TtWw"}
-    return {n for n in exported if not n.startswith(("_init", "_fini", "__"))}
-
-
 def test_entries_are_declared_prototyped_and_exported_by_a_library_of_their_own():
     header = open(os.path.join(ROOT, "include", "srgd_selfens.h")).read()
     flat = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
@@ -178,7 +172,8 @@ def test_entries_are_declared_prototyped_and_exported_by_a_library_of_their_own(
                    "inverse(5) = 6", "3*h*w < 2^31"):
         assert phrase in re.sub(r"\s*\n \*\s*", " ", header), phrase
     from srgd_amd import build as B
-    assert B.SELFENS_SOURCES == ["selfens.hip"] and "selfens.hip" not in B.SOURCES and B.SELFENS_LIB == SE.LIB_PATH
+    row = {name: (lib, sources) for name, lib, sources, _ in B.LIBRARIES}["selfens"]
+    assert row[1] == ["selfens.hip"] and "selfens.hip" not in B.SOURCES and row[0] == SE.LIB_PATH
 
 
 def test_an_unbuilt_library_is_an_error_not_a_fallback(monkeypatch, tmp_path):

@@ -6,7 +6,6 @@ import ctypes as C
 import inspect
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -25,6 +24,7 @@ from srgd_amd import model as MODEL
 from srgd_amd import solver as SV
 from tests import guidance_cases as G
 from tests import solver_cases as SC
+from tests.lib_exports import exports as _exports
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CONF = os.path.join(ROOT, "conf", "conditional_continuous_linear_df8kost_dim128.yaml")
@@ -159,12 +159,6 @@ def test_the_restated_loop_as_ddpm_is_the_oracles_loop_within_fp32_rounding():
 
 
 # ------------------------------------------------------------------------------------------- (c) C ABI, refusals, resources
-def _exports(path):
-    nm = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    exported = {ln.split()[-1] for ln in nm.splitlines() if len(ln.split()) >= 3 and ln.split()[-2] in "TtWw"}
-    return {n for n in exported if not n.startswith(("_init", "_fini", "__"))}
-
-
 def test_entries_are_declared_prototyped_and_exported_by_a_library_of_their_own():
     header = open(os.path.join(ROOT, "include", "srgd_solver.h")).read()
     flat = re.sub(r"/\*.*?\*/", "", header, flags=re.S)

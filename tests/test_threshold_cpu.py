@@ -6,7 +6,6 @@ import ctypes as C
 import inspect
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -21,6 +20,7 @@ from srgd_amd import model as MODEL
 from srgd_amd import solver as SV
 from srgd_amd import threshold as TH
 from tests import threshold_cases as TC
+from tests.lib_exports import exports as _exports
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CONF = os.path.join(ROOT, "conf", "conditional_continuous_linear_df8kost_dim128.yaml")
@@ -102,12 +102,6 @@ def test_every_kernel_case_builds_and_sits_between_canaries():
 
 
 # ------------------------------------------------------------------------------------------- the library
-def _exports(path):
-    nm = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    exported = {ln.split()[-1] for ln in nm.splitlines() if len(ln.split()) >= 3 and ln.split()[-2] in "TtWw"}
-    return {n for n in exported if not n.startswith(("_init", "_fini", "__"))}
-
-
 def test_entries_are_declared_prototyped_and_exported_by_a_library_of_their_own():
     header = open(os.path.join(ROOT, "include", "srgd_threshold.h")).read()
     flat = re.sub(r"/\*.*?\*/", "", header, flags=re.S)

@@ -13,7 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from srgd_amd.build import CSRC, FLAGS, SOURCES, _hipcc  # noqa: E402
+from srgd_amd.build import CSRC, FLAGS, SOURCES, _hipcc, link  # noqa: E402
 
 
 def main():
@@ -33,13 +33,7 @@ def main():
             return obj
         with ThreadPoolExecutor(max_workers=6) as ex:
             objs = list(ex.map(one, SOURCES))
-        vers = os.path.join(tmp, "exports.map")
-        with open(vers, "w") as f:
-            f.write("{ global: srgd_*; local: *; };\n")
-        r = subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", f"-Wl,--version-script={vers}", "-o", lib, *objs],
-                           capture_output=True, text=True)
-        if r.returncode:
-            raise RuntimeError(r.stderr)
+        link(hipcc, lib, objs, "srgd_*", os.path.join(tmp, "exports.map"))
     print(lib)
 
 
