@@ -278,10 +278,20 @@ def strip_model_prefix(sd: Dict[str, Tensor]) -> Dict[str, Tensor]:
 
 # --------------------------------------------------------------------------------------
 # sampler
+#
+# Every sampler below takes ``unet=``: the callable that stands for the network, ``unet(sd, cfg, x, log_snr, class_label, cond)``,
+# ``unet_forward`` unless a test supplies a closed form.  The samplers compute in the dtype of ``condition_x``; the step scalars and
+# schedules stay the reference's fp32 VALUES in either dtype (they are what the kernels are handed), widened without change.
 # --------------------------------------------------------------------------------------
+def _f32(v: float) -> float:
+    """A Python scalar as the fp32 value an fp32 tensor op would use (no-op on an fp32 run, the same value on a float64 one)."""
+    return float(torch.tensor(v, dtype=torch.float32))
+
+
 class NoiseSource:
     """Draws noise in the reference's order from torch's global CPU generator,
-    and optionally records every draw so a device run can replay the identical stream."""
+    and optionally records every draw so a device run can replay the identical stream.  Draws are fp32, as the reference's;
+    the samplers convert them to the dtype of their condition (a float64 condition gives a float64 run on the same noise)."""
 
     def __init__(self, record: bool = False):
         self.record = record
@@ -290,7 +300,7 @@ class NoiseSource:
     def randn(self, shape) -> Tensor:
         z = torch.randn(tuple(shape))
         if self.record:
-            self.draws.append(z)
+            self.draws.append(z.clone())                                 # a copy: the samplers write into what they are handed
         return z
 
 
@@ -303,35 +313,42 @@ class ReplayNoise:
         z = self.draws[self.i]
         self.i += 1
         assert tuple(z.shape) == tuple(shape), (tuple(z.shape), tuple(shape))
-        return z
+        return z.clone()                                                 # a copy: the stored stream stays what was recorded
 
 
 def predict_and_step(sd, cfg: UnetCfg, x: Tensor, t: Tensor, t_next: Tensor, cond: Tensor,
                      class_label: Optional[Tensor], cond_scale: float, class_cond_scale: float,
-                     noise: "NoiseSource", trace: Optional[dict] = None):
-    """model.py:3122-3188 p_mean_variance + p_sample for one minibatch of tiles."""
+                     noise: "NoiseSource", trace: Optional[dict] = None, unet=None):
+    """model.py:3122-3188 p_mean_variance + p_sample for one minibatch of tiles.  ``trace``: gains the guided eps and, under
+    "tile_noise", the minibatch's noise draw (None on the last step) for the caller to place."""
+    unet = unet or unet_forward
     s = step_scalars(t, t_next)
     ls = s["log_snr"].expand(x.shape[0])
     if cond_scale != 1.0 and class_cond_scale != 1.0:
         raise NotImplementedError(
             "Currently, you cannot specify both cond_scale and class_cond_scale at the same time.")
     if cond_scale != 1.0:                                               # :3147-3150
-        a = unet_forward(sd, cfg, x, ls, class_label, cond)
-        b = unet_forward(sd, cfg, x, ls, class_label, None)
+        a = unet(sd, cfg, x, ls, class_label, cond)
+        b = unet(sd, cfg, x, ls, class_label, None)
         eps = b + (a - b) * cond_scale
     elif class_cond_scale != 1.0:                                       # :3151-3154
-        a = unet_forward(sd, cfg, x, ls, class_label, cond)
-        b = unet_forward(sd, cfg, x, ls, None, cond)
+        a = unet(sd, cfg, x, ls, class_label, cond)
+        b = unet(sd, cfg, x, ls, None, cond)
         eps = b + (a - b) * class_cond_scale
     else:                                                               # :3155-3156
-        eps = unet_forward(sd, cfg, x, ls, class_label, cond)
+        eps = unet(sd, cfg, x, ls, class_label, cond)
     x0 = ((x - s["sigma"] * eps) / s["alpha"]).clamp(-1.0, 1.0)          # :3160-3163
     mean = s["alpha_next"] * (x * (1 - s["c"]) / s["alpha"] + s["c"] * x0)   # :3164
     if trace is not None:
         trace.setdefault("eps", []).append(eps.clone())
     if t_next == 0:                                                     # :3184-3185
+        if trace is not None:
+            trace["tile_noise"] = None
         return mean, x0
-    return mean + s["var"].sqrt() * noise.randn(x.shape), x0            # :3187-3188
+    z = noise.randn(x.shape).to(x.dtype)
+    if trace is not None:
+        trace["tile_noise"] = z
+    return mean + s["var"].sqrt() * z, x0                               # :3187-3188
 
 
 def tiled_sample(sd, cfg: UnetCfg, condition_x: Tensor, class_label: Optional[Tensor] = None, *,
@@ -339,12 +356,17 @@ def tiled_sample(sd, cfg: UnetCfg, condition_x: Tensor, class_label: Optional[Te
                  guidance_start_steps: int = 0, class_cond_scale: float = 1.0,
                  class_guidance_start_steps: int = 0, tile: int = 256, generation_start_steps: int = 0,
                  start_white_noise: bool = True,
-                 noise: Optional["NoiseSource"] = None, trace: Optional[dict] = None) -> Tensor:
+                 noise: Optional["NoiseSource"] = None, trace: Optional[dict] = None, unet=None) -> Tensor:
     """model.py:3288-3413 tiled_sample.
 
     condition_x: [1,3,H,W] in [0,1].  Returns [1,3,H,W] in [0,1].
+
+    ``trace``: a dict that receives "start" (the start canvas), "cond" (the condition canvas the tiles read) and, per executed
+    step, "img" and "x_start" (the canvases after the step and its ring re-noise), "noise" (the step's tile noise scattered onto
+    the canvas; zeros on the last step), "ring" (the odd step's ring draw, else None) and "eps" per minibatch.
     """
     noise = noise or NoiseSource()
+    dt = condition_x.dtype
     cond = condition_x * 2 - 1                                           # :3296
     _, _, h, w = cond.shape
     (left, top, right, bottom), pad = canvas_box_and_pad(h, w)            # :3301 (tile fixed at 256)
@@ -353,18 +375,21 @@ def tiled_sample(sd, cfg: UnetCfg, condition_x: Tensor, class_label: Optional[Te
         t0 = (1.0 - torch.tensor(generation_start_steps / num_sample_steps)) if generation_start_steps > 0 \
             else torch.tensor(1.0)
         ls0 = log_snr_linear(t0)
-        img = cond * ls0.sigmoid().sqrt() + noise.randn(cond.shape) * (-ls0).sigmoid().sqrt()   # :3434-3442
+        img = cond * ls0.sigmoid().sqrt() + noise.randn(cond.shape).to(dt) * (-ls0).sigmoid().sqrt()   # :3434-3442
     else:
-        img = noise.randn(cond.shape)                                    # :3311
+        img = noise.randn(cond.shape).to(dt)                             # :3311
     steps = torch.linspace(1.0, 0.0, num_sample_steps + 1)               # :3325
     hp, wp = cond.shape[-2:]
     grids = sampling_grids(hp, wp, tile, tile)
     (il, it, ir, ib), ipad = grid_bbox(grids[1], hp, wp)                  # :3337
     cond = F.pad(cond[:, :, it:ib, il:ir], ipad, mode="constant", value=0.0)   # :3341-3342
     x_start = img.clone()
+    if trace is not None:
+        trace["start"], trace["cond"] = img.clone(), cond.clone()
     for i in range(num_sample_steps):
         if i < generation_start_steps:                                   # :3347-3348
             continue
+        placed = torch.zeros_like(img) if trace is not None else None
         cs = cond_scale if i >= guidance_start_steps else 1.0            # :3349-3356
         ccs = class_cond_scale if i >= class_guidance_start_steps else 1.0
         t, t_next = steps[i], steps[i + 1]
@@ -373,16 +398,23 @@ def tiled_sample(sd, cfg: UnetCfg, condition_x: Tensor, class_label: Optional[Te
             chunk = boxes[j:j + batch_size]
             xb = torch.cat([img[:, :, a:b, c:d] for (a, b, c, d) in chunk], dim=0)
             cb = torch.cat([cond[:, :, a:b, c:d] for (a, b, c, d) in chunk], dim=0)
-            out, x0 = predict_and_step(sd, cfg, xb, t, t_next, cb, class_label, cs, ccs, noise, trace)
+            out, x0 = predict_and_step(sd, cfg, xb, t, t_next, cb, class_label, cs, ccs, noise, trace, unet)
+            z = trace.pop("tile_noise") if trace is not None else None
             for k, (a, b, c, d) in enumerate(chunk):
                 img[:, :, a:b, c:d] = out[k]
                 x_start[:, :, a:b, c:d] = x0[k]
+                if z is not None:
+                    placed[:, :, a:b, c:d] = z[k]
+        ring = None
         if i % 2 == 1:                                                   # :3392-3396 ring re-noise
             inner = img[:, :, it:ib, il:ir].clone()
             sigma = (-log_snr_linear(t_next)).sigmoid().sqrt()
-            img = noise.randn(cond.shape) * sigma                         # q_sample(0, t') :3434-3442
+            ring = noise.randn(cond.shape).to(dt)
+            img = ring * sigma                                           # q_sample(0, t') :3434-3442
             img[:, :, it:ib, il:ir] = inner
         if trace is not None:
+            trace.setdefault("noise", []).append(placed)
+            trace.setdefault("ring", []).append(None if ring is None else ring.clone())
             trace.setdefault("img", []).append(img.clone())
             trace.setdefault("x_start", []).append(x_start.clone())
     out = img[:, :, top:bottom, left:right].clamp(-1.0, 1.0)             # :3403-3404
@@ -431,20 +463,21 @@ def edm_precond_coeffs(e: EdmCfg, sigma: Tensor) -> Dict[str, Tensor]:
 
 
 def edm_denoise(sd, cfg: UnetCfg, e: EdmCfg, x: Tensor, sigma: float, cond: Tensor, class_label: Optional[Tensor],
-                cond_scale: float, class_cond_scale: float, clamp: bool) -> Tensor:
+                cond_scale: float, class_cond_scale: float, clamp: bool, unet=None) -> Tensor:
     """preconditioned_network_forward, model.py:2132-2183."""
+    unet = unet or unet_forward
     s = torch.full((x.shape[0],), sigma)
     c = edm_precond_coeffs(e, s)
     pad = lambda v: v.reshape(-1, 1, 1, 1)
     if cond_scale != 1.0 and class_cond_scale != 1.0:
         raise NotImplementedError("Currently, you cannot specify both cond_scale and class_cond_scale at the same time.")
     xin = pad(c["c_in"]) * x
-    out = pad(c["c_skip"]) * x + pad(c["c_out"]) * unet_forward(sd, cfg, xin, c["c_noise"], class_label, cond)
+    out = pad(c["c_skip"]) * x + pad(c["c_out"]) * unet(sd, cfg, xin, c["c_noise"], class_label, cond)
     if cond_scale != 1.0:
-        null = pad(c["c_skip"]) * x + pad(c["c_out"]) * unet_forward(sd, cfg, xin, c["c_noise"], class_label, None)
+        null = pad(c["c_skip"]) * x + pad(c["c_out"]) * unet(sd, cfg, xin, c["c_noise"], class_label, None)
         out = null + (out - null) * cond_scale
     if class_cond_scale != 1.0:
-        null = pad(c["c_skip"]) * x + pad(c["c_out"]) * unet_forward(sd, cfg, xin, c["c_noise"], None, cond)
+        null = pad(c["c_skip"]) * x + pad(c["c_out"]) * unet(sd, cfg, xin, c["c_noise"], None, cond)
         out = null + (out - null) * class_cond_scale
     return out.clamp(-1.0, 1.0) if clamp else out
 
@@ -453,9 +486,14 @@ def edm_tiled_sample(sd, cfg: UnetCfg, e: EdmCfg, condition_x: Tensor, class_lab
                      batch_size: int = 4, num_sample_steps: int = 32, cond_scale: float = 1.0,
                      guidance_start_steps: int = 0, class_cond_scale: float = 1.0, class_guidance_start_steps: int = 0,
                      generation_start_steps: int = 0, clamp: bool = True, zero_init: bool = False, tile: int = 256,
-                     noise: Optional["NoiseSource"] = None) -> Tensor:
-    """model.py:2309-2475.  condition_x [1,3,H,W] in [0,1] -> [1,3,H,W] in [0,1]."""
+                     noise: Optional["NoiseSource"] = None, trace: Optional[dict] = None, unet=None) -> Tensor:
+    """model.py:2309-2475.  condition_x [1,3,H,W] in [0,1] -> [1,3,H,W] in [0,1].
+
+    ``trace``: a dict that receives "start", "cond" and, per executed step, "img" (the canvas after the step and its ring
+    re-noise), "x_start" (what the reference keeps as such, :2421-2424: the last slope, d' of a Heun pair or d of the Euler step),
+    "noise" (the step's unit draw on the canvas, before S_noise) and "ring" (the odd step's ring draw, else None)."""
     noise = noise or NoiseSource()
+    dt = condition_x.dtype
     n = num_sample_steps
     cond = condition_x * 2 - 1
     _, _, h, w = cond.shape
@@ -467,42 +505,56 @@ def edm_tiled_sample(sd, cfg: UnetCfg, e: EdmCfg, condition_x: Tensor, class_lab
     # get_noised_images is called WITHOUT num_sample_steps (:2342, :2457): its sigmas are the constructor's schedule
     noised_sigmas = edm_sigmas(e, e.num_sample_steps)
     if generation_start_steps > 0:                                       # get_noised_images(cond, step) :2185-2194
-        img = cond + noised_sigmas[generation_start_steps] * noise.randn(shape)
+        img = cond + noised_sigmas[generation_start_steps] * noise.randn(shape).to(dt)
     elif zero_init:
-        img = torch.zeros(shape)
+        img = torch.zeros(shape, dtype=dt)
     else:
-        img = sigmas[0] * noise.randn(shape)
+        img = sigmas[0] * noise.randn(shape).to(dt)
     hp, wp = shape[-2:]
     grids = sampling_grids(hp, wp, tile, tile)
     (il, it, ir, ib), ipad = grid_bbox(grids[1], hp, wp)
     cond = F.pad(cond[:, :, it:ib, il:ir], ipad, mode="constant", value=0.0)
+    x_start = img.clone()
+    if trace is not None:
+        trace["start"], trace["cond"] = img.clone(), cond.clone()
     for i in range(n):
         if i < generation_start_steps:
             continue
         cs = cond_scale if i >= guidance_start_steps else 1.0
         ccs = class_cond_scale if i >= class_guidance_start_steps else 1.0
         sigma, sigma_next, gamma = sigmas[i].item(), sigmas[i + 1].item(), gammas[i].item()
-        eps = e.S_noise * noise.randn(shape)                             # :2386
+        z = noise.randn(shape).to(dt)
+        eps = _f32(e.S_noise) * z                                        # :2386
         sigma_hat = sigma + gamma * sigma
-        img_hat = img + math.sqrt(sigma_hat ** 2 - sigma ** 2) * eps     # :2389
+        img_hat = img + _f32(math.sqrt(sigma_hat ** 2 - sigma ** 2)) * eps     # :2389
         boxes = grids[i % 2]
         for j in range(0, len(boxes), batch_size):
             chunk = boxes[j:j + batch_size]
             xb = torch.cat([img_hat[:, :, a:b, c:d] for (a, b, c, d) in chunk], dim=0)
             cb = torch.cat([cond[:, :, a:b, c:d] for (a, b, c, d) in chunk], dim=0)
-            out = edm_denoise(sd, cfg, e, xb, sigma_hat, cb, class_label, cs, ccs, clamp)
-            d = (xb - out) / sigma_hat                                   # :2406
-            nxt = xb + (sigma_next - sigma_hat) * d                      # :2407
+            out = edm_denoise(sd, cfg, e, xb, sigma_hat, cb, class_label, cs, ccs, clamp, unet)
+            d = (xb - out) / _f32(sigma_hat)                             # :2406
+            nxt = xb + _f32(sigma_next - sigma_hat) * d                  # :2407
+            slope = d
             if sigma_next != 0:                                          # :2409-2414 Heun correction
-                out2 = edm_denoise(sd, cfg, e, nxt, sigma_next, cb, class_label, cs, ccs, clamp)
+                out2 = edm_denoise(sd, cfg, e, nxt, sigma_next, cb, class_label, cs, ccs, clamp, unet)
                 d2 = (nxt - out2) / sigma_next
-                nxt = xb + 0.5 * (sigma_next - sigma_hat) * (d + d2)
+                nxt = xb + _f32(0.5 * (sigma_next - sigma_hat)) * (d + d2)
+                slope = d2
             for k, (a, b, c, d_) in enumerate(chunk):
                 img[:, :, a:b, c:d_] = nxt[k]
+                x_start[:, :, a:b, c:d_] = slope[k]
+        ring = None
         if i % 2 == 1:                                                   # :2448-2452
             inner = img[:, :, it:ib, il:ir].clone()
-            img = torch.zeros(shape) + noised_sigmas[i] * noise.randn(shape)    # get_noised_images(0, i)
+            ring = noise.randn(shape).to(dt)
+            img = torch.zeros(shape, dtype=dt) + noised_sigmas[i] * ring        # get_noised_images(0, i)
             img[:, :, it:ib, il:ir] = inner
+        if trace is not None:
+            trace.setdefault("img", []).append(img.clone())
+            trace.setdefault("x_start", []).append(x_start.clone())
+            trace.setdefault("noise", []).append(z.clone())
+            trace.setdefault("ring", []).append(None if ring is None else ring.clone())
     out = img[:, :, top:bottom, left:right].clamp(-1.0, 1.0)
     return (out + 1) * 0.5
 
@@ -513,23 +565,31 @@ def edm_tiled_sample(sd, cfg: UnetCfg, e: EdmCfg, condition_x: Tensor, class_lab
 def sample(sd, cfg: UnetCfg, condition_x: Tensor, class_label: Optional[Tensor] = None, *, num_sample_steps: int = 50,
            cond_scale: float = 1.0, guidance_start_steps: int = 0, class_cond_scale: float = 1.0,
            class_guidance_start_steps: int = 0, generation_start_steps: int = 0,
-           noise: Optional["NoiseSource"] = None) -> Tensor:
+           noise: Optional["NoiseSource"] = None, trace: Optional[dict] = None, unet=None) -> Tensor:
     """condition_x: [B,3,S,S] in [0,1] (S = image_size); every image of the batch has its own noise (one randn over the
-    whole batch tensor per draw).  Returns [B,3,S,S] in [0,1]."""
+    whole batch tensor per draw).  Returns [B,3,S,S] in [0,1].  ``trace``: "start" and, per executed step, "img", "x_start"
+    and "noise" (the step's draw; None on the last step)."""
     noise = noise or NoiseSource()
+    dt = condition_x.dtype
     cond = condition_x * 2 - 1                                           # :3424
     if generation_start_steps > 0:                                       # :3198-3201 q_sample(condition, t_start)
         ls0 = log_snr_linear(1.0 - torch.tensor(generation_start_steps / num_sample_steps))
-        img = cond * ls0.sigmoid().sqrt() + noise.randn(cond.shape) * (-ls0).sigmoid().sqrt()
+        img = cond * ls0.sigmoid().sqrt() + noise.randn(cond.shape).to(dt) * (-ls0).sigmoid().sqrt()
     else:
-        img = noise.randn(cond.shape)                                    # :3203
+        img = noise.randn(cond.shape).to(dt)                             # :3203
     steps = torch.linspace(1.0, 0.0, num_sample_steps + 1)
+    if trace is not None:
+        trace["start"] = img.clone()
     for i in range(num_sample_steps):
         if i < generation_start_steps:
             continue
         cs = cond_scale if i >= guidance_start_steps else 1.0
         ccs = class_cond_scale if i >= class_guidance_start_steps else 1.0
-        img, _ = predict_and_step(sd, cfg, img, steps[i], steps[i + 1], cond, class_label, cs, ccs, noise)
+        img, x0 = predict_and_step(sd, cfg, img, steps[i], steps[i + 1], cond, class_label, cs, ccs, noise, trace, unet)
+        if trace is not None:
+            trace.setdefault("img", []).append(img.clone())
+            trace.setdefault("x_start", []).append(x0.clone())
+            trace.setdefault("noise", []).append(trace.pop("tile_noise"))
     return (img.clamp(-1.0, 1.0) + 1) * 0.5                              # :3239-3240
 
 
@@ -539,53 +599,68 @@ def sample(sd, cfg: UnetCfg, condition_x: Tensor, class_label: Optional[Tensor] 
 # --------------------------------------------------------------------------------------
 def _edm_start(e: EdmCfg, cond: Tensor, sigmas: Tensor, generation_start_steps: int, zero_init: bool, noise) -> Tensor:
     if generation_start_steps > 0:                                       # get_noised_images, ctor schedule (:2186-2194)
-        return cond + edm_sigmas(e, e.num_sample_steps)[generation_start_steps] * noise.randn(cond.shape)
+        return cond + edm_sigmas(e, e.num_sample_steps)[generation_start_steps] * noise.randn(cond.shape).to(cond.dtype)
     if zero_init:
-        return torch.zeros(cond.shape)
-    return sigmas[0] * noise.randn(cond.shape)
+        return torch.zeros(cond.shape, dtype=cond.dtype)
+    return sigmas[0] * noise.randn(cond.shape).to(cond.dtype)
 
 
 def edm_sample(sd, cfg: UnetCfg, e: EdmCfg, condition_x: Tensor, class_label: Optional[Tensor] = None, *,
                num_sample_steps: int = 32, cond_scale: float = 1.0, guidance_start_steps: int = 0,
                class_cond_scale: float = 1.0, class_guidance_start_steps: int = 0, generation_start_steps: int = 0,
-               clamp: bool = True, zero_init: bool = False, noise: Optional["NoiseSource"] = None) -> Tensor:
-    """sample_org, model.py:2212-2306.  condition_x [B,3,h,w] in [0,1]; one randn over the batch tensor per draw."""
+               clamp: bool = True, zero_init: bool = False, noise: Optional["NoiseSource"] = None,
+               trace: Optional[dict] = None, unet=None) -> Tensor:
+    """sample_org, model.py:2212-2306.  condition_x [B,3,h,w] in [0,1]; one randn over the batch tensor per draw.
+    ``trace``: "start" and, per executed step, "img", "x_start" (the last slope, :2288-2291) and "noise" (the unit draw)."""
     noise = noise or NoiseSource()
     n = num_sample_steps
     cond = condition_x * 2 - 1                                           # :2223
     sigmas = edm_sigmas(e, n)
     gammas = edm_gammas(e, sigmas, n)
     img = _edm_start(e, cond, sigmas, generation_start_steps, zero_init, noise)
+    if trace is not None:
+        trace["start"] = img.clone()
     for i in range(n):
         if i < generation_start_steps:
             continue
         cs = cond_scale if i >= guidance_start_steps else 1.0
         ccs = class_cond_scale if i >= class_guidance_start_steps else 1.0
         sigma, sigma_next, gamma = sigmas[i].item(), sigmas[i + 1].item(), gammas[i].item()
-        eps = e.S_noise * noise.randn(cond.shape)                        # :2269
+        z = noise.randn(cond.shape).to(cond.dtype)
+        eps = _f32(e.S_noise) * z                                        # :2269
         sigma_hat = sigma + gamma * sigma
-        img_hat = img + math.sqrt(sigma_hat ** 2 - sigma ** 2) * eps     # :2272
-        out = edm_denoise(sd, cfg, e, img_hat, sigma_hat, cond, class_label, cs, ccs, clamp)
-        d = (img_hat - out) / sigma_hat                                  # :2276
-        nxt = img_hat + (sigma_next - sigma_hat) * d                     # :2278
+        img_hat = img + _f32(math.sqrt(sigma_hat ** 2 - sigma ** 2)) * eps     # :2272
+        out = edm_denoise(sd, cfg, e, img_hat, sigma_hat, cond, class_label, cs, ccs, clamp, unet)
+        d = (img_hat - out) / _f32(sigma_hat)                            # :2276
+        nxt = img_hat + _f32(sigma_next - sigma_hat) * d                 # :2278
+        slope = d
         if sigma_next != 0:                                              # :2282-2286
-            out2 = edm_denoise(sd, cfg, e, nxt, sigma_next, cond, class_label, cs, ccs, clamp)
+            out2 = edm_denoise(sd, cfg, e, nxt, sigma_next, cond, class_label, cs, ccs, clamp, unet)
             d2 = (nxt - out2) / sigma_next
-            nxt = img_hat + 0.5 * (sigma_next - sigma_hat) * (d + d2)
+            nxt = img_hat + _f32(0.5 * (sigma_next - sigma_hat)) * (d + d2)
+            slope = d2
         img = nxt
+        if trace is not None:
+            trace.setdefault("img", []).append(img.clone())
+            trace.setdefault("x_start", []).append(slope.clone())
+            trace.setdefault("noise", []).append(z.clone())
     return (img.clamp(-1.0, 1.0) + 1) * 0.5                              # :2298, :2306
 
 
 def edm_sample_dpmpp(sd, cfg: UnetCfg, e: EdmCfg, condition_x: Tensor, class_label: Optional[Tensor] = None, *,
                      num_sample_steps: int = 32, cond_scale: float = 1.0, guidance_start_steps: int = 0,
                      class_cond_scale: float = 1.0, class_guidance_start_steps: int = 0, generation_start_steps: int = 0,
-                     clamp: bool = True, zero_init: bool = False, noise: Optional["NoiseSource"] = None) -> Tensor:
-    """sample_using_dpmpp, model.py:2479-2557: one U-Net evaluation per step, a two-step multistep update in t = -log sigma."""
+                     clamp: bool = True, zero_init: bool = False, noise: Optional["NoiseSource"] = None,
+                     trace: Optional[dict] = None, unet=None) -> Tensor:
+    """sample_using_dpmpp, model.py:2479-2557: one U-Net evaluation per step, a two-step multistep update in t = -log sigma.
+    ``trace``: "start" and, per executed step, "img" and "x_start" (the extrapolated denoised image, :2547)."""
     noise = noise or NoiseSource()
     n = num_sample_steps
     cond = condition_x * 2 - 1                                           # :2494
     sigmas = edm_sigmas(e, n)
     img = _edm_start(e, cond, sigmas, generation_start_steps, zero_init, noise)
+    if trace is not None:
+        trace["start"] = img.clone()
     t_of = lambda s: s.log().neg()                                       # :2513-2514
     sigma_of = lambda t: t.neg().exp()
     old = None
@@ -594,7 +669,7 @@ def edm_sample_dpmpp(sd, cfg: UnetCfg, e: EdmCfg, condition_x: Tensor, class_lab
             continue
         cs = cond_scale if i >= guidance_start_steps else 1.0
         ccs = class_cond_scale if i >= class_guidance_start_steps else 1.0
-        den = edm_denoise(sd, cfg, e, img, sigmas[i].item(), cond, class_label, cs, ccs, clamp)   # :2528
+        den = edm_denoise(sd, cfg, e, img, sigmas[i].item(), cond, class_label, cs, ccs, clamp, unet)   # :2528
         t, t_next = t_of(sigmas[i]), t_of(sigmas[i + 1])
         h = t_next - t
         if old is None or sigmas[i + 1] == 0:                            # :2533
@@ -605,4 +680,7 @@ def edm_sample_dpmpp(sd, cfg: UnetCfg, e: EdmCfg, condition_x: Tensor, class_lab
             den_d = (1 - g) * den + g * old                              # :2539
         img = (sigma_of(t_next) / sigma_of(t)) * img - (-h).expm1() * den_d   # :2541
         old = den
+        if trace is not None:
+            trace.setdefault("img", []).append(img.clone())
+            trace.setdefault("x_start", []).append(den_d.clone())
     return (img.clamp(-1.0, 1.0) + 1) * 0.5                              # :2549, :2557
