@@ -16,10 +16,10 @@ import torch
 
 from . import _lib
 from . import resize as RZ
+from ._flat import ALIGN, check_flat, device_of, gather, layout, round16
 
 MAX_SIDE = 16384
 MAX_BLEED = 64
-ALIGN = 16                                                # offsets, and every image's part of a scratch, are multiples of it
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libsrgd_alpha.so")
 
 
@@ -81,45 +81,6 @@ def alpha_of(pil_image):
     return np.asarray(pil_image.convert("RGBA").getchannel("A"), dtype=np.uint8).copy()
 
 
-def _round(n):
-    return (n + ALIGN - 1) // ALIGN * ALIGN
-
-
-def _device_of(tensors, what):
-    dev = next((t.device for t in tensors if t.is_cuda), None)
-    if dev is None:
-        if not torch.cuda.is_available():
-            raise _lib.SrgdHipError(f"{what} runs on MI355X only (no CPU fallback)")
-        dev = torch.device("cuda", torch.cuda.current_device())
-    return dev
-
-
-def _gather(tensors, dev):
-    """The tensors, flattened, at 16-byte aligned offsets of one flat uint8 device buffer -> (buffer, offsets)."""
-    offsets, total = [], 0
-    for t in tensors:
-        offsets.append(total)
-        total += _round(t.numel())
-    buf = torch.empty(max(total, ALIGN), device=dev, dtype=torch.uint8)
-    for t, off in zip(tensors, offsets):
-        buf[off:off + t.numel()].copy_(t.reshape(-1), non_blocking=True)
-    return buf, offsets
-
-
-def _check_flat(what, buffers, n, *spans):
-    """``spans``: (buffer, offsets, [bytes of image i]) - contiguous flat uint8 device buffers on one device, n >= 1 offsets each,
-    multiples of 16, every image inside its buffer."""
-    if not all(t.is_cuda for t in buffers):
-        raise _lib.SrgdHipError(f"{what} runs on MI355X only (no CPU fallback)")
-    for t in buffers:
-        if t.dtype != torch.uint8 or not t.is_contiguous() or t.device != buffers[0].device or t.dim() != 1:
-            raise ValueError(f"{what}: flat contiguous uint8 buffers on one device")
-    for buf, offsets, sizes in spans:
-        if n < 1 or len(offsets) != n or min(offsets) < 0 or any(off % ALIGN for off in offsets) \
-                or max(off + size for off, size in zip(offsets, sizes)) > buf.numel():
-            raise ValueError(f"{what}: offsets / sizes do not fit the buffers")
-
-
 def _check_hw(what, sizes):
     for h, w in sizes:
         if not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
@@ -129,13 +90,13 @@ def _check_hw(what, sizes):
 def plane_scratch_bytes(sizes):
     """Bytes of the scratch ``srgd_alpha_resize_planes`` needs for ``[(h_in, w_in, h_out, w_out)]``: per plane the horizontal pass's
     ``h_in * w_out`` bytes, rounded up to a multiple of 16."""
-    return sum(_round(h_in * w_out) for (h_in, _, _, w_out) in sizes)
+    return sum(round16(h_in * w_out) for (h_in, _, _, w_out) in sizes)
 
 
 def bleed_scratch_bytes(sizes):
     """Bytes of the scratch ``srgd_alpha_bleed`` needs for ``[(h, w)]``: two state buffers of one dword per pixel, every image's
     part rounded up to a multiple of 16."""
-    return 2 * sum(_round(4 * h * w) for h, w in sizes)
+    return 2 * sum(round16(4 * h * w) for h, w in sizes)
 
 
 def resize_planes_flat(src, src_offsets, dst, dst_offsets, sizes, filter="bicubic"):
@@ -147,7 +108,7 @@ def resize_planes_flat(src, src_offsets, dst, dst_offsets, sizes, filter="bicubi
     sizes = [tuple(int(v) for v in size) for size in sizes]
     n = len(sizes)
     RZ.check_sizes(sizes)
-    _check_flat("alpha plane resize", (src, dst), n, (src, src_offsets, [s[0] * s[1] for s in sizes]),
+    check_flat("alpha plane resize", (src, dst), n, (src, src_offsets, [s[0] * s[1] for s in sizes]),
                 (dst, dst_offsets, [s[2] * s[3] for s in sizes]))
     host_tables, tab_offsets = RZ.build_tables(sizes, filter)
     tables = torch.from_numpy(np.concatenate([host_tables, np.zeros(4, np.int32)])).to(src.device)       # never empty
@@ -172,7 +133,7 @@ def pack_rgba_flat(rgb, rgb_offsets, alpha, alpha_offsets, rgba, rgba_offsets, s
     sizes = [(int(h), int(w)) for h, w in sizes]
     n = len(sizes)
     _check_hw("alpha pack", sizes)
-    _check_flat("alpha pack", (rgb, alpha, rgba), n, (rgb, rgb_offsets, [3 * h * w for h, w in sizes]),
+    check_flat("alpha pack", (rgb, alpha, rgba), n, (rgb, rgb_offsets, [3 * h * w for h, w in sizes]),
                 (alpha, alpha_offsets, [h * w for h, w in sizes]), (rgba, rgba_offsets, [4 * h * w for h, w in sizes]))
     images = (AlphaImage * n)(*[AlphaImage(co, ao, do, h, w) for co, ao, do, (h, w) in zip(rgb_offsets, alpha_offsets, rgba_offsets, sizes)])
     with torch.cuda.device(rgb.device):
@@ -191,7 +152,7 @@ def bleed_flat(rgba, rgba_offsets, rgb, rgb_offsets, sizes, passes):
     sizes = [(int(h), int(w)) for h, w in sizes]
     n = len(sizes)
     _check_hw("alpha bleed", sizes)
-    _check_flat("alpha bleed", (rgba, rgb), n, (rgba, rgba_offsets, [4 * h * w for h, w in sizes]),
+    check_flat("alpha bleed", (rgba, rgb), n, (rgba, rgba_offsets, [4 * h * w for h, w in sizes]),
                 (rgb, rgb_offsets, [3 * h * w for h, w in sizes]))
     scratch = torch.empty(max(bleed_scratch_bytes(sizes) if passes else 0, ALIGN), device=rgba.device, dtype=torch.uint8)
     images = (AlphaImage * n)(*[AlphaImage(do, 0, so, h, w) for so, do, (h, w) in zip(rgba_offsets, rgb_offsets, sizes)])
@@ -220,13 +181,10 @@ def bleed_on_device(rgba_list, passes):
     call.  ``ValueError``: shapes that are not ``[H,W,4]`` uint8, passes outside 0 .. 64."""
     passes = check_bleed(passes)
     _check_list("bleed_on_device", rgba_list, 4)
-    dev = _device_of(rgba_list, "the alpha bleed")
+    dev = device_of(rgba_list, "the alpha bleed")
     sizes = [(int(t.shape[0]), int(t.shape[1])) for t in rgba_list]
-    src, src_offsets = _gather(rgba_list, dev)
-    dst_offsets, total = [], 0
-    for h, w in sizes:
-        dst_offsets.append(total)
-        total += _round(3 * h * w)
+    src, src_offsets = gather(rgba_list, dev)
+    dst_offsets, total = layout([3 * h * w for h, w in sizes])
     dst = torch.empty(total, device=dev, dtype=torch.uint8)
     bleed_flat(src, src_offsets, dst, dst_offsets, sizes, passes)
     return [dst[off:off + 3 * h * w].view(h, w, 3) for off, (h, w) in zip(dst_offsets, sizes)]
@@ -243,12 +201,9 @@ def resize_planes_on_device(planes, sizes, filter="bicubic"):
         raise ValueError("resize_planes_on_device: one (h_out, w_out) per plane")
     geo = [(int(p.shape[0]), int(p.shape[1]), int(h), int(w)) for p, (h, w) in zip(planes, sizes)]
     RZ.check_sizes(geo)
-    dev = _device_of(planes, "the alpha plane resize")
-    src, src_offsets = _gather(planes, dev)
-    dst_offsets, total = [], 0
-    for (_, _, h, w) in geo:
-        dst_offsets.append(total)
-        total += _round(h * w)
+    dev = device_of(planes, "the alpha plane resize")
+    src, src_offsets = gather(planes, dev)
+    dst_offsets, total = layout([h * w for (_, _, h, w) in geo])
     dst = torch.empty(total, device=dev, dtype=torch.uint8)
     resize_planes_flat(src, src_offsets, dst, dst_offsets, geo, filter)
     return [dst[off:off + h * w].view(h, w) for off, (_, _, h, w) in zip(dst_offsets, geo)]
@@ -261,14 +216,11 @@ def pack_rgba_on_device(rgb_list, alpha_list):
     _check_list("pack_rgba_on_device", alpha_list, None)
     if len(rgb_list) != len(alpha_list) or any(tuple(c.shape[:2]) != tuple(a.shape) for c, a in zip(rgb_list, alpha_list)):
         raise ValueError("pack_rgba_on_device: one [H,W] plane per [H,W,3] image")
-    dev = _device_of(list(rgb_list) + list(alpha_list), "the alpha pack")
+    dev = device_of(list(rgb_list) + list(alpha_list), "the alpha pack")
     sizes = [(int(c.shape[0]), int(c.shape[1])) for c in rgb_list]
-    rgb, rgb_offsets = _gather(rgb_list, dev)
-    alpha, alpha_offsets = _gather(alpha_list, dev)
-    dst_offsets, total = [], 0
-    for h, w in sizes:
-        dst_offsets.append(total)
-        total += _round(4 * h * w)
+    rgb, rgb_offsets = gather(rgb_list, dev)
+    alpha, alpha_offsets = gather(alpha_list, dev)
+    dst_offsets, total = layout([4 * h * w for h, w in sizes])
     dst = torch.empty(total, device=dev, dtype=torch.uint8)
     pack_rgba_flat(rgb, rgb_offsets, alpha, alpha_offsets, dst, dst_offsets, sizes)
     return [dst[off:off + 4 * h * w].view(h, w, 4) for off, (h, w) in zip(dst_offsets, sizes)]

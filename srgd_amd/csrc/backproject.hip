@@ -42,10 +42,11 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/srgd_backproject.h"
-#include "ext_common.hpp"
+#include "pillow_x4.hpp"
 
 // This file is a library of its own (libsrgd_backproject.so, include/srgd_backproject.h): it shares no symbol with the engine or the other nine
-// extension libraries; ext_common.hpp is their common host plumbing.
+// extension libraries; ext_common.hpp is their common host plumbing, pillow_x4.hpp the selectors of the x4 vectors and the byte extractor it
+// has in common with consistency.hip and guidance.hip.
 namespace srgd {
 namespace {
 
@@ -91,12 +92,6 @@ __host__ __device__ inline unsigned long long bp_plane(int h, int w) { return ro
 __host__ __device__ inline unsigned long long bp_scratch(int h, int w) {
   return 2ull * bp_plane(h, w) + round_up(3ull * (unsigned)h * (unsigned)w, 256ull);
 }
-
-// the reduction's vector of output index i of n
-__device__ __forceinline__ int bp_down_vector(int i, int n) { return i == 0 ? 0 : (i == 1 ? 1 : (i == n - 2 ? 3 : (i == n - 1 ? 4 : 2))); }
-// the enlargement's vector of output index j of n4 = 4n (any vector for an index beyond the image: its result is never used)
-__device__ __forceinline__ int bp_up_vector(int j, int n4) { return j < 6 ? j : (j >= n4 - 6 ? min(15, 10 + j - (n4 - 6)) : 6 + ((j + 2) & 3)); }
-__device__ __forceinline__ int bp_byte(const unsigned* d, int k) { return (int)((d[k >> 2] >> (8 * (k & 3))) & 0xffu); }
 
 // q: the output as saved (mul 255, truncation), saturated outside [0,1]; NaN -> 0
 __device__ __forceinline__ unsigned bp_quant_out(float v) {
@@ -167,7 +162,7 @@ __global__ __launch_bounds__(BP_THREADS) void backproject_end_kernel(BpTable tab
       float v[4], r[4];
       bp_load4(src + (size_t)c * npix, 4u * q, vec_src, v);
 #pragma unroll
-      for (int k = 0; k < 4; ++k) r[k] = isfinite(v[k]) ? __fdiv_rn((float)bp_byte(d, 3 * k + c), 255.0f) : v[k];
+      for (int k = 0; k < 4; ++k) r[k] = isfinite(v[k]) ? __fdiv_rn((float)u8_of(d, 3 * k + c), 255.0f) : v[k];
       float* o = dst + (size_t)c * npix + 4u * q;
       if (vec_dst) {
         *reinterpret_cast<float4*>(o) = make_float4(r[0], r[1], r[2], r[3]);
@@ -220,7 +215,7 @@ __global__ __launch_bounds__(BP_THREADS) void backproject_reduce_kernel(BpTable 
   {
     const int x = tid & (BP_TW - 1);
     int kx[BP_RTAPS];
-    const int4* kv = reinterpret_cast<const int4*>(kk[bp_down_vector(tx0 + x, w)]);
+    const int4* kv = reinterpret_cast<const int4*>(kk[x4_down_vector(tx0 + x, w)]);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int4 c = kv[q];
@@ -235,7 +230,7 @@ __global__ __launch_bounds__(BP_THREADS) void backproject_reduce_kernel(BpTable 
 #pragma unroll
       for (int t = 0; t < BP_RTAPS; ++t) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) acc[c] += __mul24(kx[t], bp_byte(d, 2 + 3 * t + c));
+        for (int c = 0; c < 3; ++c) acc[c] += __mul24(kx[t], u8_of(d, 2 + 3 * t + c));
       }
       unsigned char* o = hbuf + r * BP_HSTRIDE + 3 * x;
 #pragma unroll
@@ -250,7 +245,7 @@ __global__ __launch_bounds__(BP_THREADS) void backproject_reduce_kernel(BpTable 
     const int yl = i / BP_HDWORDS, j = i - yl * BP_HDWORDS;
     const int gy = ty0 + yl;
     if (gy >= h) continue;
-    const int4* kv = reinterpret_cast<const int4*>(kk[bp_down_vector(gy, h)]);
+    const int4* kv = reinterpret_cast<const int4*>(kk[x4_down_vector(gy, h)]);
     int ky[BP_RTAPS];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -263,7 +258,7 @@ __global__ __launch_bounds__(BP_THREADS) void backproject_reduce_kernel(BpTable 
     for (int t = 0; t < BP_RTAPS; ++t) {
       const unsigned d = p[t * BP_HDWORDS];
 #pragma unroll
-      for (int b = 0; b < 4; ++b) acc[b] += __mul24(ky[t], bp_byte(&d, b));
+      for (int b = 0; b < 4; ++b) acc[b] += __mul24(ky[t], u8_of(&d, b));
     }
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
@@ -304,7 +299,7 @@ __global__ __launch_bounds__(BP_THREADS) void backproject_update_kernel(BpTable 
   //    tx0 + floor((x - 6) / 4) = patch pixel (x + 2) >> 2: the 4 dwords from that pixel's dword hold its 12 bytes.
   {
     const int x = tid & (BP_UW - 1);
-    const int4 kx4 = *reinterpret_cast<const int4*>(kk[bp_up_vector(4 * tx0 + x, 4 * w)]);
+    const int4 kx4 = *reinterpret_cast<const int4*>(kk[x4_up_vector(4 * tx0 + x, 4 * w)]);
     const int kx[BP_UTAPS] = {kx4.x, kx4.y, kx4.z, kx4.w};
     const int first = 3 * ((x + 2) >> 2), skip = first & 3;
     for (int r = tid / BP_UW; r < BP_DROWS; r += BP_THREADS / BP_UW) {
@@ -314,7 +309,7 @@ __global__ __launch_bounds__(BP_THREADS) void backproject_update_kernel(BpTable 
 #pragma unroll
       for (int t = 0; t < BP_UTAPS; ++t) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) acc[c] += __mul24(kx[t], bp_byte(d, skip + 3 * t + c));
+        for (int c = 0; c < 3; ++c) acc[c] += __mul24(kx[t], u8_of(d, skip + 3 * t + c));
       }
       unsigned char* o = ubuf + r * BP_USTRIDE + 3 * x;
 #pragma unroll
@@ -332,7 +327,7 @@ __global__ __launch_bounds__(BP_THREADS) void backproject_update_kernel(BpTable 
     const int y = i / BP_UDWORDS, j = i - y * BP_UDWORDS;
     const int gy = 4 * ty0 + y, gb = BP_USTRIDE * tile_x + 4 * j;
     if (gy >= 4 * h || gb >= row_bytes) continue;                    // 12 w is a multiple of 4: a dword never straddles a row's end
-    const int4 ky4 = *reinterpret_cast<const int4*>(kk[bp_up_vector(gy, 4 * h)]);
+    const int4 ky4 = *reinterpret_cast<const int4*>(kk[x4_up_vector(gy, 4 * h)]);
     const int ky[BP_UTAPS] = {ky4.x, ky4.y, ky4.z, ky4.w};
     int acc[4] = {1 << (PILLOW_PREC_BITS - 1), 1 << (PILLOW_PREC_BITS - 1), 1 << (PILLOW_PREC_BITS - 1), 1 << (PILLOW_PREC_BITS - 1)};
     const unsigned* p = reinterpret_cast<const unsigned*>(ubuf + ((y + 2) >> 2) * BP_USTRIDE) + j;
@@ -340,14 +335,14 @@ __global__ __launch_bounds__(BP_THREADS) void backproject_update_kernel(BpTable 
     for (int t = 0; t < BP_UTAPS; ++t) {
       const unsigned d = p[t * BP_UDWORDS];
 #pragma unroll
-      for (int b = 0; b < 4; ++b) acc[b] += __mul24(ky[t], bp_byte(&d, b));
+      for (int b = 0; b < 4; ++b) acc[b] += __mul24(ky[t], u8_of(&d, b));
     }
     const size_t g = (size_t)gy * (size_t)row_bytes + (size_t)gb;    // < 48 h w
     const unsigned ov = *reinterpret_cast<const unsigned*>(o_u8 + g), cv = *reinterpret_cast<const unsigned*>(c_u8 + g);
     unsigned res = 0u;
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
-      const int v = bp_byte(&ov, b) + bp_byte(&cv, b) - clip8(acc[b]);
+      const int v = u8_of(&ov, b) + u8_of(&cv, b) - clip8(acc[b]);
       res |= (unsigned)(v < 0 ? 0 : (v > 255 ? 255 : v)) << (8 * b);
     }
     *reinterpret_cast<unsigned*>(o_u8 + g) = res;

@@ -39,10 +39,11 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/srgd_consistency.h"
-#include "ext_common.hpp"
+#include "pillow_x4.hpp"
 
 // This file is a library of its own (libsrgd_consistency.so, include/srgd_consistency.h): it shares no symbol with the engine or the other nine
-// extension libraries; ext_common.hpp is their common host plumbing.
+// extension libraries; ext_common.hpp is their common host plumbing, pillow_x4.hpp the selectors of the x4 vectors and the byte extractor it
+// has in common with backproject.hip and guidance.hip.
 namespace srgd {
 namespace {
 
@@ -69,10 +70,6 @@ struct CsRecord { unsigned long long sse[3], max_abs; };
 
 __host__ __device__ inline unsigned cs_tiles_x(int w) { return (unsigned)((w + CS_TW - 1) / CS_TW); }
 __host__ __device__ inline unsigned cs_tiles_y(int h) { return (unsigned)((h + CS_TH - 1) / CS_TH); }
-
-// the coefficient vector of output index i of n
-__device__ __forceinline__ int cs_vector(int i, int n) { return i == 0 ? 0 : (i == 1 ? 1 : (i == n - 2 ? 3 : (i == n - 1 ? 4 : 2))); }
-__device__ __forceinline__ int cs_byte(const unsigned* d, int k) { return (int)((d[k >> 2] >> (8 * (k & 3))) & 0xffu); }
 
 __global__ __launch_bounds__(CS_THREADS) void consistency_tile_kernel(CsTable tab, CsCoeffs coeffs, const unsigned char* __restrict__ hr_u8,
                                                                       const unsigned char* __restrict__ lr_u8,
@@ -117,7 +114,7 @@ __global__ __launch_bounds__(CS_THREADS) void consistency_tile_kernel(CsTable ta
   {
     const int x = tid & (CS_TW - 1);
     int kx[CS_TAPS];
-    const int4* kv = reinterpret_cast<const int4*>(kk[cs_vector(tx0 + x, w)]);
+    const int4* kv = reinterpret_cast<const int4*>(kk[x4_down_vector(tx0 + x, w)]);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int4 c = kv[q];
@@ -132,7 +129,7 @@ __global__ __launch_bounds__(CS_THREADS) void consistency_tile_kernel(CsTable ta
 #pragma unroll
       for (int t = 0; t < CS_TAPS; ++t) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) acc[c] += __mul24(kx[t], cs_byte(d, 2 + 3 * t + c));
+        for (int c = 0; c < 3; ++c) acc[c] += __mul24(kx[t], u8_of(d, 2 + 3 * t + c));
       }
       unsigned char* o = hbuf + r * CS_HSTRIDE + 3 * x;
 #pragma unroll
@@ -149,7 +146,7 @@ __global__ __launch_bounds__(CS_THREADS) void consistency_tile_kernel(CsTable ta
     const int yl = i / CS_HDWORDS, j = i - yl * CS_HDWORDS;
     const int gy = ty0 + yl;
     if (gy >= h) continue;
-    const int4* kv = reinterpret_cast<const int4*>(kk[cs_vector(gy, h)]);
+    const int4* kv = reinterpret_cast<const int4*>(kk[x4_down_vector(gy, h)]);
     int ky[CS_TAPS];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -162,7 +159,7 @@ __global__ __launch_bounds__(CS_THREADS) void consistency_tile_kernel(CsTable ta
     for (int t = 0; t < CS_TAPS; ++t) {
       const unsigned d = p[t * CS_HDWORDS];
 #pragma unroll
-      for (int b = 0; b < 4; ++b) acc[b] += __mul24(ky[t], cs_byte(&d, b));
+      for (int b = 0; b < 4; ++b) acc[b] += __mul24(ky[t], u8_of(&d, b));
     }
 #pragma unroll
     for (int b = 0; b < 4; ++b) {

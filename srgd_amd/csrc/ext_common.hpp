@@ -2,7 +2,10 @@
 // threshold, selfens): the last-error string behind every srgd_<name>_last_error, the export attribute, byte ranges for the
 // overlap checks, and Pillow's 8-bit clip for the integer kernels.  Each of these libraries is ONE translation unit: the error
 // string has internal linkage, so a library of several files would hold several.  The engine's own plumbing is common.hpp, which is
-// deliberately not included here (its set_error is defined in engine.hip).
+// deliberately not included here (its set_error is defined in engine.hip).  What some of the libraries have in common beyond this
+// plumbing is headers as well, each included into the one translation unit of its users, so that no library shares a SYMBOL with
+// another: pillow_resample.hpp, the general two-pass 8-bit resize (kernel bodies and host driver) of resize.hip and alpha.hip, and
+// pillow_x4.hpp, the selectors of the x4 vectors and the byte extractor of consistency.hip, backproject.hip and guidance.hip.
 #pragma once
 
 #include <algorithm>

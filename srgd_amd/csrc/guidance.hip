@@ -33,10 +33,11 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/srgd_guidance.h"
-#include "ext_common.hpp"
+#include "pillow_x4.hpp"
 
 // This file is a library of its own (libsrgd_guidance.so, include/srgd_guidance.h): it shares no symbol with the engine or the other nine
-// extension libraries; ext_common.hpp is their common host plumbing.
+// extension libraries; ext_common.hpp is their common host plumbing, pillow_x4.hpp the selectors of the x4 vectors it has in common with
+// consistency.hip and backproject.hip.
 namespace srgd {
 namespace {
 
@@ -74,11 +75,6 @@ __host__ __device__ inline unsigned gd_tiles_x(int w) { return (unsigned)((w + G
 __host__ __device__ inline unsigned gd_tiles_y(int h) { return (unsigned)((h + GD_TH - 1) / GD_TH); }
 inline unsigned long long gd_scratch(long long h, long long w) { return round_up((unsigned long long)(12 * h * w), 256ull); }
 
-// the reduction's vector of output index i of n
-__device__ __forceinline__ int gd_down_vector(int i, int n) { return i == 0 ? 0 : (i == 1 ? 1 : (i == n - 2 ? 3 : (i == n - 1 ? 4 : 2))); }
-// the enlargement's vector of output index j of n4 = 4n (any vector for an index beyond the image: its result is never used)
-__device__ __forceinline__ int gd_up_vector(int j, int n4) { return j < 6 ? j : (j >= n4 - 6 ? min(15, 10 + j - (n4 - 6)) : 6 + ((j + 2) & 3)); }
-
 // D = x4 reduction of x_start inside the crop box, fp32.
 __global__ __launch_bounds__(GD_THREADS) void guidance_reduce_kernel(GdTable tab, GdDown coeffs, const float* __restrict__ x_start,
                                                                      float* __restrict__ scratch) {
@@ -109,7 +105,7 @@ __global__ __launch_bounds__(GD_THREADS) void guidance_reduce_kernel(GdTable tab
   {
     const int x = tid & (GD_TW - 1);
     float kx[GD_RTAPS];
-    const float* kv = kk[gd_down_vector(tx0 + x, w)];
+    const float* kv = kk[x4_down_vector(tx0 + x, w)];
 #pragma unroll
     for (int t = 0; t < GD_RTAPS; ++t) kx[t] = kv[t];
     for (int r = tid / GD_TW; r < GD_PROWS; r += GD_THREADS / GD_TW) {
@@ -128,7 +124,7 @@ __global__ __launch_bounds__(GD_THREADS) void guidance_reduce_kernel(GdTable tab
     const int yl = i / GD_TW, x = i - yl * GD_TW;
     const int gy = ty0 + yl, gx = tx0 + x;
     if (gy >= h || gx >= w) continue;
-    const float* ky = kk[gd_down_vector(gy, h)];
+    const float* ky = kk[x4_down_vector(gy, h)];
     const float* p = hbuf + 4 * yl * GD_TW + x;
     float acc = 0.0f;
 #pragma unroll
@@ -167,7 +163,7 @@ __global__ __launch_bounds__(GD_THREADS) void guidance_update_kernel(GdTable tab
   //    tx0 + floor((x - 6) / 4) = patch column (x + 2) >> 2.
   {
     const int x = tid & (GD_UW - 1);
-    const float* kv = kk[gd_up_vector(4 * tx0 + x, 4 * w)];
+    const float* kv = kk[x4_up_vector(4 * tx0 + x, 4 * w)];
     const float kx[GD_UTAPS] = {kv[0], kv[1], kv[2], kv[3]};
     for (int r = tid / GD_UW; r < GD_DROWS; r += GD_THREADS / GD_UW) {
       const float* p = dpatch + r * GD_DCOLS + ((x + 2) >> 2);
@@ -187,7 +183,7 @@ __global__ __launch_bounds__(GD_THREADS) void guidance_update_kernel(GdTable tab
     const int y = i / GD_UW, x = i - y * GD_UW;
     const int gy = 4 * ty0 + y, gx = 4 * tx0 + x;
     if (gy >= 4 * h || gx >= 4 * w) continue;
-    const float* ky = kk[gd_up_vector(gy, 4 * h)];
+    const float* ky = kk[x4_up_vector(gy, 4 * h)];
     const float* p = ubuf + ((y + 2) >> 2) * GD_UW + x;
     float u = 0.0f;
 #pragma unroll

@@ -20,7 +20,8 @@
 #include "ext_common.hpp"
 
 // This file is a library of its own (libsrgd_solver.so, include/srgd_solver.h): it shares no symbol with the engine or the other nine
-// extension libraries; ext_common.hpp is their common host plumbing.
+// extension libraries; ext_common.hpp is their common host plumbing (pillow_resample.hpp and pillow_x4.hpp, the code some of them have in
+// common, are headers too: no symbol is shared).
 namespace srgd {
 namespace {
 

@@ -14,7 +14,8 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _flat, _lib
+from ._flat import ALIGN, round16
 
 FILTERS = {"bicubic": 3, "bilinear": 2, "lanczos": 1}     # name -> the library's number (PIL.Image.Resampling's)
 MAX_SIDE = 16384
@@ -22,7 +23,6 @@ MAX_RATIO = 8
 MAX_TAPS = 49
 SCALE = 4                                                 # the network's factor: --outscale 4 is the output as it is
 OUTSCALE_MIN, OUTSCALE_MAX = 0.5, 32.0
-ALIGN = 16                                                # offsets, and every image's part of the scratch, are multiples of it
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libsrgd_resize.so")
 
 
@@ -106,14 +106,10 @@ def coeffs(in_size, out_size, filter="bicubic"):
     return tab[:2 * out_size].reshape(out_size, 2).copy(), tab[2 * out_size:].reshape(out_size, -1).copy()
 
 
-def _round(n):
-    return (n + ALIGN - 1) // ALIGN * ALIGN
-
-
 def scratch_bytes(sizes):
     """Bytes of the scratch the C entry needs for ``[(h_in, w_in, h_out, w_out)]`` (include/srgd_resize.h: per image the horizontal
     pass's ``3 * h_in * w_out`` bytes, rounded up to a multiple of 16)."""
-    return sum(_round(3 * h_in * w_out) for (h_in, _, _, w_out) in sizes)
+    return sum(round16(3 * h_in * w_out) for (h_in, _, _, w_out) in sizes)
 
 
 def check_sizes(sizes):
@@ -141,7 +137,7 @@ def build_tables(sizes, filter="bicubic"):
                 if a != b:
                     parts.append(_table(a, b, filter))
                     total += 4 * parts[-1].size
-            pad = _round(total) - total
+            pad = round16(total) - total
             if pad:
                 parts.append(np.zeros(pad // 4, np.int32))
                 total += pad
@@ -155,19 +151,13 @@ def resize_flat(src, src_offsets, dst, dst_offsets, sizes, filter="bicubic"):
     w_out)]``.  The tables are computed on the host and uploaded; the scratch is allocated here.  Returns ``dst``.  No
     synchronisation."""
     filter = check_filter(filter)
-    if not (src.is_cuda and dst.is_cuda):
-        raise _lib.SrgdHipError("the resize runs on MI355X only (no CPU fallback)")
-    for t in (src, dst):
-        if t.dtype != torch.uint8 or not t.is_contiguous() or t.device != src.device or t.dim() != 1:
-            raise ValueError("resize: flat contiguous uint8 buffers on one device")
+    # check_flat's two halves, apart: the buffers are refused before the sizes are, the spans after, and the first message says
+    # "the resize" where the others say "resize" - the order and the words the callers and the tests know
+    _flat.check_buffers("resize", (src, dst), subject="the resize")
     sizes = [tuple(int(v) for v in size) for size in sizes]
     n = len(sizes)
     check_sizes(sizes)
-    if n < 1 or len(src_offsets) != n or len(dst_offsets) != n or min(src_offsets) < 0 or min(dst_offsets) < 0 \
-            or any(off % ALIGN for off in list(src_offsets) + list(dst_offsets)) \
-            or max(off + 3 * s[0] * s[1] for off, s in zip(src_offsets, sizes)) > src.numel() \
-            or max(off + 3 * s[2] * s[3] for off, s in zip(dst_offsets, sizes)) > dst.numel():
-        raise ValueError("resize: offsets / sizes do not fit the buffers")
+    _flat.check_spans("resize", n, (src, src_offsets, [3 * s[0] * s[1] for s in sizes]), (dst, dst_offsets, [3 * s[2] * s[3] for s in sizes]))
     host_tables, tab_offsets = build_tables(sizes, filter)
     tables = torch.from_numpy(np.concatenate([host_tables, np.zeros(4, np.int32)])).to(src.device)       # never empty
     scratch = torch.empty(max(scratch_bytes(sizes), ALIGN), device=src.device, dtype=torch.uint8)
@@ -194,20 +184,8 @@ def resize_on_device(images, sizes, filter="bicubic"):
             raise ValueError("resize_on_device: images are uint8 [H,W,3] tensors")
     geo = [(int(im.shape[0]), int(im.shape[1]), int(h), int(w)) for im, (h, w) in zip(images, sizes)]
     check_sizes(geo)
-    dev = next((im.device for im in images if im.is_cuda), None)
-    if dev is None:
-        if not torch.cuda.is_available():
-            raise _lib.SrgdHipError("the resize runs on MI355X only (no CPU fallback)")
-        dev = torch.device("cuda", torch.cuda.current_device())
-    src_offsets, dst_offsets, s_total, d_total = [], [], 0, 0
-    for (h_in, w_in, h_out, w_out) in geo:
-        src_offsets.append(s_total)
-        dst_offsets.append(d_total)
-        s_total += _round(3 * h_in * w_in)
-        d_total += _round(3 * h_out * w_out)
-    src = torch.empty(s_total, device=dev, dtype=torch.uint8)
-    for im, off in zip(images, src_offsets):
-        src[off:off + im.numel()].copy_(im.reshape(-1), non_blocking=True)
-    dst = torch.empty(d_total, device=dev, dtype=torch.uint8)
+    src, src_offsets = _flat.gather(images, _flat.device_of(images, "the resize"))
+    dst_offsets, total = _flat.layout([3 * h * w for (_, _, h, w) in geo])
+    dst = torch.empty(total, device=src.device, dtype=torch.uint8)
     resize_flat(src, src_offsets, dst, dst_offsets, geo, filter)
     return [dst[off:off + 3 * h * w].view(h, w, 3) for off, (_, _, h, w) in zip(dst_offsets, geo)]

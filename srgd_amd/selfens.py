@@ -11,8 +11,8 @@ import os
 import torch
 
 from . import _lib
+from ._flat import check_flat, gather, layout
 
-ALIGN = 16                                                # offsets are multiples of it
 MAX_SOURCES = 8                                           # SRGD_SELFENS_MAX_SOURCES
 MAX_IMAGES = 32                                           # SRGD_SELFENS_MAX_IMAGES: images of one launch
 TILE = 32                                                 # SRGD_SELFENS_TILE
@@ -80,28 +80,10 @@ def out_size(h, w, op):
     return (w, h) if check_op(op) & 4 else (h, w)
 
 
-def _round(n):
-    return (n + ALIGN - 1) // ALIGN * ALIGN
-
-
 def _check_hw(what, sizes):
     for h, w in sizes:
         if h < 1 or w < 1 or 3 * h * w >= 2 ** 31:
             raise ValueError(f"{what}: {h}x{w} is outside what the kernels take (sizes >= 1, 3*h*w < 2^31)")
-
-
-def _check_flat(what, buffers, n, *spans):
-    """``spans``: (buffer, offsets, [bytes of image i]) - contiguous flat uint8 device buffers on one device, n >= 1 offsets each,
-    multiples of 16, every image inside its buffer."""
-    if not all(t.is_cuda for t in buffers):
-        raise _lib.SrgdHipError(f"{what} runs on MI355X only (no CPU fallback)")
-    for t in buffers:
-        if t.dtype != torch.uint8 or not t.is_contiguous() or t.device != buffers[0].device or t.dim() != 1:
-            raise ValueError(f"{what}: flat contiguous uint8 buffers on one device")
-    for buf, offsets, sizes in spans:
-        if n < 1 or len(offsets) != len(sizes) or min(offsets) < 0 or any(off % ALIGN for off in offsets) \
-                or max(off + size for off, size in zip(offsets, sizes)) > buf.numel():
-            raise ValueError(f"{what}: offsets / sizes do not fit the buffers")
 
 
 def transform_flat(src, src_offsets, dst, dst_offsets, sizes, ops):
@@ -115,7 +97,7 @@ def transform_flat(src, src_offsets, dst, dst_offsets, sizes, ops):
         raise ValueError("self-ensemble transform: one op, one source offset and one destination offset per image")
     _check_hw("self-ensemble transform", sizes)
     nbytes = [3 * h * w for h, w in sizes]
-    _check_flat("the self-ensemble transform", (src, dst), n, (src, src_offsets, nbytes), (dst, dst_offsets, nbytes))
+    check_flat("the self-ensemble transform", (src, dst), n, (src, src_offsets, nbytes), (dst, dst_offsets, nbytes))
     recs = (SelfensRecord * n)(*[SelfensRecord(so, do, h, w, op, 0) for so, do, (h, w), op in zip(src_offsets, dst_offsets, sizes, ops)])
     with torch.cuda.device(src.device):
         rc = lib().srgd_selfens_transform(C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()), recs, n,
@@ -141,7 +123,7 @@ def merge_flat(src, src_offsets, ops, dst, dst_offsets, sizes, mean01=None, mean
         raise ValueError(f"self-ensemble merge: 1 .. {MAX_SOURCES} sources per image, one op per source")
     _check_hw("self-ensemble merge", sizes)
     nbytes = [3 * h * w for h, w in sizes]
-    _check_flat("the self-ensemble merge", (src, dst), n, (src, [o for s in src_offsets for o in s], [b for s, b in zip(src_offsets, nbytes) for _ in s]),
+    check_flat("the self-ensemble merge", (src, dst), n, (src, [o for s in src_offsets for o in s], [b for s, b in zip(src_offsets, nbytes) for _ in s]),
                 (dst, dst_offsets, nbytes))
     if mean01 is not None:
         if not mean01.is_cuda or mean01.dtype != torch.float32 or not mean01.is_contiguous() or mean01.device != src.device \
@@ -169,18 +151,6 @@ def _check_images(what, tensors):
     _check_hw(what, [(int(t.shape[0]), int(t.shape[1])) for t in tensors])
 
 
-def _gather(tensors, dev):
-    """The tensors, flattened, at 16-byte aligned offsets of one flat uint8 device buffer -> (buffer, offsets)."""
-    offsets, total = [], 0
-    for t in tensors:
-        offsets.append(total)
-        total += _round(t.numel())
-    buf = torch.empty(max(total, ALIGN), device=dev, dtype=torch.uint8)
-    for t, off in zip(tensors, offsets):
-        buf[off:off + t.numel()].copy_(t.reshape(-1), non_blocking=True)
-    return buf, offsets
-
-
 def _one_gpu(what, tensors):
     dev = tensors[0].device
     if not all(t.is_cuda and t.device == dev for t in tensors):
@@ -200,13 +170,10 @@ def dihedral_on_device(images, ops):
     unique = {}
     for t in images:
         unique.setdefault(id(t), t)
-    src, offs = _gather(list(unique.values()), dev)
+    src, offs = gather(list(unique.values()), dev)
     where = dict(zip(unique, offs))
     sizes = [(int(t.shape[0]), int(t.shape[1])) for t in images]
-    dst_offsets, total = [], 0
-    for h, w in sizes:
-        dst_offsets.append(total)
-        total += _round(3 * h * w)
+    dst_offsets, total = layout([3 * h * w for h, w in sizes])
     dst = torch.empty(total, device=dev, dtype=torch.uint8)
     transform_flat(src, [where[id(t)] for t in images], dst, dst_offsets, sizes, ops)
     return [dst[off:off + 3 * h * w].view(*out_size(h, w, op), 3) for off, (h, w), op in zip(dst_offsets, sizes, ops)]
@@ -231,16 +198,15 @@ def self_ensemble_on_device(groups, return_mean01=False):
         sizes.append(turned.pop())
     tensors = [t for g in groups for t, _ in g]
     dev = _one_gpu("the self-ensemble merge", tensors)
-    src, flat_offs = _gather(tensors, dev)
+    src, flat_offs = gather(tensors, dev)
     src_offsets, at = [], 0
     for g in groups:
         src_offsets.append(flat_offs[at:at + len(g)])
         at += len(g)
-    dst_offsets, m_offsets, total, m_total = [], [], 0, 0
+    dst_offsets, total = layout([3 * h * w for h, w in sizes])
+    m_offsets, m_total = [], 0
     for h, w in sizes:
-        dst_offsets.append(total)
         m_offsets.append(m_total)
-        total += _round(3 * h * w)
         m_total += 3 * h * w
     dst = torch.empty(total, device=dev, dtype=torch.uint8)
     m01 = torch.empty(m_total, device=dev, dtype=torch.float32) if return_mean01 else None

@@ -223,6 +223,25 @@ def test_the_list_apis_move_images_to_the_gpu_and_return_device_tensors():
             bad()
 
 
+# both tilings' edges (32- and 64-pixel horizontal tiles, 16-row tiles), the dword and the byte paths, the 49-tap table, one-pass forms
+PLANE_IS_CHANNEL_GEOMETRIES = [((5, 7), (3, 2)), ((17, 70), (33, 131)), ((16, 64), (64, 256)), ((40, 52), (20, 26)), ((64, 264), (8, 33)),
+                               ((9, 12), (9, 24)), ((12, 9), (24, 9))]
+
+
+@pytest.mark.parametrize("filter", list(RC.FILTERS))
+def test_a_plane_is_a_channel_of_the_rgb_resize(filter):
+    # the two libraries instantiate one template (pillow_resample.hpp): <3 channels, 32 pixels, 2 rows> and <1, 64, 4>
+    g = torch.Generator().manual_seed(20)
+    images = [torch.randint(0, 256, (h, w, 3), dtype=torch.uint8, generator=g) for (h, w), _ in PLANE_IS_CHANNEL_GEOMETRIES]
+    sizes = [out for _, out in PLANE_IS_CHANNEL_GEOMETRIES]
+    rgb = RZ.resize_on_device(images, sizes, filter)
+    planes = AL.resize_planes_on_device([im[:, :, c].contiguous() for im in images for c in range(3)], [s for s in sizes for _ in range(3)], filter)
+    for i, (geometry, out) in enumerate(zip(PLANE_IS_CHANNEL_GEOMETRIES, rgb)):
+        assert tuple(out.shape) == geometry[1] + (3,)
+        for c in range(3):
+            assert torch.equal(planes[3 * i + c], out[:, :, c]), (geometry, filter, c)
+
+
 # ------------------------------------------------------------------------------------------- (b) the refusals, with real buffers
 def test_every_error_returns_minus_one_with_a_message_and_writes_nothing():
     # invalid arguments only: every one is refused on the host before anything is launched
