@@ -150,6 +150,44 @@ int srgd_k_conv1x1_split_rms(const void* x, int Cin, int B, int N, const float* 
                              const float* pre_norm_g_host, const float* post_norm_g_host, const void* residual, void* out,
                              void* stream);
 
+/* ---- read-only probes of the conditioning path and of gn_finalize (tests/test_cond_exact_gpu.py); the engine calls none of them.
+ * Host code only: each makes the launches the engine makes, on the caller's buffers.  All return -1 with a message on a null argument.
+ *
+ * The two launchers of cond.hip.  Device pointers, fp32; synchronise.
+ *   time_features: feat[r] = [x, sin(2 pi x w[0..half)), cos(2 pi x w[0..half))] for x = log_snr[r]; feat rows are 2 * half + 1 wide.
+ *   linear_rows:   y[r][o] = act_out(sum_i W[o][i] * act_in(x[r][i]) + b[o]) + add[r * add_stride + o] for r < rows, o < out_f;
+ *                  x rows x_stride apart, y rows y_stride apart; act 0: none, 1: erf-GELU on the output, 2: SiLU on the input;
+ *                  b and add nullable; add_stride 0: one row of `add` for every r. */
+int srgd_k_time_features(const float* log_snr, const float* w, int half, int rows, float* feat, void* stream);
+int srgd_k_linear_rows(const float* x, int x_stride, const float* W, const float* b, float* y, int y_stride, int rows, int in_f,
+                       int out_f, int act, const float* add, int add_stride, void* stream);
+/* The conditioning table of n log-SNR values and K >= 1 labels, computed by the engine's own routine on a table of this call's own
+ * (no table of the engine is touched, no record added to its profile): row i * (K + 1) + k carries the class embedding of class_ids_host[k], row i * (K + 1) + K
+ * none (K = 1 with class_ids_host[0] < 0: no label, both rows alike).  table_host: [(K + 1) * n][ss_stride] fp32 on the HOST.
+ * `engine` is a finalized srgd_engine.  Synchronises. */
+int srgd_k_conditioning_table(void* engine, const float* log_snr_host, int n, const int32_t* class_ids_host, int K,
+                              float* table_host, void* stream);
+/* The columns of that table: *ss_stride = its row width, *n_blocks = the number of ResnetBlocks (both nullable); for 0 <= index <
+ * n_blocks, in the order the engine registered them: the block's state-dict prefix (name, nullable), the column of its scale vector
+ * (*ss_offset; its shift vector follows at *ss_offset + *Cout) and its width.  index < 0: only the two totals. */
+int srgd_k_conditioning_layout(void* engine, int* ss_stride, int* n_blocks, int index, char* name, size_t name_cap, int* ss_offset,
+                               int* Cout);
+/* gn_finalize alone: coefA / coefB [B][C] (device) from partial [B][groups][nslots][2], gamma, beta [C] and - if ss_table is given -
+ * the (scale | shift) vectors at column ss_offset of row ss_rows[b] + *step_ptr * step_mul of a table with rows ss_stride wide
+ * (ss_rows: device [B]; step_ptr: device int, nullable).  No tensor is passed: the statistics are the accumulators' alone.
+ * eps = 1e-5.  Synchronises. */
+int srgd_k_gn_coefficients(const float* partial, int nslots, int B, int hw, int C, int groups, const float* gamma, const float* beta,
+                           const float* ss_table, int ss_stride, int ss_offset, const int* ss_rows, const int* step_ptr,
+                           int step_mul, float* coefA, float* coefB, void* stream);
+
+/* The conditioning rows of one U-Net batch of a sampler step, as the step's own launch (launch_step_rows) writes them: `engine` has
+ * a begun run (srgd_sampler_begin / _begin_images / srgd_edm_begin, with or without srgd_sampler_image_labels).  The batch is tiles
+ * [first, first + nt) of the even (parity 0) or odd grid in one (nb == nt) or two (nb == 2 nt) passes; ev = evaluation of the step
+ * (EDM: 0 at sigma_hat, 1 at sigma_next); pass1_null: the second pass takes the null row.  rows_host: nb ints on the HOST, each
+ * (K + 1) * ev + (label slot | K); the step's share (K + 1) * evals * step is added on the device and is not part of them.  The launch
+ * writes to a buffer of this call's own: nothing of the run changes.  Synchronises. */
+int srgd_k_step_rows(void* engine, int parity, int nb, int nt, int first, int ev, int pass1_null, int32_t* rows_host, void* stream);
+
 /* Counter-based Gaussian noise (Philox4x32-10 + Box-Muller) for n_streams noise streams in ONE launch: the batched counterpart of
  * srgd_randn (srgd_hip.h).  Stream k writes counts_host[k] floats at dst + offsets_host[k] from seeds_host[k], with its counter
  * starting at 0: bit for bit what srgd_randn writes for (counts_host[k], seeds_host[k], stream_id).  Offsets and counts need not be

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/srgd_hip.h"
+#include "../../include/srgd_hip_kernels.h"
 #include "kernels.hpp"
 
 namespace srgd {
@@ -1682,6 +1683,50 @@ int srgd_unet_forward_labels(srgd_engine* e, const float* xin, const float* cond
   return unet_forward_with_rows(e, xin, cond, eps_out, B, H, W, st);
 }
 
+// Probes of the conditioning path (srgd_hip_kernels.h): compute_conditioning on a table of the call's own, and the table's columns
+int srgd_k_conditioning_table(void* engine, const float* log_snr_host, int n, const int32_t* class_ids_host, int K,
+                              float* table_host, void* stream) {
+  srgd_engine* e = (srgd_engine*)engine;
+  if (!e || !log_snr_host || !class_ids_host || !table_host) SRGD_FAIL("srgd_k_conditioning_table: null argument");
+  if (!e->finalized) SRGD_FAIL("srgd_k_conditioning_table: engine has no weights");
+  if (n < 1 || K < 1) SRGD_FAIL("srgd_k_conditioning_table: empty table");
+  if (class_ids_host[0] >= 0 && e->cfg.num_classes <= 0) SRGD_FAIL("class label given but the U-Net has no class embedding");
+  hipStream_t st = (hipStream_t)stream;
+  SRGD_HIP(hipSetDevice(e->cfg.device));
+  std::vector<int> ids(class_ids_host, class_ids_host + K);
+  CondTable ct;
+  const bool prof_on = e->prof_on;           // a probe leaves no record in the engine's profile
+  e->prof_on = false;
+  int rc = compute_conditioning(e, ct, log_snr_host, n, ids.data(), K, st);
+  e->prof_on = prof_on;
+  if (rc == 0 && hipMemcpyAsync(table_host, ct.table, (size_t)(K + 1) * n * e->ss_stride * 4, hipMemcpyDeviceToHost, st) != hipSuccess) rc = -2;
+  if (hipStreamSynchronize(st) != hipSuccess && rc == 0) rc = -2;
+  for (float* q : {ct.table, ct.ls, ct.feat, ct.h1, ct.t1, ct.trows, ct.c1, ct.c2})
+    if (q) hipFree(q);
+  if (rc == -2) SRGD_FAIL("srgd_k_conditioning_table: copying the table back failed");
+  return rc;
+}
+
+int srgd_k_conditioning_layout(void* engine, int* ss_stride, int* n_blocks, int index, char* name, size_t name_cap, int* ss_offset,
+                               int* Cout) {
+  const srgd_engine* e = (const srgd_engine*)engine;
+  if (!e) SRGD_FAIL("srgd_k_conditioning_layout: null argument");
+  if (ss_stride) *ss_stride = e->ss_stride;
+  if (n_blocks) *n_blocks = (int)e->all_rb.size();
+  if (index < 0) return 0;
+  if (index >= (int)e->all_rb.size()) SRGD_FAIL("srgd_k_conditioning_layout: bad index");
+  const ResW* r = e->all_rb[index];
+  if (name && name_cap) {
+    const std::string& w = e->wt[r->mlp.wi].name;            // "<block>.mlp.1.weight"
+    const std::string block = w.substr(0, w.size() - std::strlen(".mlp.1.weight"));
+    std::strncpy(name, block.c_str(), name_cap - 1);
+    name[name_cap - 1] = 0;
+  }
+  if (ss_offset) *ss_offset = r->ss_offset;
+  if (Cout) *Cout = r->Cout;
+  return 0;
+}
+
 // one image of a run as the begin entries receive it: its geometry, its two tile grids (host [n][2] = (y, x)) and its noise class
 struct ImageIn { srgd_sampler_image g; const int32_t* tiles_even; const int32_t* tiles_odd; };
 
@@ -1865,6 +1910,30 @@ int srgd_sampler_image_labels(srgd_engine* e, const int32_t* class_ids_host, int
   e->run_labels = true;
   e->run_class = labels[0];
   SRGD_HIP(hipStreamSynchronize(st));
+  return 0;
+}
+
+// Probe of launch_step_rows (srgd_hip_kernels.h): the launch a sampler step makes for one U-Net batch, into a buffer of the call's own
+int srgd_k_step_rows(void* engine, int parity, int nb, int nt, int first, int ev, int pass1_null, int32_t* rows_host, void* stream) {
+  srgd_engine* e = (srgd_engine*)engine;
+  if (!e || !rows_host) SRGD_FAIL("srgd_k_step_rows: null argument");
+  if (!e->run_active) SRGD_FAIL("srgd_k_step_rows: call srgd_sampler_begin, srgd_sampler_begin_images or srgd_edm_begin first");
+  const int par = parity & 1;
+  if (nt < 1 || (nb != nt && nb != 2 * nt) || first < 0 || first + nt > e->n_grid[par] || ev < 0 || ev > 1)
+    SRGD_FAIL("srgd_k_step_rows: the batch is one or two passes of tiles [first, first + nt) of the parity's grid, ev is 0 or 1");
+  hipStream_t st = (hipStream_t)stream;
+  SRGD_HIP(hipSetDevice(e->cfg.device));
+  int* tmp = nullptr;
+  SRGD_HIP(hipMalloc((void**)&tmp, (size_t)nb * sizeof(int)));
+  int* const run_rows = e->d_rows;           // the run keeps its own buffer and its contents
+  e->d_rows = tmp;
+  launch_step_rows(e, nb, nt, par ? e->d_tiles_odd : e->d_tiles_even, first, ev, pass1_null != 0, st);
+  e->d_rows = run_rows;
+  hipError_t err = hipGetLastError();
+  if (err == hipSuccess) err = hipMemcpyAsync(rows_host, tmp, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, st);
+  if (err == hipSuccess) err = hipStreamSynchronize(st);
+  (void)hipFree(tmp);
+  SRGD_HIP(err);
   return 0;
 }
 

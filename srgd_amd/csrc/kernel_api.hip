@@ -253,6 +253,43 @@ int srgd_k_groupnorm_silu_twin(const void* x, void* y, const void* residual, con
                              stream);
 }
 
+int srgd_k_time_features(const float* log_snr, const float* w, int half, int rows, float* feat, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!log_snr || !w || !feat) SRGD_FAIL("srgd_k_time_features: null argument");
+  if (half < 1 || rows < 1) SRGD_FAIL("srgd_k_time_features: empty input");
+  SRGD_TRY(time_features(log_snr, w, half, rows, feat, st));
+  SRGD_HIP(hipStreamSynchronize(st));
+  return 0;
+}
+
+int srgd_k_linear_rows(const float* x, int x_stride, const float* W, const float* b, float* y, int y_stride, int rows, int in_f,
+                       int out_f, int act, const float* add, int add_stride, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!x || !W || !y) SRGD_FAIL("srgd_k_linear_rows: null argument");
+  if (rows < 1 || rows > 65535 || in_f < 1 || out_f < 1 || x_stride < in_f || y_stride < out_f || (add_stride != 0 && add_stride < out_f))
+    SRGD_FAIL("srgd_k_linear_rows: bad shape");
+  if (act != ACT_NONE && act != ACT_GELU && act != ACT_SILU_IN) SRGD_FAIL("srgd_k_linear_rows: act is 0, 1 or 2");
+  SRGD_TRY(linear_rows(x, x_stride, W, b, y, y_stride, rows, in_f, out_f, act, add, add_stride, st));
+  SRGD_HIP(hipStreamSynchronize(st));
+  return 0;
+}
+
+int srgd_k_gn_coefficients(const float* partial, int nslots, int B, int hw, int C, int groups, const float* gamma, const float* beta,
+                           const float* ss_table, int ss_stride, int ss_offset, const int* ss_rows, const int* step_ptr,
+                           int step_mul, float* coefA, float* coefB, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!partial || !gamma || !beta || !coefA || !coefB || (ss_table && !ss_rows)) SRGD_FAIL("srgd_k_gn_coefficients: null argument");
+  if (nslots < 1 || B < 1 || hw < 1 || C < 1 || groups < 1 || C % groups != 0) SRGD_FAIL("srgd_k_gn_coefficients: bad shape");
+  if (ss_table && (ss_offset < 0 || ss_stride < ss_offset + 2 * C)) SRGD_FAIL("srgd_k_gn_coefficients: the table row does not hold scale | shift");
+  GnFinalizeArgs f;
+  f.partial = partial; f.nslots = nslots; f.B = B; f.C = C; f.groups = groups; f.hw = hw;
+  f.gamma = gamma; f.beta = beta; f.ss_table = ss_table; f.ss_rows = ss_rows; f.step_ptr = step_ptr;
+  f.step_mul = step_mul; f.ss_stride = ss_stride; f.ss_offset = ss_offset; f.eps = 1e-5f; f.coefA = coefA; f.coefB = coefB;
+  SRGD_TRY(gn_finalize(f, st));
+  SRGD_HIP(hipStreamSynchronize(st));
+  return 0;
+}
+
 int srgd_k_rmsnorm(const void* x, void* y, const void* residual, const float* g, int64_t npix, int C, int is_bf16,
                    void* stream) {
   return rms_norm(x, y, residual, g, (long)npix, C, is_bf16 != 0, (hipStream_t)stream);

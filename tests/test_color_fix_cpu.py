@@ -139,7 +139,7 @@ def test_entries_are_declared_prototyped_and_exported():
     nm = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
     exported = {ln.split()[-1] for ln in nm.splitlines() if ln.strip()}
     assert set(names) <= exported
-    assert len([n for n in exported if n.startswith("srgd_")]) == len(_lib.PROTOTYPES) == 52
+    assert len([n for n in exported if n.startswith("srgd_")]) == len(_lib.PROTOTYPES) == 58
 
 
 def test_color_fix_kernels_do_not_spill():
