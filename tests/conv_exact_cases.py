@@ -11,6 +11,7 @@ product and every partial sum is an exact integer below 2^24, so the result depe
 tile shape: the kernel must equal the float64 convolution bit for bit (after `.to(bfloat16)` in bf16 mode).  Integers |v| <= 3 are
 exact in bf16, in f16 (the `lo` halves of the split are zero, the power-of-two weight scale is exact) and in e4m3 under any
 power-of-two block scale, so this holds in every reduced-precision kernel as well.
+(The lo halves of the split, its cross products and the weight scale on non-integers: tests/split_exact_cases.py.)
 
 The non-linear epilogues: the device SiLU is x / (1 + expf(-x)) or x * rcp(1 + __expf(-x)); for x >= 32, 1 + exp(-x) rounds to
 exactly 1 in fp32, so SiLU is the identity on integers >= 32.  The reference below therefore APPLIES NO SiLU: the data make every
