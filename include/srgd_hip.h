@@ -60,11 +60,24 @@ typedef struct srgd_engine srgd_engine;
                                  * bar 1e-3).  The blocks at the tile's own resolution (final block, last up stage, first down stage) keep
                                  * the three-MFMA arithmetic - that is where the error is made: within 1.4-1.8x of SRGD_PRECISION_F16X3
                                  * on every reference fixture, +7 % throughput.  Everything else as SRGD_PRECISION_F16X3. */
+#define SRGD_PRECISION_F16X1 7 /* THROUGHPUT mode between SRGD_PRECISION_BF16 and _F16X3: everything as SRGD_PRECISION_F16X3 (fp32 tensors, norms,
+                                * attention, sampler; pointwise layers and leftovers on their three-term kernels), except that every 3x3 /
+                                * stride-1 / pad-1 convolution the halo kernel covers (conv3x3_split.hip: Cin % 32 == 0, Cout % 128 == 0, 8 x 32
+                                * pixel patches) contracts the hi halves alone,
+                                *     y = conv(hi(x), hi(w s)) / s + bias,   hi(v) = round-to-nearest-even f16 of the saturated v,
+                                * with the layer's power-of-two weight scale s and fp32 accumulation: ONE v_mfma_f32_16x16x32_f16 per fragment
+                                * pair, 11 significand bits per operand against bf16's 8.  hi(x), hi(w s) are bit for bit _F16X3's hi halves
+                                * and the weights are its packing (the lo tiles are not read).  A 3x3 layer the halo kernel does not cover
+                                * keeps three terms.  It does NOT meet the 1e-3 parity bar.  Priced on the CPU against the reference's
+                                * fixtures, random-init weights (profiles/f16x1_numerics.jsonl): max-abs 3.81e-3, 77.46 dB on dim128_config1;
+                                * max-abs 7.5e-2, 64.37 dB on dim128_config2_1024_2steps - about 21 dB above SRGD_PRECISION_BF16.  Quality on
+                                * trained weights is unmeasured (the checkpoint in the tree is an LFS pointer).  Headline configuration, one session
+                                * (profiles/f16x1_bench.txt): 0.697 HR tiles/s against _F16X3's 0.423, _F16MX2's 0.450 and _BF16's 1.365. */
 
 /* Non-finite values, in EVERY precision above: a NaN or an infinity that enters a kernel reaches every output that the same
  * operation of the reference would make non-finite, and no other output changes.  In particular the sampler's clamps keep a NaN
  * (torch.clamp's rule), the RMSNorms' max(norm, 1e-12) keeps a NaN norm, and the f16 (hi, lo) split of SRGD_PRECISION_F16X3 /
- * _F16MX2 turns a NaN or an infinite activation into NaN; only a FINITE activation beyond f16's range (|x| > 65504) saturates
+ * _F16MX2 / _F16X1 turns a NaN or an infinite activation into NaN; only a FINITE activation beyond f16's range (|x| > 65504) saturates
  * there.  MX-fp8 operands: a NaN becomes the e4m3 NaN byte, an infinity saturates to +-448 like any out-of-range value. */
 
 /* Constructor arguments of ConditionalSRUnet (model.py:537-556) as get_model passes them

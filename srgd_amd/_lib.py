@@ -18,6 +18,7 @@ PRECISION_BF16_W8 = 2    # bf16 kernels, conv weights rounded through fp8 e4m3 (
 PRECISION_FP8 = 3        # 3x3 convolutions on the block-scaled MX-fp8 matrix cores (e4m3 + E8M0 per 32 channels), rest bf16
 PRECISION_F16X3 = 5      # fp32 tensors, convolutions as three f16 MFMAs per product on (hi, lo) operand pairs: <= 1e-3 parity like fp32
 PRECISION_F16MX2 = 6     # prototype: F16X3 with the 3x3 convolutions' cross terms on MX-fp8 operands (conv3x3_mx2.hip)
+PRECISION_F16X1 = 7      # throughput mode: F16X3 with the halo-kernel 3x3 convolutions on the hi halves alone (one f16 MFMA per product); not a parity mode
 PRECISION_FP8_MIXED = 4  # the same below the top resolution; the 256x256-resolution zones keep bf16 3x3 convolutions
 
 

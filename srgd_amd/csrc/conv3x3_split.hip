@@ -42,6 +42,7 @@ constexpr int A_BUF = 2 * A_IMG;               // hi | lo
 constexpr int B_TILE = BN3 * KC * 2;           // 8 KiB: one 16-bit weight tile
 constexpr int B_SLOT = 2 * B_TILE;             // hi | lo
 constexpr int LDS_BYTES = 2 * A_BUF + 3 * B_SLOT;   // 147,456: one workgroup per CU
+constexpr int LDS1_BYTES = 2 * A_IMG + 3 * B_TILE;  // 73,728: the one-term instances (hi images alone)
 
 struct Split3Args {
   const float* in0; const float* in1; int C0, C1;
@@ -68,6 +69,26 @@ struct Split3Args {
     mma(C0_, bh0, ah); mma(C1_, bh1, ah); mma(C2_, bh2, ah); mma(C3_, bh3, ah);                \
   }
 
+// The one-term instances' K-row: x_hi * w_hi alone, four MFMAs.
+#define HI_K_ROW(A, I, C0_, C1_, C2_, C3_)                                                     \
+  {                                                                                            \
+    const frag ah = *reinterpret_cast<const frag*>((A) + a_addr(tap, I));                      \
+    mma(C0_, bh0, ah); mma(C1_, bh1, ah); mma(C2_, bh2, ah); mma(C3_, bh3, ah);                \
+  }
+
+// 8 fp32 (two 16-byte vectors) -> their 8 f16 hi halves, bit for bit the hi fragment of split8<true> (split_hi_f16: a finite value
+// beyond f16's range saturates, a NaN or an infinity leaves as NaN); no lo halves are computed.
+__device__ __forceinline__ void hi8(const u32x4& r0, const u32x4& r1, u32x4& hi) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const unsigned ua = k < 2 ? r0[2 * k] : r1[2 * k - 4], ub = k < 2 ? r0[2 * k + 1] : r1[2 * k - 3];   // (copied out first: conv_common.hpp)
+    float a = __uint_as_float(ua), b = __uint_as_float(ub);
+    f32x2 hf;
+    const unsigned h = split_hi_f16(a, b, hf);
+    hi[k] = h;
+  }
+}
+
 // The lane's sixteen bias values (both kernels below): channels chw + chl .. + 15 (16-byte aligned: launcher), zero without a bias.
 __device__ __forceinline__ void split_load_bias(const float* bias, int chw, int chl, f32x4& bs0, f32x4& bs1, f32x4& bs2, f32x4& bs3) {
   bs0 = bs1 = bs2 = bs3 = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -85,8 +106,24 @@ __device__ __forceinline__ void split_load_bias(const float* bias, int chw, int 
 // to the fp32 halo pieces in registers, ahead of the split - the separate gn_apply pass over that tensor (4 B read + 4 B written per
 // element) disappears.  Out-of-image halo pixels stay zero (the convolution pads the ACTIVATED tensor).  v_exp_f32 / v_rcp_f32
 // (1 ulp each) instead of gn_apply's expf and IEEE division: ~3e-7 relative, far inside the mode's 2^-22 per product.
-template <bool STATS, bool F16, bool GNIN>
-__global__ __launch_bounds__(NT3, 2) void conv3x3_split_kernel(Split3Args p) {
+//
+// TERMS == 1 (f16 halves only; the engine's f16x1 mode): y = conv(hi(x), hi(w s)) / s + bias - ONE MFMA per fragment pair.  Same tile
+// decode, staging, swizzled images, ring and epilogue; what exists for the lo halves is compiled out: the lo halo image (an A buffer
+// is one 24 KB image), the lo weight tile's DMA (the hi tile of pack_conv3x3_split's unit is copied, the lo tile behind it in HBM is
+// skipped; a ring slot is 8 KB), the lo fragment reads and eight of the twelve MFMAs of a K-row.  LDS 2 x 24 + 3 x 8 = 72 KB.
+// Two workgroups would fit a CU's LDS but need 128 VGPRs per wave; the instances take 176 (198 with GNIN: 64 accumulators, 24 staging
+// registers, 16 coefficients, 32 operand fragments, one operand address per tap and block) and a build held to 128 spills 64 .. 123 of
+// them (compiled only, never timed: profiles/f16x1_bench.txt), so the kernel keeps the three-term kernel's bounds: one workgroup per CU, two waves per SIMD.
+// (-DSRGD_SPLIT1_WAVES=4 compiles that build, for the resource table only - tools/time_f16x1.py prints it; the launcher stays as it is.)
+#ifndef SRGD_SPLIT1_WAVES
+#define SRGD_SPLIT1_WAVES 2
+#endif
+template <bool STATS, bool F16, bool GNIN, int TERMS = 3>
+__global__ __launch_bounds__(NT3, TERMS == 1 ? SRGD_SPLIT1_WAVES : 2) void conv3x3_split_kernel(Split3Args p) {
+  static_assert(TERMS == 3 || (TERMS == 1 && F16), "one term: f16 halves");
+  constexpr bool ONE = TERMS == 1;
+  constexpr int ABUF = ONE ? A_IMG : A_BUF;       // one A buffer in LDS
+  constexpr int BSLOT = ONE ? B_TILE : B_SLOT;    // one ring slot in LDS (in HBM a unit is B_SLOT bytes for both)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -128,7 +165,7 @@ __global__ __launch_bounds__(NT3, 2) void conv3x3_split_kernel(Split3Args p) {
       __builtin_amdgcn_make_buffer_rsrc((void*)w_base, 0, (int)((size_t)(9 * CC - 1) * w_tile_stride + B_SLOT), 0x00020000);
 
   char* const sA0 = smem;
-  char* const sB0 = smem + 2 * A_BUF;
+  char* const sB0 = smem + 2 * ABUF;
 
   // fp32 halo pieces of the NEXT chunk in flight (24 registers)
   u32x4 ra00, ra01, ra10, ra11, ra20, ra21;
@@ -162,22 +199,29 @@ __global__ __launch_bounds__(NT3, 2) void conv3x3_split_kernel(Split3Args p) {
     if constexpr (GNIN) {
       if ((j == 0 ? a_pix0 : (j == 1 ? a_pix1 : a_pix2)) >= 0) { act4(r0, ga0, gb0); act4(r1, ga1, gb1); }
     }
-    u32x4 hi, lo;
-    split8<F16>(r0, r1, hi, lo);
-    char* dst = sA0 + (cc & 1) * A_BUF + (tid + NT3 * j) * 16;
-    *reinterpret_cast<u32x4*>(dst) = hi;
-    *reinterpret_cast<u32x4*>(dst + A_IMG) = lo;
+    if constexpr (ONE) {
+      u32x4 hi;
+      hi8(r0, r1, hi);
+      *reinterpret_cast<u32x4*>(sA0 + (cc & 1) * ABUF + (tid + NT3 * j) * 16) = hi;
+    } else {
+      u32x4 hi, lo;
+      split8<F16>(r0, r1, hi, lo);
+      char* dst = sA0 + (cc & 1) * A_BUF + (tid + NT3 * j) * 16;
+      *reinterpret_cast<u32x4*>(dst) = hi;
+      *reinterpret_cast<u32x4*>(dst + A_IMG) = lo;
+    }
   };
   // K-step (cc, tap) -> weight unit (tap, cc) into ring slot tap % 3 (9 % 3 == 0); every wave copies 1 KiB of the hi tile and
-  // 1 KiB of the lo tile.  `tap` is a compile-time constant (0..10: 9 and 10 are taps 0 and 1 of the next chunk).
+  // 1 KiB of the lo tile (one term: the hi tile alone - ONE request per K-step).  `tap` is a compile-time constant (0..10: 9 and 10
+  // are taps 0 and 1 of the next chunk).
   const int w_tap_stride = (int)(CC * w_tile_stride);
   const int tid16 = tid * 16;
   auto issue_b = [&](int cc, int tap) {
     if (tap >= 9) { tap -= 9; cc += 1; }
-    char* dst = sB0 + (tap % 3) * B_SLOT + wave * 1024;
+    char* dst = sB0 + (tap % 3) * BSLOT + wave * 1024;
     const int so = tap * w_tap_stride + cc * (int)w_tile_stride;
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lds_ptr)dst, 16, tid16, so, 0, 0);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lds_ptr)(dst + B_TILE), 16, tid16, so + B_TILE, 0, 0);
+    if constexpr (!ONE) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lds_ptr)(dst + B_TILE), 16, tid16, so + B_TILE, 0, 0);
   };
 
   f32x4 c00 = 0, c01 = 0, c02 = 0, c03 = 0, c10 = 0, c11 = 0, c12 = 0, c13 = 0,
@@ -197,16 +241,23 @@ __global__ __launch_bounds__(NT3, 2) void conv3x3_split_kernel(Split3Args p) {
     else c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wt), __builtin_bit_cast(bf16x8, px), c, 0, 0, 0);
   };
   auto compute = [&](int cc, int tap) {
-    const char* A = sA0 + (cc & 1) * A_BUF;
-    const char* Bt = sB0 + (tap % 3) * B_SLOT;
+    const char* A = sA0 + (cc & 1) * ABUF;
+    const char* Bt = sB0 + (tap % 3) * BSLOT;
     const frag bh0 = *reinterpret_cast<const frag*>(Bt + b_base), bh1 = *reinterpret_cast<const frag*>(Bt + b_base + 1024),
                bh2 = *reinterpret_cast<const frag*>(Bt + b_base + 2048), bh3 = *reinterpret_cast<const frag*>(Bt + b_base + 3072);
-    const frag bl0 = *reinterpret_cast<const frag*>(Bt + B_TILE + b_base), bl1 = *reinterpret_cast<const frag*>(Bt + B_TILE + b_base + 1024),
-               bl2 = *reinterpret_cast<const frag*>(Bt + B_TILE + b_base + 2048), bl3 = *reinterpret_cast<const frag*>(Bt + B_TILE + b_base + 3072);
-    SPLIT_K_ROW(A, A_IMG, 0, c00, c01, c02, c03)
-    SPLIT_K_ROW(A, A_IMG, 1, c10, c11, c12, c13)
-    SPLIT_K_ROW(A, A_IMG, 2, c20, c21, c22, c23)
-    SPLIT_K_ROW(A, A_IMG, 3, c30, c31, c32, c33)
+    if constexpr (ONE) {
+      HI_K_ROW(A, 0, c00, c01, c02, c03)
+      HI_K_ROW(A, 1, c10, c11, c12, c13)
+      HI_K_ROW(A, 2, c20, c21, c22, c23)
+      HI_K_ROW(A, 3, c30, c31, c32, c33)
+    } else {
+      const frag bl0 = *reinterpret_cast<const frag*>(Bt + B_TILE + b_base), bl1 = *reinterpret_cast<const frag*>(Bt + B_TILE + b_base + 1024),
+                 bl2 = *reinterpret_cast<const frag*>(Bt + B_TILE + b_base + 2048), bl3 = *reinterpret_cast<const frag*>(Bt + B_TILE + b_base + 3072);
+      SPLIT_K_ROW(A, A_IMG, 0, c00, c01, c02, c03)
+      SPLIT_K_ROW(A, A_IMG, 1, c10, c11, c12, c13)
+      SPLIT_K_ROW(A, A_IMG, 2, c20, c21, c22, c23)
+      SPLIT_K_ROW(A, A_IMG, 3, c30, c31, c32, c33)
+    }
   };
 
   // ---- prologue: A(0) through registers, B[0], B[1]
@@ -216,7 +267,7 @@ __global__ __launch_bounds__(NT3, 2) void conv3x3_split_kernel(Split3Args p) {
   store_piece(0, 0, ra00, ra01);
   store_piece(0, 1, ra10, ra11);
   store_piece(0, 2, ra20, ra21);
-  WAIT_VM(2);                                    // B[0] landed (B[1]'s two copies may still fly)
+  if constexpr (ONE) WAIT_VM(1); else WAIT_VM(2);  // B[0] landed (B[1]'s two copies - one term: its one copy - may still fly)
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   BARRIER();
 
@@ -226,6 +277,10 @@ __global__ __launch_bounds__(NT3, 2) void conv3x3_split_kernel(Split3Args p) {
   // vmcnt bookkeeping (loads retire in order): at the end of tap t the requests younger than B[s+1] are
   //   tap 0: B[s+2] (2) + A (6) = 8;   tap 1: A (6) + B[s+2] (2) = 8;   taps 2..8: B[s+2] (2)   (tap 2's wait retires the A loads);
   //   GNIN: the chunk's four coefficient loads ride with the A loads (12 instead of 8).
+  // One term: B[s+2] is ONE request (the hi tile), so
+  //   tap 0: B[s+2] (1) + A (6) = 7;   tap 1: A (6) + B[s+2] (1) = 7;   taps 2..8: B[s+2] (1);   GNIN: 11 instead of 7;
+  //   prologue: B[1] (1) behind B[0] (the A loads, younger, were drained by the stores that consumed them);
+  //   last chunk: taps 0..6 B[s+2] (1), taps 7 and 8 nothing in flight (0).
   for (int cc = 0; cc < CC - 1; ++cc) {
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) {
@@ -239,8 +294,13 @@ __global__ __launch_bounds__(NT3, 2) void conv3x3_split_kernel(Split3Args p) {
       if (tap == 3) store_piece(cc + 1, 0, ra00, ra01);
       if (tap == 4) store_piece(cc + 1, 1, ra10, ra11);
       if (tap == 5) store_piece(cc + 1, 2, ra20, ra21);
-      if (tap < 2) { if constexpr (GNIN) WAIT_VM(12); else WAIT_VM(8); }        // GNIN: + the four coefficient loads of tap 0
-      else WAIT_VM(2);
+      if constexpr (ONE) {
+        if (tap < 2) { if constexpr (GNIN) WAIT_VM(11); else WAIT_VM(7); }
+        else WAIT_VM(1);
+      } else {
+        if (tap < 2) { if constexpr (GNIN) WAIT_VM(12); else WAIT_VM(8); }        // GNIN: + the four coefficient loads of tap 0
+        else WAIT_VM(2);
+      }
       if (tap == 8) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // this wave's A pieces are in LDS before the barrier publishes them
       BARRIER();
     }
@@ -251,7 +311,7 @@ __global__ __launch_bounds__(NT3, 2) void conv3x3_split_kernel(Split3Args p) {
     for (int tap = 0; tap < 9; ++tap) {
       if (tap < 7) issue_b(cc, tap + 2);
       compute(cc, tap);
-      if (tap < 7) WAIT_VM(2); else WAIT_VM(0);
+      if (tap >= 7) WAIT_VM(0); else if constexpr (ONE) WAIT_VM(1); else WAIT_VM(2);
       if (tap < 8) BARRIER();
     }
   }
@@ -270,7 +330,12 @@ __global__ __launch_bounds__(NT3, 2) void conv3x3_split_kernel(Split3Args p) {
   // pixel rows instead of 64 scattered 16-byte pieces (conv3x3_bf16.hip; wave-private, no barrier, compiler fences only).
   constexpr int STG_ROW = 272;
   static_assert(8 * 16 * STG_ROW <= A_BUF, "store staging fits the idle A buffer");
-  char* const stg = smem + (CC & 1) * A_BUF + wave * (16 * STG_ROW);
+  // One term: the idle A buffer is one 24 KB image and holds five waves' rows; waves 5..7 stage in ring slots 0 and 1, which nobody
+  // reads any more: a wave arrives here past tap 7's barrier, so every wave has finished taps 6 and 7 (slots 0 and 1), every copy has
+  // landed (tap 7's vmcnt(0)), and tap 8, which others may still be computing, reads slot 2 and the OTHER A buffer.
+  static_assert(5 * 16 * STG_ROW <= A_IMG && 3 * 16 * STG_ROW <= 2 * B_TILE, "one term: store staging fits the idle A image + two ring slots");
+  char* const stg = ONE ? (wave < 5 ? smem + (CC & 1) * ABUF + wave * (16 * STG_ROW) : sB0 + (wave - 5) * (16 * STG_ROW))
+                        : smem + (CC & 1) * ABUF + wave * (16 * STG_ROW);
   const int stg_w = r16 * STG_ROW + q16 * 64;
   const int stg_r = (lane >> 4) * STG_ROW + (lane & 15) * 16;       // read-back: pixel lane >> 4 (+ 4, 8, 12), 16-byte piece lane & 15
   const int line_off = (lane >> 4) * p.Cout * 4 + (lane & 15) * 16;
@@ -606,8 +671,9 @@ void pack_conv3x3_split(const float* src_oihw, int Cin, int Cout, bool f16, floa
 }
 
 int conv3x3_split(const ConvArgs& a, const void* packed_w, float w_inv_scale, bool f16, hipStream_t st, const float* gn_in_a,
-                  const float* gn_in_b, int form) {
+                  const float* gn_in_b, int form, int terms) {
   if (!conv3x3_split_eligible(a)) SRGD_FAIL("conv3x3_split: shape not eligible");
+  if (terms != 3 && (terms != 1 || !f16)) SRGD_FAIL("conv3x3_split: three terms, or one term on f16 halves");
   const bool gnin = gn_in_a != nullptr;
   if (gnin && (a.C1 != 0 || !gn_in_b || !f16 || ((size_t)gn_in_a & 15) || ((size_t)gn_in_b & 15)))
     SRGD_FAIL("conv3x3_split: fused input GroupNorm needs one source, f16 halves and 16-byte aligned scale / shift arrays");
@@ -629,6 +695,22 @@ int conv3x3_split(const ConvArgs& a, const void* packed_w, float w_inv_scale, bo
     once.done();
   }
   const bool stats = a.gn_partial != nullptr;
+  if (terms == 1) {
+    static bool attr_set1[64] = {};
+    if (DeviceSetup once(attr_set1); once.need) {
+#define K_SET1(S_, G_)                                                                                    \
+  SRGD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_split_kernel<S_, true, G_, 1>),     \
+                               hipFuncAttributeMaxDynamicSharedMemorySize, LDS1_BYTES));
+      K_SET1(true, false) K_SET1(false, false) K_SET1(true, true) K_SET1(false, true)
+#undef K_SET1
+      once.done();
+    }
+#define K_GO1(S_, G_) hipLaunchKernelGGL((conv3x3_split_kernel<S_, true, G_, 1>), dim3(grid), dim3(NT3), LDS1_BYTES, st, p)
+    if (stats && gnin) K_GO1(true, true); else if (stats) K_GO1(true, false); else if (gnin) K_GO1(false, true); else K_GO1(false, false);
+#undef K_GO1
+    SRGD_HIP(hipGetLastError());
+    return 0;
+  }
   // default: the 512-thread kernel (one workgroup per CU); SRGD_SPLIT3_WG=2: the 256-thread kernel (two per CU; f16 halves only).
   // Same-box A/B (profiles/r6/conv3x3_split_forms_ab.txt): bit-identical results, 0.3873 vs 0.3854 HR tiles/s - the kernel is not
   // waiting on its barriers, it runs at the matrix pipe's sustained rate like conv3x3_bf16 - so the form with half the weight traffic stays

@@ -286,6 +286,7 @@ struct srgd_engine {
   // the tile's own resolution - final block + last up stage (tail 2), first down stage (head 1) - because that is where the error is
   // made (tools/mx2_tail_study.py, profiles/r6/conv3x3_mx2_prototype.txt: configs[1] after 2 steps 2.3e-3 -> 2.3e-4 for 4 % of speed)
   int mx2_exact_tail = 2, mx2_exact_head = 1;
+  bool x1 = false;            // SRGD_PRECISION_F16X1: split mode whose halo-kernel 3x3 convolutions contract the hi halves alone (one f16 MFMA per product)
   bool split = false;         // SRGD_PRECISION_F16X3: fp32 tensors, convolutions as three f16 MFMAs per product (conv3x3_split.hip)
   bool fp8 = false;           // SRGD_PRECISION_FP8: 3x3 convolutions on the block-scaled MX-fp8 matrix cores, the rest as bf16
   bool w8 = false;            // SRGD_PRECISION_BF16_W8: conv weights rounded through fp8 e4m3 (per-output-channel scale)
@@ -462,9 +463,10 @@ int build_topology(srgd_engine* e) {
   if (c.sinus_dim < 2 || c.sinus_dim % 2) SRGD_FAIL("learned_sinusoidal_dim must be even");
   if (c.dim % 16 != 0) SRGD_FAIL("unet_dim must be a multiple of 16");
   if (c.groups < 1 || c.dim % c.groups != 0) SRGD_FAIL("unet_dim must be divisible by resnet_block_groups");
-  if (c.precision < SRGD_PRECISION_FP32 || c.precision > SRGD_PRECISION_F16MX2) SRGD_FAIL("unknown precision mode");
+  if (c.precision < SRGD_PRECISION_FP32 || c.precision > SRGD_PRECISION_F16X1) SRGD_FAIL("unknown precision mode");
   e->mx2 = c.precision == SRGD_PRECISION_F16MX2;
-  e->split = c.precision == SRGD_PRECISION_F16X3 || e->mx2;
+  e->x1 = c.precision == SRGD_PRECISION_F16X1;
+  e->split = c.precision == SRGD_PRECISION_F16X3 || e->mx2 || e->x1;
   e->bf16 = c.precision != SRGD_PRECISION_FP32 && !e->split;
   e->w8 = c.precision == SRGD_PRECISION_BF16_W8;
   e->fp8 = c.precision == SRGD_PRECISION_FP8 || c.precision == SRGD_PRECISION_FP8_MIXED;
@@ -799,7 +801,7 @@ int run_conv(Ctx& x, const ConvW& c, const void* in0, int C0, const void* in1, i
   if (split3) {
     if (stats) e->stats_slots = conv3x3_bf16_stats_slots(a);
     if (c.wm3) return conv3x3_mx2(a, c.wm3, c.ws_inv, x.st, gn_in ? e->coefA : nullptr, gn_in ? e->coefB : nullptr);
-    return conv3x3_split(a, c.ws3, c.ws_inv, true, x.st, gn_in ? e->coefA : nullptr, gn_in ? e->coefB : nullptr);
+    return conv3x3_split(a, c.ws3, c.ws_inv, true, x.st, gn_in ? e->coefA : nullptr, gn_in ? e->coefB : nullptr, 0, e->x1 ? 1 : 3);
   }
   if (gn_in) SRGD_FAIL("internal: fused input GroupNorm requested on the generic conv path");
   if (split1) return conv1x1_split(a, c.ws1, c.ws_inv, x.st);

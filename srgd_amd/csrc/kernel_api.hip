@@ -121,14 +121,16 @@ static int conv2d_body(const void* in0, const void* in1, int C0, int C1, int B, 
   // impl 8 / 9: the same two kernels with bf16 halves (numerics comparison only - the engine uses f16)
   // impl 10: the streaming pointwise kernel of that mode (conv1x1_split.hip; f16 halves)
   // impl 11: impl 6 with the producer's GroupNorm + SiLU applied while the input is staged (gn_tail_a / gn_tail_b = [B][C0] scale / shift)
-  const bool split_gnin = impl == 11 || impl == 13;
+  // impl 16 / 17: impl 6 / 11 with ONE term per product, the hi halves alone (conv3x3_split's one-term instances; the f16x1 mode)
+  const bool split_one = impl == 16 || impl == 17;
+  const bool split_gnin = impl == 11 || impl == 13 || impl == 17;
   if (split_gnin) {
-    if (!gn_tail_a || !gn_tail_b || C1) SRGD_FAIL("srgd_k_conv2d: impl 11 (GroupNorm-in-staging) needs one source and gn_tail_a / gn_tail_b");
+    if (!gn_tail_a || !gn_tail_b || C1) SRGD_FAIL("srgd_k_conv2d: impl 11 / 13 / 17 (GroupNorm-in-staging) needs one source and gn_tail_a / gn_tail_b");
     a.gn_res_src = nullptr; a.gn_res_a = nullptr; a.gn_res_b = nullptr;
   }
   // impl 12 / 13: impl 6 / 11 on the 256-thread form of the kernel (two workgroups per CU) instead of the engine's default
   const bool split_form2 = impl == 12 || impl == 13;
-  const bool split3 = impl == 6 || impl == 8 || impl == 12 || split_gnin, splitg = impl == 7 || impl == 9, split1 = impl == 10, split_f16 = impl == 6 || impl == 7 || impl == 12 || split1 || split_gnin;
+  const bool split3 = impl == 6 || impl == 8 || impl == 12 || impl == 16 || split_gnin, splitg = impl == 7 || impl == 9, split1 = impl == 10, split_f16 = impl == 6 || impl == 7 || impl == 12 || impl == 16 || split1 || split_gnin;
   DevBuf dws;
   float ws_inv = 1.f;
   if (split3 || splitg || split1) {
@@ -161,7 +163,7 @@ static int conv2d_body(const void* in0, const void* in1, int C0, int C1, int B, 
   if (stats_slots) *stats_slots = (fast || split3 || mx2) ? conv3x3_bf16_stats_slots(a) : (a.Hout * a.Wout) / conv_tile_m();
   auto run = [&]() -> int {
     if (mx2) return conv3x3_mx2(a, dwm.p, ws_inv, st, impl == 15 ? gn_tail_a : nullptr, impl == 15 ? gn_tail_b : nullptr);
-    if (split3) return conv3x3_split(a, dws.p, ws_inv, split_f16, st, split_gnin ? gn_tail_a : nullptr, split_gnin ? gn_tail_b : nullptr, split_form2 ? 2 : 0);
+    if (split3) return conv3x3_split(a, dws.p, ws_inv, split_f16, st, split_gnin ? gn_tail_a : nullptr, split_gnin ? gn_tail_b : nullptr, split_form2 ? 2 : 0, split_one ? 1 : 3);
     if (split1) return conv1x1_split(a, dws.p, ws_inv, st);
     if (splitg) return conv_igemm_split(a, dws.p, ws_inv, split_f16, st);
     if (fastq1) return conv1x1_mxfp8(a, q0.p, s0.p, q1.p, s1.p, dwq1.p, st);

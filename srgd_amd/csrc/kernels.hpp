@@ -119,8 +119,10 @@ void pack_conv3x3_split(const float* src_oihw, int Cin, int Cout, bool f16, floa
 // staged (the producer's GroupNorm + SiLU, fused; single source)
 // form: 0 = the engine's choice (SRGD_SPLIT3_WG, default 1), 1 = the 512-thread kernel (one workgroup per CU), 2 = the 256-thread
 // kernel (two workgroups per CU; f16 halves only)
+// terms: 3, or 1 = the hi halves alone (f16 halves only; the same packed_w, whose lo tiles are then not read; the 512-thread kernel
+// whatever `form` and SRGD_SPLIT3_WG say - the 256-thread kernel has no one-term instance)
 int conv3x3_split(const ConvArgs& a, const void* packed_w, float w_inv_scale, bool f16, hipStream_t st,
-                  const float* gn_in_a = nullptr, const float* gn_in_b = nullptr, int form = 0);
+                  const float* gn_in_a = nullptr, const float* gn_in_b = nullptr, int form = 0, int terms = 3);
 // conv3x3_mx2.hip: prototype of a TWO-MFMA split arithmetic (f16 leading term, both cross terms on MX-fp8 operands); conv3x3_split's shapes
 void pack_conv3x3_mx2(const float* src_oihw, int Cin, int Cout, float scale, std::vector<unsigned char>& out);
 int conv3x3_mx2(const ConvArgs& a, const void* packed_w, float w_inv_scale, hipStream_t st, const float* gn_in_a = nullptr,

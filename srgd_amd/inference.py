@@ -6,7 +6,7 @@ Differences that are deliberate and documented: torchvision/log
 ``T.Resize`` on a PIL image, ``ToTensor`` and ``ToPILImage`` do; ``pil_to_unit_tensor`` / ``unit_tensor_to_pil`` are
 the host-side equivalents kept for tests); ``--no_amp`` is accepted and, as upstream (whose sampler ignores ``amp`` and
 always computes fp32), changes nothing: the default run reproduces the reference's fp32 numerics.
-Engine-only switches: ``--precision {fp32,f16x3,bf16,bf16_w8,fp8,fp8_mixed}`` opts into a throughput mode, ``--device_noise`` switches from
+Engine-only switches: ``--precision {fp32,f16x3,f16x1,bf16,bf16_w8,fp8,fp8_mixed}`` opts into a throughput mode, ``--device_noise`` switches from
 the reference-compatible host noise stream to on-device Philox.
 """
 from __future__ import annotations
@@ -71,11 +71,15 @@ def parse_args(argv=None):
     p.add_argument("--seed", type=int, default=71)
     p.add_argument("--backend", type=str, default="ddp")
     # engine-only switches (absent upstream)
-    p.add_argument("--precision", choices=["fp32", "f16x3", "f16mx2", "bf16", "bf16_w8", "fp8", "fp8_mixed"], default="f16x3",
+    p.add_argument("--precision", choices=["fp32", "f16x3", "f16mx2", "f16x1", "bf16", "bf16_w8", "fp8", "fp8_mixed"], default="f16x3",
                    help="f16x3 (default since round 6): fp32 tensors, every convolution product as three f16 MFMAs on (hi, lo) operand "
                         "pairs - within 1e-5 of the reference's CPU path on its fixtures (bar: 1e-3), 3x the speed of fp32; "
                         "fp32: exact-fp32 MFMA (the reference's arithmetic up to summation order); bf16 / bf16_w8 / fp8 / fp8_mixed: "
-                        "throughput modes of the MI355X engine (explicit opt-in, not within 1e-3)")
+                        "throughput modes of the MI355X engine (explicit opt-in, not within 1e-3); f16x1: a throughput mode between "
+                        "bf16 and f16x3 - f16x3 with the 3x3 convolutions on the f16 hi halves alone, one MFMA per product: "
+                        "0.697 HR tiles/s at the headline configuration where f16x3 gives 0.423 and bf16 1.365 (profiles/f16x1_bench.txt); "
+                        "77.5 dB / max-abs 3.8e-3 against the reference on its 256^2 fixture where bf16 gives 55.9 dB, random-init weights "
+                        "(profiles/f16x1_numerics.jsonl) - NOT within 1e-3, quality on trained weights unmeasured")
     p.add_argument("--device_noise", action="store_true",
                    help="draw DDPM noise on the GPU (Philox) instead of replaying torch's CPU stream")
     group = p.add_mutually_exclusive_group()

@@ -17,6 +17,9 @@ operands reproduce what three MFMAs accumulate up to summation order.  Variants:
     f16x3ns  f16 halves, no weight scaling (what the subnormal range costs)
     bf16     plain bf16 operands (one MFMA): the throughput mode's convolution arithmetic, for scale
     f16x2_w1 / f16x2_x1 / f16mx2   cheaper relatives of f16x3 (two MFMAs' worth of matrix work; oracle/split_emulation.py), for pricing
+    f16x1    the engine's f16x1 mode: conv(x_hi, w_hi) alone (ONE MFMA; the same halves and weight scale) in the 3x3 / stride-1 / pad-1
+             convolutions its halo kernel covers (Cin % 32 == 0, Cout % 128 == 0, H % 8 == 0, W % 32 == 0), f16x3 everywhere else
+    f16x1_all  one term in EVERY convolution with Cin % 32 == 0 (what dropping the terms in the pointwise layers too would cost)
 The report is the final-pixel max-abs / PSNR against the REFERENCE's fixture (tests/golden), next to the plain fp32 oracle's.
 """
 from __future__ import annotations
@@ -37,10 +40,26 @@ sys.path.insert(0, ROOT)
 
 from oracle import srgd_oracle as O                 # noqa: E402
 from srgd_amd.synth import synth_state_dict         # noqa: E402
-from oracle.split_emulation import mixed_split_conv2d, split_conv2d    # noqa: E402
+from oracle.split_emulation import halves, mixed_split_conv2d, split_conv2d, weight_scale    # noqa: E402
 from tests.golden import cases as C                 # noqa: E402
 
 G = os.path.join(ROOT, "tests", "golden")
+
+
+def one_term_conv2d(x, w, b=None, stride=1, padding=0):
+    """conv(hi(x), hi(w s)) / s + b: the f16 hi halves of oracle/split_emulation.py alone, fp32 accumulation"""
+    s = weight_scale(w, "f16")
+    y = TF.conv2d(halves(x, "f16")[0], halves(w * s, "f16")[0], None, stride=stride, padding=padding) * (1.0 / s)
+    return y if b is None else y + b.view(1, -1, 1, 1)
+
+
+def halo_kernel_covers(x, w, stride, padding):
+    """The SHAPE part of conv3x3_split_eligible (srgd_amd/csrc/conv3x3_bf16.hip: conv3x3_patch_eligible), on the concatenated input:
+    the kernel asks C0 % 32 == 0 and C1 % 32 == 0 of each source separately, an unpadded Cout and its GroupNorm group sizes, none of
+    which the oracle's conv2d call shows.  At dim 128 every two-source 3x3 layer has both sources in multiples of 128 and the two
+    tests agree; at another width this is an approximation of the engine's dispatch."""
+    return (tuple(w.shape[2:]) == (3, 3) and stride == 1 and padding == 1 and x.shape[1] % 32 == 0 and w.shape[0] % 128 == 0
+            and x.shape[2] % 8 == 0 and x.shape[3] % 32 == 0)
 
 
 def make_conv(variant):
@@ -51,6 +70,10 @@ def make_conv(variant):
         if variant == "bf16":
             y = TF.conv2d(x.to(torch.bfloat16).float(), w.to(torch.bfloat16).float(), None, stride=stride, padding=padding)
             return y if b is None else y + b.view(1, -1, 1, 1)
+        if variant == "f16x1_all" or (variant == "f16x1" and halo_kernel_covers(x, w, stride, padding)):
+            return one_term_conv2d(x, w, b, stride=stride, padding=padding)
+        if variant == "f16x1":
+            return split_conv2d(x, w, b, stride=stride, padding=padding, kind="f16", terms=3)
         if variant in ("f16x2_w1", "f16x2_x1", "f16mx2"):        # cheaper relatives of f16x3 (pricing only, no kernel)
             return mixed_split_conv2d(x, w, b, stride=stride, padding=padding, mode=variant)
         kind = "bf16" if variant.startswith("bf16") else "f16"
