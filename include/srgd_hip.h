@@ -213,13 +213,33 @@ int srgd_sampler_noise_seeds(srgd_engine* e, const uint64_t* seeds_host, int n_c
  *   passes = 1: eps = unet(label, cond).                       (model.py:3155-3156)
  *   passes = 2, guidance_kind 1: class guidance  (label vs None)   (model.py:3151-3154)
  *   passes = 2, guidance_kind 2: condition guidance (cond vs zeros) (model.py:3147-3150)
+ *   passes = 3: joint guidance, see below (DDPM entries only; the EDM entries keep passes 1 or 2)
  * img / x_start (nullable): device fp32 canvases [n_images,3,Hp,Wp], updated in place; sub_batch counts tiles over
  * all images (image-major order).
  * noise_tiles: device fp32 [n_tiles_of_this_grid,3,tile,tile] in reference draw order, or NULL;
  * noise_canvas: device fp32 [3,Hp,Wp] for the odd-step ring, or NULL.  When a needed noise
  * pointer is NULL the engine draws it on the device (Philox, `seed`).  The last step adds none.  The noise of
  * one image is shared by all n_images (each image of the reference is sampled after reseeding with the same seed,
- * inference.py:73, so same-sized images see identical draws). */
+ * inference.py:73, so same-sized images see identical draws).
+ *
+ * Joint guidance (an engine extension; upstream refuses both scales, model.py:3138-3146 holds a commented-out four-pass form):
+ * condition and class guidance in ONE step, passes = 3.  guidance_scale is the condition scale s_c; the class scale s_l travels in
+ * guidance_kind, which a three-pass step has no other use for, as the bit pattern of the fp32 value (memcpy of the float into
+ * the int) - the export table and every existing signature stay as they are.  Per tile and pixel, three evaluations of the U-Net
+ * on the same x_t:
+ *   e   = unet(x, label, cond)
+ *   n_c = unet(x, label, zeros)     the condition dropped, the null of model.py:3149
+ *   n_l = unet(x, None,  cond)      the label dropped, the null of model.py:3153
+ *   eps = e + (s_c - 1) (e - n_c) + (s_l - 1) (e - n_l)
+ * The fully unconditional network unet(x, None, zeros) is not evaluated.  With s_l = 1 this is algebraically model.py:3150, with
+ * s_c = 1 it is :3154.  Arithmetic is fp32 in a fixed order, each operation rounded once: wc = s_c - 1, wl = s_l - 1,
+ * dc = e - n_c, dl = e - n_l, r = fma(wc, dc, e), eps = fma(wl, dl, r) - the two differences, then the two multiply-adds, both
+ * fused, the condition term first.  No clamp or select is added: a non-finite value in any of the three predictions comes out
+ * non-finite at that pixel.  Everything after the combine is the one- and two-pass step's.  One U-Net launch holds 3 x sub_batch
+ * entries (full | condition masked | null row); in a run with per-image labels the first two passes read the image's own label row.
+ * Errors of the joint form (< 0, nothing launched): no begun DDPM run (an EDM run included); a scale of exactly 1 (its term
+ * vanishes: that step is a one- or two-pass step, "passes must be 1 or 2"); a run begun without a class (class_id < 0 and no
+ * image labels); a non-finite scale. */
 int srgd_sampler_step(srgd_engine* e, int step, float* img, const float* cond_canvas, float* x_start,
                       const float* noise_tiles, const float* noise_canvas, int passes, int guidance_kind,
                       float guidance_scale, int sub_batch, uint64_t seed, void* stream);

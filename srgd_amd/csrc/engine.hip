@@ -83,19 +83,21 @@ void pack_conv_weights(const float* src, const float* bias_in, int kind, int Cin
 
 namespace {
 
-__global__ void fill_rows_kernel(int* rows, int n, int split, int v0, int v1) {
+// Batch row i of a launch is pass i / nt.  null_mask bit p: pass p reads the null row (class guidance 0b010, joint guidance
+// 0b100, otherwise 0); every other pass reads the label row.
+__global__ void fill_rows_kernel(int* rows, int n, int nt, int null_mask, int v_label, int v_null) {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) rows[i] = (i < split) ? v0 : v1;
+  if (i < n) rows[i] = ((null_mask >> (i / nt)) & 1) ? v_null : v_label;
 }
 // Per-image labels: batch row i of a launch is pass i / nt of tile first + i % nt.  The tile's image (third int of its
-// tile-list record, the index TileBatch addresses ImageDesc with) selects the image's label slot; pass 1 takes null_row
-// under class guidance (null_row >= 0) and the label row otherwise.  base: row offset of the evaluation inside a step.
+// tile-list record, the index TileBatch addresses ImageDesc with) selects the image's label slot; a pass whose bit of
+// null_mask is set takes null_row, every other pass the image's own label row.  base: row offset of the evaluation inside a step.
 __global__ void fill_rows_labels_kernel(int* rows, int n, int nt, const int* tile_yx, int first, const int* slots, int base,
-                                        int null_row) {
+                                        int null_mask, int null_row) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const int pass = i / nt, image = tile_yx[3 * (first + (i - pass * nt)) + 2];
-  rows[i] = base + ((pass == 1 && null_row >= 0) ? null_row : slots[image]);
+  rows[i] = base + (((null_mask >> pass) & 1) ? null_row : slots[image]);
 }
 __global__ void set_step_kernel(int* step, int v) { *step = v; }
 __global__ void rows_api_kernel(int* rows, int n, int odd) {
@@ -364,11 +366,12 @@ struct srgd_engine {
   struct StepKey {                   // everything a captured step bakes in besides what it reads through d_step
     int mode;                        // 0: DDPM step, 1: EDM step
     int parity, passes, kind, sub_batch; float scale; const void *img, *cond, *xs; uint64_t seed; bool last;
+    float scale2;                    // joint guidance: the class scale (0 otherwise)
     int tile_first, tile_count; bool ring;
     const void* work;                // EDM step: its scratch canvases
     bool operator==(const StepKey& o) const {
       return mode == o.mode && parity == o.parity && passes == o.passes && kind == o.kind && sub_batch == o.sub_batch &&
-             scale == o.scale && img == o.img && cond == o.cond && xs == o.xs && seed == o.seed && last == o.last &&
+             scale == o.scale && scale2 == o.scale2 && img == o.img && cond == o.cond && xs == o.xs && seed == o.seed && last == o.last &&
              tile_first == o.tile_first && tile_count == o.tile_count && ring == o.ring && work == o.work;
     }
   };
@@ -1257,18 +1260,18 @@ int label_slots(const srgd_engine* e, const int32_t* ids, int n, std::vector<int
 }
 
 // Conditioning rows of one U-Net launch of a sampler step: evaluation `ev` of the step (EDM: 0 at sigma_hat, 1 at sigma_next),
-// entries [0, nt) = pass 0, [nt, nb) = pass 1 (the null row under class guidance).  The step's own rows are added on the
-// device (Ctx::step_mul).
-void launch_step_rows(srgd_engine* e, int nb, int nt, const int* tiles, int first, int ev, bool pass1_null, hipStream_t st) {
+// entries [p * nt, (p + 1) * nt) = pass p; null_mask bit p: pass p takes the null row (class guidance: pass 1, joint guidance:
+// pass 2).  The step's own rows are added on the device (Ctx::step_mul).
+void launch_step_rows(srgd_engine* e, int nb, int nt, const int* tiles, int first, int ev, int null_mask, hipStream_t st) {
   if (e->run_labels) {
     const int K = e->n_labels;
     hipLaunchKernelGGL(fill_rows_labels_kernel, dim3(cdiv(nb, 256)), dim3(256), 0, st, e->d_rows, nb, nt, tiles, first,
-                       e->d_slots, ev * (K + 1), pass1_null ? K : -1);
+                       e->d_slots, ev * (K + 1), null_mask, K);
     return;
   }
   const int row_label = e->run_class >= 0 ? 0 : 1, row_null = 1;
-  hipLaunchKernelGGL(fill_rows_kernel, dim3(cdiv(nb, 256)), dim3(256), 0, st, e->d_rows, nb, nt, 2 * ev + row_label,
-                     2 * ev + (pass1_null ? row_null : row_label));
+  hipLaunchKernelGGL(fill_rows_kernel, dim3(cdiv(nb, 256)), dim3(256), 0, st, e->d_rows, nb, nt, null_mask, 2 * ev + row_label,
+                     2 * ev + row_null);
 }
 
 // what a network evaluation of a sampler step needs besides its tiles
@@ -1278,6 +1281,7 @@ struct StepEval {
   float *img, *x_start;      // the canvases the final step updates
   int ev;                    // evaluation of the step whose conditioning rows it takes (EDM: 0 at sigma_hat, 1 at sigma_next)
   int evals;                 // evaluations per step the conditioning table holds: 1 (DDPM), 2 (EDM, both solvers)
+  float class_scale = 0.f;   // joint guidance (passes 3, kind 3): s_l; guidance_scale is s_c
 };
 
 // One U-Net evaluation of one launch's tiles, the same for every sampler step: input conv from the canvases -> conditioning
@@ -1290,9 +1294,11 @@ template <typename Gather, typename Final>
 int eval_tile_batch(srgd_engine* e, const TileBatch& tb, const StepEval& s, hipStream_t st, Gather&& gather, Final&& final_launch) {
   const int tile = tb.tile, nt = tb.ntiles, nb = nt * s.passes;
   // the second pass of a guided step: without the condition (condition guidance, kind 2: mask bit p = pass p sees it) or on
-  // the null conditioning row (class guidance, kind 1)
-  const int mask = (s.passes == 2 && s.guidance_kind == 2) ? 0x1 : 0x3;
-  const bool pass1_null = s.passes == 2 && s.guidance_kind == 1;
+  // the null conditioning row (class guidance, kind 1).  Joint guidance (three passes, kind 3): [0, nt) full, [nt, 2nt) without
+  // the condition, [2nt, 3nt) on the null row
+  const bool joint = s.passes == 3;
+  const int mask = joint ? 0x5 : (s.passes == 2 && s.guidance_kind == 2) ? 0x1 : 0x3;
+  const int null_mask = joint ? 0x4 : (s.passes == 2 && s.guidance_kind == 1) ? 0x2 : 0x0;
   void* x0 = e->pool.get((size_t)nb * tile * tile * e->dim * e->es);
   if (!x0) return -1;
   {
@@ -1305,7 +1311,7 @@ int eval_tile_batch(srgd_engine* e, const TileBatch& tb, const StepEval& s, hipS
   }
   // conditioning row = base + evals * (K+1) * step (the step's share is added on the device: Ctx::step_mul), base = (K+1) * ev +
   // (label row / K: none); K = 1 unless the run has per-image labels
-  launch_step_rows(e, nb, nt, tb.tile_yx, tb.first, s.ev, pass1_null, st);
+  launch_step_rows(e, nb, nt, tb.tile_yx, tb.first, s.ev, null_mask, st);
   Ctx x{e, nb, tile, tile, e->d_rows, e->ct_sampler.table, st, e->d_step, s.evals * (e->n_labels + 1)};
   void* act = nullptr;
   float* eps4 = final_fusion_possible(e) ? (float*)e->pool.get((size_t)nb * tile * tile * 16) : nullptr;
@@ -1313,7 +1319,7 @@ int eval_tile_batch(srgd_engine* e, const TileBatch& tb, const StepEval& s, hipS
   x.eps4 = eps4;
   SRGD_TRY(unet_body(x, x0, &act));
   FinalStepArgs fa{};
-  fa.act = act; fa.C = e->dim; fa.passes = s.passes; fa.guidance = s.guidance_scale;
+  fa.act = act; fa.C = e->dim; fa.passes = s.passes; fa.guidance = s.guidance_scale; fa.guidance2 = s.class_scale;
   fa.w = e->final_w; fa.bias = e->final_b; fa.img = s.img; fa.x_start = s.x_start;
   fa.step_ptr = e->d_step;
   fa.eps4 = x.eps4_done ? eps4 : nullptr;
@@ -1336,13 +1342,17 @@ struct StepPlan {
 // entry's test of its own pointers, reported after the step check), the tile range (tile_count < 0: to the end of the grid),
 // the size of a launch, and the scratch for it - every allocation of a step happens before any capture.
 int step_prologue(srgd_engine* e, const char* name, bool edm, bool null_arg, int step, int tile_first, int tile_count, int passes,
-                  int guidance_kind, int sub_batch, StepPlan* plan) {
+                  int guidance_kind, int sub_batch, StepPlan* plan, bool joint = false) {
   const std::string nm(name);
   if (!e || !e->run_active || e->run_is_edm != edm) SRGD_FAIL(nm + ": call " + (edm ? "srgd_edm_begin" : "srgd_sampler_begin") + " first");
   if (step < 0 || step >= e->n_steps) SRGD_FAIL(nm + ": step out of range");
   if (null_arg) SRGD_FAIL(nm + ": null argument");
-  if (passes != 1 && passes != 2) SRGD_FAIL(nm + ": passes must be 1 or 2");
-  if (passes == 2 && guidance_kind != 1 && guidance_kind != 2) SRGD_FAIL(nm + ": guidance_kind must be 1 or 2");
+  if (joint) {               // the DDPM entry decoded the joint form itself: three passes, kind 3
+    if (edm || passes != 3 || guidance_kind != 3) SRGD_FAIL(nm + ": internal: joint form");
+  } else {
+    if (passes != 1 && passes != 2) SRGD_FAIL(nm + ": passes must be 1 or 2" + (edm ? "" : " (or 3: joint guidance)"));
+    if (passes == 2 && guidance_kind != 1 && guidance_kind != 2) SRGD_FAIL(nm + ": guidance_kind must be 1 or 2");
+  }
   if (sub_batch < 1) SRGD_FAIL(nm + ": sub_batch must be >= 1");
   SRGD_HIP(hipSetDevice(e->cfg.device));
   const int parity = step & 1;
@@ -1929,7 +1939,7 @@ int srgd_k_step_rows(void* engine, int parity, int nb, int nt, int first, int ev
   SRGD_HIP(hipMalloc((void**)&tmp, (size_t)nb * sizeof(int)));
   int* const run_rows = e->d_rows;           // the run keeps its own buffer and its contents
   e->d_rows = tmp;
-  launch_step_rows(e, nb, nt, par ? e->d_tiles_odd : e->d_tiles_even, first, ev, pass1_null != 0, st);
+  launch_step_rows(e, nb, nt, par ? e->d_tiles_odd : e->d_tiles_even, first, ev, pass1_null != 0 ? 0x2 : 0x0, st);
   e->d_rows = run_rows;
   hipError_t err = hipGetLastError();
   if (err == hipSuccess) err = hipMemcpyAsync(rows_host, tmp, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, st);
@@ -2085,7 +2095,7 @@ int srgd_edm_dpmpp_step(srgd_engine* e, int step, float* img, const float* cond_
 static int sampler_step_launch(srgd_engine* e, bool last, int parity, int tile_first, int tile_count, bool ring, float* img,
                                const float* cond_canvas, float* x_start, const float* noise_tiles,
                                const float* noise_canvas, int passes, int guidance_kind, float guidance_scale,
-                               int sub_batch, uint64_t seed, hipStream_t st) {
+                               float class_scale, int sub_batch, uint64_t seed, hipStream_t st) {
   const srgd_sampler_geometry& g = e->geo;
   const int* tiles = parity ? e->d_tiles_odd : e->d_tiles_even;
   const int n = tile_first + tile_count;               // this call covers tiles [tile_first, n) of the image-major list
@@ -2104,7 +2114,7 @@ static int sampler_step_launch(srgd_engine* e, bool last, int parity, int tile_f
       nz = e->rng_tiles;
     }
   }
-  const StepEval ev{passes, guidance_kind, guidance_scale, img, x_start, 0, 1};
+  const StepEval ev{passes, guidance_kind, guidance_scale, img, x_start, 0, 1, class_scale};
   for (int first = tile_first; first < n; first += sub_batch) {
     const TileBatch tb{tiles, first, std::min(sub_batch, n - first), g.Hp, g.Wp, g.tile, 0, e->d_images, parity};
     SRGD_TRY(eval_tile_batch(
@@ -2155,14 +2165,34 @@ int srgd_sampler_step(srgd_engine* e, int step, float* img, const float* cond_ca
                                  guidance_kind, guidance_scale, sub_batch, seed, stream);
 }
 
+// The joint form of srgd_sampler_step / _step_tiles (srgd_hip.h): passes == 3, and guidance_kind holds the bits of the class scale
+static float joint_class_scale(int guidance_kind) {
+  float v;
+  static_assert(sizeof(v) == sizeof(guidance_kind), "the class scale travels in the int");
+  std::memcpy(&v, &guidance_kind, sizeof(v));
+  return v;
+}
+
 int srgd_sampler_step_tiles(srgd_engine* e, int step, int tile_first, int tile_count, int do_ring, float* img,
                             const float* cond_canvas, float* x_start, const float* noise_tiles,
                             const float* noise_canvas, int passes, int guidance_kind, float guidance_scale,
                             int sub_batch, uint64_t seed, void* stream) {
   hipStream_t st = (hipStream_t)stream;
+  const bool joint = passes == 3 && e && e->run_active && !e->run_is_edm;
+  float class_scale = 0.f;
+  if (joint) {               // refused before anything of the run is touched
+    class_scale = joint_class_scale(guidance_kind);
+    guidance_kind = 3;
+    // with a scale of exactly 1 its term vanishes and the step is a one- or two-pass step: the caller asks for that
+    if (guidance_scale == 1.0f || class_scale == 1.0f)
+      SRGD_FAIL("srgd_sampler_step: passes must be 1 or 2 (3 is joint guidance, which needs both scales different from 1)");
+    if (e->run_class < 0 && !e->run_labels)
+      SRGD_FAIL("srgd_sampler_step: joint guidance on a run begun without a class (the label-dropped pass would repeat the full one)");
+    if (!std::isfinite(guidance_scale) || !std::isfinite(class_scale)) SRGD_FAIL("srgd_sampler_step: joint guidance needs finite scales");
+  }
   StepPlan p;
   SRGD_TRY(step_prologue(e, "srgd_sampler_step", /*edm=*/false, /*null_arg=*/false, step, tile_first, tile_count, passes, guidance_kind,
-                         sub_batch, &p));
+                         sub_batch, &p, joint));
   const bool ring = do_ring != 0;
   if (!noise_tiles)    // a seeded run draws every class's tiles (sized by srgd_sampler_noise_seeds already; a no-op then)
     SRGD_TRY(ensure(e, &e->rng_tiles, &e->rng_tiles_cap,
@@ -2172,15 +2202,15 @@ int srgd_sampler_step_tiles(srgd_engine* e, int step, int tile_first, int tile_c
   const bool graphable = e->use_graphs && !e->prof_on && !noise_tiles && !noise_canvas;
   if (!graphable)
     return sampler_step_launch(e, p.last, p.parity, p.tile_first, p.tile_count, ring, img, cond_canvas, x_start, noise_tiles,
-                               noise_canvas, passes, guidance_kind, guidance_scale, p.sub_batch, seed, st);
+                               noise_canvas, passes, guidance_kind, guidance_scale, class_scale, p.sub_batch, seed, st);
   srgd_engine::StepKey key{};
   key.mode = 0; key.work = nullptr;
   key.parity = p.parity; key.last = p.last; key.tile_first = p.tile_first; key.tile_count = p.tile_count; key.sub_batch = p.sub_batch;
-  key.passes = passes; key.kind = guidance_kind; key.scale = guidance_scale; key.seed = seed; key.ring = ring;
+  key.passes = passes; key.kind = guidance_kind; key.scale = guidance_scale; key.scale2 = class_scale; key.seed = seed; key.ring = ring;
   key.img = img; key.cond = cond_canvas; key.xs = x_start;
   return run_step_through_graph(e, key, st, [&](hipStream_t s2) {
     return sampler_step_launch(e, p.last, p.parity, p.tile_first, p.tile_count, ring, img, cond_canvas, x_start, nullptr, nullptr,
-                               passes, guidance_kind, guidance_scale, p.sub_batch, seed, s2);
+                               passes, guidance_kind, guidance_scale, class_scale, p.sub_batch, seed, s2);
   });
 }
 

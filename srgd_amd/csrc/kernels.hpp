@@ -303,6 +303,10 @@ struct FinalStepArgs {
   const void* act;         // NHWC [ntiles*passes, tile, tile, C]
   int C, passes;
   float guidance;          // eps = null + (cond - null) * guidance when passes == 2
+  // passes == 3, joint guidance (srgd_hip.h, srgd_sampler_step with passes = 3): act / eps4 hold e | n_c | n_l, guidance = s_c, guidance2 = s_l,
+  // eps = fma(s_l - 1, e - n_l, fma(s_c - 1, e - n_c, e)): the two differences, then the two fused multiply-adds, the condition
+  // term first; s - 1 is an fp32 subtraction.  No clamp, no select: a non-finite prediction stays non-finite.  DDPM step only.
+  float guidance2 = 0.f;
   const float* w;          // [3][C]
   const float* bias;       // [3]
   float* img;              // canvas, updated in place

@@ -149,10 +149,19 @@ __device__ __forceinline__ void out_conv3_coop(const T* __restrict__ a, int C, c
   e[2] = s2 + bias[2];
 }
 
+// Joint guidance (FinalStepArgs, passes == 3): four fp32 operations, each rounded once, in this order.
+__device__ __forceinline__ float joint_combine(float e, float nc, float nl, float wc, float wl) {
+  const float dc = __fsub_rn(e, nc);          // e - n_c
+  const float dl = __fsub_rn(e, nl);          // e - n_l
+  const float r = __fmaf_rn(wc, dc, e);       // e + (s_c - 1)(e - n_c), fused
+  return __fmaf_rn(wl, dl, r);                // ... + (s_l - 1)(e - n_l), fused
+}
+
 // One block = 256 consecutive pixels of one tile.  Phase 1: 16 groups of 16 lanes walk the pixels (coalesced reads of
 // the activation rows), eps (after the guidance combine) goes to LDS; phase 2: one thread per pixel does the DDPM
-// update on the three canvas planes (coalesced along x).
-template <typename T>
+// update on the three canvas planes (coalesced along x).  JOINT: the three-pass instance (a.passes == 3); the one- and two-pass
+// instance holds nothing of it.
+template <typename T, bool JOINT>
 __global__ __launch_bounds__(256) void final_step_kernel(FinalStepArgs a, TileBatch tb) {
   __shared__ float eps[3][256];
   const int tile = tb.tile;
@@ -162,10 +171,19 @@ __global__ __launch_bounds__(256) void final_step_kernel(FinalStepArgs a, TileBa
   const T* act = reinterpret_cast<const T*>(a.act);
   if (a.eps4) {                              // the output convolution ran in the last ResnetBlock's epilogue (ConvArgs::eps4)
     f32x4 e = *reinterpret_cast<const f32x4*>(a.eps4 + (p0 + threadIdx.x) * 4);
+    if constexpr (!JOINT) {
     if (a.passes == 2) {
       const f32x4 n = *reinterpret_cast<const f32x4*>(a.eps4 + (p0 + threadIdx.x + per_tile * tb.ntiles) * 4);
 #pragma unroll
       for (int c = 0; c < 3; ++c) e[c] = n[c] + (e[c] - n[c]) * a.guidance;
+    }
+    } else {
+      const long pass = per_tile * tb.ntiles;
+      const f32x4 nc = *reinterpret_cast<const f32x4*>(a.eps4 + (p0 + threadIdx.x + pass) * 4);
+      const f32x4 nl = *reinterpret_cast<const f32x4*>(a.eps4 + (p0 + threadIdx.x + 2 * pass) * 4);
+      const float wc = __fsub_rn(a.guidance, 1.0f), wl = __fsub_rn(a.guidance2, 1.0f);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) e[c] = joint_combine(e[c], nc[c], nl[c], wc, wl);
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) eps[c][threadIdx.x] = e[c];
@@ -175,11 +193,21 @@ __global__ __launch_bounds__(256) void final_step_kernel(FinalStepArgs a, TileBa
     const int q = i * 16 + grp;
     float e[3];
     out_conv3_coop<T>(act + (p0 + q) * a.C, a.C, a.w, a.bias, lane16, e);
+    if constexpr (!JOINT) {
     if (a.passes == 2) {
       float n[3];
       out_conv3_coop<T>(act + (p0 + q + per_tile * tb.ntiles) * a.C, a.C, a.w, a.bias, lane16, n);
 #pragma unroll
       for (int c = 0; c < 3; ++c) e[c] = n[c] + (e[c] - n[c]) * a.guidance;     // model.py:3150 / :3154
+    }
+    } else {
+      const long pass = per_tile * tb.ntiles;
+      float nc[3], nl[3];
+      out_conv3_coop<T>(act + (p0 + q + pass) * a.C, a.C, a.w, a.bias, lane16, nc);
+      out_conv3_coop<T>(act + (p0 + q + 2 * pass) * a.C, a.C, a.w, a.bias, lane16, nl);
+      const float wc = __fsub_rn(a.guidance, 1.0f), wl = __fsub_rn(a.guidance2, 1.0f);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) e[c] = joint_combine(e[c], nc[c], nl[c], wc, wl);
     }
     if (lane16 < 3) eps[lane16][q] = lane16 == 0 ? e[0] : (lane16 == 1 ? e[1] : e[2]);
   }
@@ -568,8 +596,12 @@ int final_step(const FinalStepArgs& a, const TileBatch& tb, bool is_bf16, hipStr
   if (a.C % (is_bf16 ? 8 : 4) != 0) SRGD_FAIL("final_step: C must be a multiple of the vector width");
   if (((long)tb.tile * tb.tile) % 256 != 0) SRGD_FAIL("final_step: tile area must be a multiple of 256");
   if (!tb.images) SRGD_FAIL("final_step: tile batch without image records");
-  if (is_bf16) hipLaunchKernelGGL((final_step_kernel<bf16>), dim3(grid), dim3(256), 0, st, a, tb);
-  else hipLaunchKernelGGL((final_step_kernel<float>), dim3(grid), dim3(256), 0, st, a, tb);
+  if (a.passes < 1 || a.passes > 3) SRGD_FAIL("final_step: one, two or three passes");
+  if (a.passes == 3) {
+    if (is_bf16) hipLaunchKernelGGL((final_step_kernel<bf16, true>), dim3(grid), dim3(256), 0, st, a, tb);
+    else hipLaunchKernelGGL((final_step_kernel<float, true>), dim3(grid), dim3(256), 0, st, a, tb);
+  } else if (is_bf16) hipLaunchKernelGGL((final_step_kernel<bf16, false>), dim3(grid), dim3(256), 0, st, a, tb);
+  else hipLaunchKernelGGL((final_step_kernel<float, false>), dim3(grid), dim3(256), 0, st, a, tb);
   SRGD_HIP(hipGetLastError());
   return 0;
 }

@@ -6,6 +6,7 @@ arithmetic step of the hot path happens inside ``libsrgd_hip.so``.
 from __future__ import annotations
 
 import ctypes as C
+import struct
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -190,6 +191,25 @@ class HipEngine:
                                                   _dev_ptr(noise_tiles), _dev_ptr(noise_canvas), passes, guidance_kind,
                                                   float(guidance_scale), int(sub_batch), int(seed) & (2 ** 64 - 1),
                                                   _stream_ptr(self.device)), "srgd_sampler_step_tiles")
+
+    @staticmethod
+    def _joint_kind(class_scale: float) -> int:
+        """The class scale of a joint step as it travels in ``guidance_kind``: the bits of the fp32 value (srgd_hip.h)."""
+        return struct.unpack("<i", struct.pack("<f", float(class_scale)))[0]
+
+    def sampler_step_joint(self, step: int, img: torch.Tensor, cond_canvas: torch.Tensor, x_start: Optional[torch.Tensor],
+                           noise_tiles: Optional[torch.Tensor], noise_canvas: Optional[torch.Tensor], cond_scale: float,
+                           class_scale: float, sub_batch: int, seed: int = 0) -> None:
+        """Condition and class guidance in one three-pass step: ``srgd_sampler_step`` with passes = 3; ``sub_batch`` counts tiles."""
+        self.sampler_step(step, img, cond_canvas, x_start, noise_tiles, noise_canvas, 3, self._joint_kind(class_scale), cond_scale,
+                          sub_batch, seed)
+
+    def sampler_step_joint_tiles(self, step: int, tile_first: int, tile_count: int, do_ring: bool, img: torch.Tensor,
+                                 cond_canvas: torch.Tensor, x_start: Optional[torch.Tensor],
+                                 noise_tiles: Optional[torch.Tensor], noise_canvas: Optional[torch.Tensor], cond_scale: float,
+                                 class_scale: float, sub_batch: int, seed: int = 0) -> None:
+        self.sampler_step_tiles(step, tile_first, tile_count, do_ring, img, cond_canvas, x_start, noise_tiles, noise_canvas, 3,
+                                self._joint_kind(class_scale), cond_scale, sub_batch, seed)
 
     def sampler_unpack_gathered(self, parity: int, world: int, slice_w: int, part_off: int, part_w: int, canvas: torch.Tensor,
                                 gathered: torch.Tensor) -> None:

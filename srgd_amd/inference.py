@@ -152,6 +152,12 @@ def parse_args(argv=None):
                         "clips the prediction to [-s, s] and divides it by s - for guidance scales above 1 (--cond_scale, "
                         "--class_cond_scale), whose overshoot a hard clamp turns into saturated regions; one small batched GPU "
                         "call per step (engine extension)")
+    p.add_argument("--joint_guidance", action="store_true",
+                   help="allow --cond_scale and --class_cond_scale together in the DDPM sampling loop: every step on which both are "
+                        "in force is one three-pass step, eps = e + (s_c - 1)(e - n_c) + (s_l - 1)(e - n_l), with n_c the prediction "
+                        "without the condition and n_l the one without the label; about 1.5 times the time of a two-pass step, no "
+                        "more memory; without the flag both scales are refused as upstream refuses them; see --dynamic_threshold "
+                        "for the overshoot (engine extension)")
     p.add_argument("--outscale", type=float, default=4.0, metavar="S",
                    help="write every file at S times the size of its input instead of 4 times, S in [0.5, 32] (4, the default: off): the "
                         "x4 output as it would have been saved - after --color_fix and --back_project - is resampled on the GPU to "
@@ -294,6 +300,11 @@ def _threshold_kw(dynamic_threshold):
     """``tiled_sample``'s ``dynamic_threshold`` keyword for a percentile > 0; nothing for 0 / None (the call a run without the flag
     makes)."""
     return {"dynamic_threshold": dynamic_threshold} if dynamic_threshold else {}
+
+
+def _joint_kw(joint_guidance):
+    """``tiled_sample``'s ``joint_guidance`` keyword where it is set; nothing otherwise (the call a run without the flag makes)."""
+    return {"joint_guidance": True} if joint_guidance else {}
 
 
 def _sampler_kw(sampler="ddpm", eta=None, step_spacing="time"):
@@ -499,7 +510,8 @@ def sr_target_image(image, sr_model, scale=4, batch_size=8, test_label=2, cond_s
                     class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0,
                     num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None, reference=None,
                     crop_border=4, back_project=0, consistency_guidance=0.0,
-                    consistency_guidance_start_steps=0, sampler="ddpm", eta=None, step_spacing="time", dynamic_threshold=None):
+                    consistency_guidance_start_steps=0, sampler="ddpm", eta=None, step_spacing="time", dynamic_threshold=None,
+                    joint_guidance=False):
     """``reference`` (engine extension; here and in the three group forms below): the ground truth as a uint8 ``[H,W,3]`` tensor (a
     list of one per image in the group forms).  The return value is then ``(image(s), metric dicts)``: PSNR / SSIM of every image as
     saved, with ``crop_border`` pixels cut from every side (srgd_amd.metrics)."""
@@ -518,7 +530,8 @@ def sr_target_image(image, sr_model, scale=4, batch_size=8, test_label=2, cond_s
                                        num_sample_steps=num_sample_steps, amp=enable_amp, **_color_fix_kw(color_fix),
                                        **_reference_kw(reference, crop_border), **_back_project_kw(back_project),
                                        **_guidance_kw(consistency_guidance, consistency_guidance_start_steps),
-                                       **_sampler_kw(sampler, eta, step_spacing), **_threshold_kw(dynamic_threshold))
+                                       **_sampler_kw(sampler, eta, step_spacing), **_threshold_kw(dynamic_threshold),
+                                       **_joint_kw(joint_guidance))
     output, quality = _split_quality(output, reference)
     sr_img = unit_tensor_to_pil_on_device(output[0])
     assert sr_img.size == (width * 4, height * 4)
@@ -529,7 +542,8 @@ def sr_target_images(images, sr_model, scale=4, batch_size=8, test_label=2, cond
                      class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0,
                      num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None, reference=None,
                      crop_border=4, back_project=0, consistency_guidance=0.0,
-                     consistency_guidance_start_steps=0, sampler="ddpm", eta=None, step_spacing="time", dynamic_threshold=None):
+                     consistency_guidance_start_steps=0, sampler="ddpm", eta=None, step_spacing="time", dynamic_threshold=None,
+                     joint_guidance=False):
     """``sr_target_image`` for several same-sized images in lock-step (engine extension): one ``tiled_sample`` call on a
     ``[B,3,H,W]`` condition.  Each image is sampled exactly as it would be alone after the reference's per-image
     ``seed_everything(seed)`` (inference.py:73) - bit-identical outputs - while their tiles fill the U-Net launches.
@@ -549,7 +563,8 @@ def sr_target_images(images, sr_model, scale=4, batch_size=8, test_label=2, cond
                                        num_sample_steps=num_sample_steps, amp=enable_amp, **_color_fix_kw(color_fix),
                                        **_reference_kw(reference, crop_border), **_back_project_kw(back_project),
                                        **_guidance_kw(consistency_guidance, consistency_guidance_start_steps),
-                                       **_sampler_kw(sampler, eta, step_spacing), **_threshold_kw(dynamic_threshold))
+                                       **_sampler_kw(sampler, eta, step_spacing), **_threshold_kw(dynamic_threshold),
+                                       **_joint_kw(joint_guidance))
     output, quality = _split_quality(output, reference)
     outs = [unit_tensor_to_pil_on_device(o) for o in output]
     assert all(o.size == (width * 4, height * 4) for o in outs)
@@ -560,7 +575,8 @@ def sr_target_images_mixed(images, sr_model, scale=4, batch_size=8, test_label=2
                            class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0,
                            num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None, reference=None,
                            crop_border=4, back_project=0, consistency_guidance=0.0,
-                           consistency_guidance_start_steps=0, sampler="ddpm", eta=None, step_spacing="time", dynamic_threshold=None):
+                           consistency_guidance_start_steps=0, sampler="ddpm", eta=None, step_spacing="time", dynamic_threshold=None,
+                           joint_guidance=False):
     """``sr_target_image`` for several images of any sizes in lock-step (engine extension): one ``tiled_sample`` call on a list
     of conditions.  Each image comes out bit-identical to its own ``sr_target_image`` run (with its own label where
     ``test_label`` is a sequence of one label per image)."""
@@ -577,7 +593,8 @@ def sr_target_images_mixed(images, sr_model, scale=4, batch_size=8, test_label=2
                                        num_sample_steps=num_sample_steps, amp=enable_amp, **_color_fix_kw(color_fix),
                                        **_reference_kw(reference, crop_border), **_back_project_kw(back_project),
                                        **_guidance_kw(consistency_guidance, consistency_guidance_start_steps),
-                                       **_sampler_kw(sampler, eta, step_spacing), **_threshold_kw(dynamic_threshold))
+                                       **_sampler_kw(sampler, eta, step_spacing), **_threshold_kw(dynamic_threshold),
+                                       **_joint_kw(joint_guidance))
     output, quality = _split_quality(output, reference)
     outs = [unit_tensor_to_pil_on_device(o[0]) for o in output]
     assert all(o.size == (im.size[0] * 4, im.size[1] * 4) for o, im in zip(outs, images))
@@ -588,7 +605,8 @@ def sr_target_images_seeded(images, seeds, sr_model, scale=4, batch_size=8, test
                             class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0,
                             num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None,
                             reference=None, crop_border=4, back_project=0, consistency_guidance=0.0,
-                            consistency_guidance_start_steps=0, sampler="ddpm", eta=None, step_spacing="time", dynamic_threshold=None):
+                            consistency_guidance_start_steps=0, sampler="ddpm", eta=None, step_spacing="time", dynamic_threshold=None,
+                            joint_guidance=False):
     """``sr_target_images_mixed`` with one noise seed per image (engine extension, ``tiled_sample(seeds=...)``): image i comes out
     bit-identical to its own ``sr_target_image`` run with ``seed=seeds[i]``; an image may appear several times with different
     seeds (each PIL image is upsampled once).  ``seed`` seeds the process as the other entry points do and is not a noise seed."""
@@ -608,7 +626,8 @@ def sr_target_images_seeded(images, seeds, sr_model, scale=4, batch_size=8, test
                                        num_sample_steps=num_sample_steps, amp=enable_amp, seeds=list(seeds),
                                        **_color_fix_kw(color_fix), **_reference_kw(reference, crop_border), **_back_project_kw(back_project),
                                        **_guidance_kw(consistency_guidance, consistency_guidance_start_steps),
-                                       **_sampler_kw(sampler, eta, step_spacing), **_threshold_kw(dynamic_threshold))
+                                       **_sampler_kw(sampler, eta, step_spacing), **_threshold_kw(dynamic_threshold),
+                                       **_joint_kw(joint_guidance))
     output, quality = _split_quality(output, reference)
     outs = [unit_tensor_to_pil_on_device(o[0]) for o in output]
     assert all(o.size == (im.size[0] * 4, im.size[1] * 4) for o, im in zip(outs, images))
@@ -655,8 +674,10 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
                            ensemble_name="ensemble.json", consistency=False, consistency_name="consistency.json", back_project=0,
                            consistency_guidance=0.0, consistency_guidance_start_steps=0, sampler="ddpm", eta=None,
                            step_spacing="time", outscale=None, outscale_filter="bicubic", alpha="drop", alpha_bleed=0,
-                           dynamic_threshold=0.0, self_ensemble=1):
-    """``self_ensemble`` (``--self_ensemble N``, N in 1, 2, 4, 8): with N > 1 every planned entry (file, sample seed) becomes N
+                           dynamic_threshold=0.0, self_ensemble=1, joint_guidance=False):
+    """``joint_guidance`` (``--joint_guidance``): handed by keyword to whichever ``sr_target_image*`` function samples a group only
+    where it is set (``tiled_sample(joint_guidance=True)``: both guidance scales in one three-pass step).
+    ``self_ensemble`` (``--self_ensemble N``, N in 1, 2, 4, 8): with N > 1 every planned entry (file, sample seed) becomes N
     consecutive entries of the grouping, one per op of ``srgd_amd.selfens.OPS[N]`` in that order, all with the entry's seed and label;
     their inputs are ``dihedral_on_device`` of the opened input (after ``alpha_bleed``), transformed once per opened file.  The
     variants are ordinary images of their lock-step group (with neither lock-step argument they group as ``lockstep = N * samples``;
@@ -735,7 +756,7 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
               num_sample_steps=num_sample_steps, enable_amp=enable_amp, interpolation=interpolation, seed=seed,
               color_fix=None if color_fix in (None, "none") else color_fix, **_back_project_kw(back_project),
               **_guidance_kw(consistency_guidance, consistency_guidance_start_steps), **_sampler_kw(sampler, eta, step_spacing),
-              **_threshold_kw(dynamic_threshold))
+              **_threshold_kw(dynamic_threshold), **_joint_kw(joint_guidance))
     check_sampler(sampler or "ddpm", eta, step_spacing or "time")
     check_percentile(dynamic_threshold)
     outscale, outscale_filter = check_outscale(outscale), check_filter(outscale_filter)
@@ -1069,6 +1090,7 @@ def main(argv=None):
                            outscale=args.outscale, outscale_filter=args.outscale_filter, alpha=args.alpha,
                            alpha_bleed=args.alpha_bleed, dynamic_threshold=args.dynamic_threshold,
                            **({"self_ensemble": args.self_ensemble} if args.self_ensemble > 1 else {}),
+                           **_joint_kw(args.joint_guidance),
                            consistency_name="consistency.json" if world == 1 else f"consistency_rank{rank}.json")
 
 

@@ -505,15 +505,59 @@ class ConditionalSRUnet(nn.Module):
 # ---------------------------------------------------------------------------------------------
 # the sampler
 # ---------------------------------------------------------------------------------------------
-def _step_guidance(i, cond_scale, guidance_start_steps, class_cond_scale, class_guidance_start_steps):
-    """(passes, guidance_kind, scale) of DDPM step i (model.py:3147-3156)."""
+_BOTH_SCALES = "Currently, you cannot specify both cond_scale and class_cond_scale at the same time."
+
+
+def _step_guidance(i, cond_scale, guidance_start_steps, class_cond_scale, class_guidance_start_steps, joint=False):
+    """(passes, guidance_kind, scale) of DDPM step i (model.py:3147-3156).  ``joint``: a step on which both current scales differ
+    from 1 is the three-pass joint step, (3, 3, (cond scale, class scale)); every other step is what it is without it."""
     cur_cond_scale = 1.0 if i < guidance_start_steps else cond_scale
     cur_class_scale = 1.0 if i < class_guidance_start_steps else class_cond_scale
+    if joint and cur_cond_scale != 1.0 and cur_class_scale != 1.0:
+        return 3, 3, (cur_cond_scale, cur_class_scale)
     if cur_cond_scale != 1.0:
         return 2, 2, cur_cond_scale
     if cur_class_scale != 1.0:
         return 2, 1, cur_class_scale
     return 1, 0, 1.0
+
+def _launch_tiles(passes, sub_batch):
+    """Tiles per U-Net launch of a step.  A joint step (three passes) is capped at two thirds of the limit: its launches then hold
+    at most the 2 x sub_batch entries of a two-pass step, so the memory high-water mark is that of a two-pass run of the same
+    command line (results do not depend on the grouping)."""
+    return max(1, 2 * sub_batch // 3) if passes == 3 else sub_batch
+
+
+def _ddpm_step(e_, i, part, img, cond_canvas, x_start, noise_tiles, noise_canvas, passes, kind, scale, sub_batch, seed):
+    """One DDPM step on engine ``e_``: the whole grid (``part`` None) or a lane's ``(first, count, ring)``; ``passes`` 3 is the
+    joint step with ``scale = (cond scale, class scale)``, everything else today's entries."""
+    if passes == 3:
+        if part is None:
+            e_.sampler_step_joint(i, img, cond_canvas, x_start, noise_tiles, noise_canvas, scale[0], scale[1], sub_batch, seed=seed)
+        else:
+            e_.sampler_step_joint_tiles(i, part[0], part[1], part[2], img, cond_canvas, x_start, noise_tiles, noise_canvas, scale[0],
+                                        scale[1], sub_batch, seed=seed)
+    elif part is None:
+        e_.sampler_step(i, img, cond_canvas, x_start, noise_tiles, noise_canvas, passes, kind, scale, sub_batch, seed=seed)
+    else:
+        e_.sampler_step_tiles(i, part[0], part[1], part[2], img, cond_canvas, x_start, noise_tiles, noise_canvas, passes, kind, scale,
+                              sub_batch, seed=seed)
+
+
+def _check_joint(joint_guidance, cond_scale, class_cond_scale, class_label, canvas_group):
+    """Both scales at once: refused as upstream does unless ``joint_guidance``; then the refusals of the joint step itself."""
+    if cond_scale == 1.0 or class_cond_scale == 1.0:
+        return False
+    if not joint_guidance:
+        raise NotImplementedError(_BOTH_SCALES)
+    if class_label is None:
+        raise ValueError("joint_guidance needs a class_label (the label-dropped pass would repeat the full one)")
+    if canvas_group is not None:
+        raise NotImplementedError("joint_guidance on a canvas sharded over ranks (canvas_group)")
+    if not (math.isfinite(cond_scale) and math.isfinite(class_cond_scale)):
+        raise ValueError("joint_guidance: the scales must be finite")
+    return True
+
 
 class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
     def __init__(self, model, *, image_size, channels=3, noise_schedule="linear", num_sample_steps=500,
@@ -564,7 +608,8 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                      generation_start_steps=0, num_sample_steps=None, with_images=False, with_x0_images=False,
                      start_white_noise=True, amp=False, precision=None, seeds=None, color_fix=None, reference=None,
                      crop_border=4, back_project=0, consistency_guidance=0.0, consistency_guidance_start_steps=0,
-                     sampler="ddpm", eta=None, step_spacing="time", dynamic_threshold=None, threshold_log=None):
+                     sampler="ddpm", eta=None, step_spacing="time", dynamic_threshold=None, threshold_log=None,
+                     joint_guidance=False):
         """Tiled CFG-DDPM sampling (reference model.py:3288-3413).
 
         ``amp`` is accepted and ignored exactly as in the reference (which always computes fp32); the engine
@@ -639,6 +684,16 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
         ``with_x0_images`` shows the thresholded predictions.  ``threshold_log``: a list that receives one CPU tensor
         [executed steps, images] of s.  Every image of a group is bit-identical to its solo run.  Combines with every sampler, step
         spacing, ``consistency_guidance``, ``generation_start_steps``, seeds and labels.  Not available on a canvas sharded over
+        ranks.  Picture quality on trained weights is not measured.
+
+        ``joint_guidance`` (engine-only keyword, absent upstream): False (default): ``cond_scale`` and ``class_cond_scale`` both
+        different from 1 raise ``NotImplementedError`` as upstream does.  True: every step on which both current scales differ from 1
+        (after ``guidance_start_steps`` and ``class_guidance_start_steps``) is one three-pass step, eps = e + (s_c - 1)(e - n_c) +
+        (s_l - 1)(e - n_l) with n_c the prediction without the condition and n_l the one without the label (include/srgd_hip.h,
+        srgd_sampler_step with passes = 3); steps with one active scale are today's two-pass steps byte for byte, steps with none the one-pass
+        step.  A joint step launches at most ``max(1, 2 * batch_size // 3)`` tiles at once, so the run needs no more memory than a
+        two-pass run of the same arguments.  Works in all three drivers and with every other keyword, which act on the canvases
+        after the step.  ``class_label=None``: ``ValueError`` before anything is sampled; not available on a canvas sharded over
         ranks.  Picture quality on trained weights is not measured."""
         sampler, eta, step_spacing = check_sampler(sampler, eta, step_spacing)
         threshold = check_percentile(dynamic_threshold)
@@ -668,8 +723,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                 if condition_x.dim() != 4 or condition_x.shape[1] != 3:
                     raise ValueError("condition_x must be [B,3,H,W] (B=1 in the reference, whose tile gather assumes batch 1)")
                 condition_x = [condition_x[i:i + 1] for i in range(condition_x.shape[0])]
-            if cond_scale != 1.0 and class_cond_scale != 1.0:
-                raise NotImplementedError("Currently, you cannot specify both cond_scale and class_cond_scale at the same time.")
+            joint = _check_joint(joint_guidance, cond_scale, class_cond_scale, class_label, self.canvas_group)
             if tile_size != 256 or tile_stride != 256:
                 raise NotImplementedError("tile_size/tile_stride other than 256 are unusable in the reference too "
                                           "(get_coord_and_pad is called without them, model.py:3301)")
@@ -677,7 +731,8 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                                              guidance_start_steps, class_cond_scale, class_guidance_start_steps,
                                              generation_start_steps, num_sample_steps, start_white_noise, precision, seeds=seeds,
                                              color_fix=color_fix, reference=reference, crop_border=crop_border, back_project=back_project,
-                                             guidance=guidance, solver=solver, threshold=threshold, threshold_log=threshold_log)
+                                             guidance=guidance, solver=solver, threshold=threshold, threshold_log=threshold_log,
+                                             joint=joint)
             if reference is not None:
                 return (outs[0] if as_list else torch.cat(outs[0], 0)), outs[1]
             return outs if as_list else torch.cat(outs, 0)
@@ -686,8 +741,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                 raise NotImplementedError("with_images / with_x0_images of a mixed-size group (trajectories of different shapes)")
             if self.canvas_group is not None:
                 raise NotImplementedError("mixed-size lock-step on a canvas sharded over ranks (canvas_group)")
-            if cond_scale != 1.0 and class_cond_scale != 1.0:
-                raise NotImplementedError("Currently, you cannot specify both cond_scale and class_cond_scale at the same time.")
+            joint = _check_joint(joint_guidance, cond_scale, class_cond_scale, class_label, self.canvas_group)
             if tile_size != 256 or tile_stride != 256:
                 raise NotImplementedError("tile_size/tile_stride other than 256 are unusable in the reference too "
                                           "(get_coord_and_pad is called without them, model.py:3301)")
@@ -695,9 +749,9 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                                              guidance_start_steps, class_cond_scale, class_guidance_start_steps,
                                              generation_start_steps, num_sample_steps, start_white_noise, precision,
                                              color_fix=color_fix, reference=reference, crop_border=crop_border, back_project=back_project,
-                                             guidance=guidance, solver=solver, threshold=threshold, threshold_log=threshold_log)
-        if cond_scale != 1.0 and class_cond_scale != 1.0:
-            raise NotImplementedError("Currently, you cannot specify both cond_scale and class_cond_scale at the same time.")
+                                             guidance=guidance, solver=solver, threshold=threshold, threshold_log=threshold_log,
+                                             joint=joint)
+        joint = _check_joint(joint_guidance, cond_scale, class_cond_scale, class_label, self.canvas_group)
         if tile_size != 256 or tile_stride != 256:
             raise NotImplementedError("tile_size/tile_stride other than 256 are unusable in the reference too "
                                       "(get_coord_and_pad is called without them, model.py:3301)")
@@ -769,7 +823,8 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
             if i < generation_start_steps:
                 continue
             passes, kind, scale = _step_guidance(i, cond_scale, guidance_start_steps, class_cond_scale,
-                                                 class_guidance_start_steps)
+                                                 class_guidance_start_steps, joint)
+            step_tiles = _launch_tiles(passes, sub_batch)
             n_tiles = len(grids[i % 2])
             last = i == num_sample_steps - 1
             noise_tiles = noise_canvas = None
@@ -781,7 +836,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                 if i % 2 == 1:
                     noise_canvas = _host_randn(self.host_generator, 1, 3, hp, wp).to(dev, non_blocking=True)
             n_step = n_tiles * batch
-            n_lanes = lanes_wanted(n_step, passes, sub_batch, self.step_lanes, precision or self.precision) if self.canvas_group is None else 1
+            n_lanes = lanes_wanted(n_step, passes, step_tiles, self.step_lanes, precision or self.precision) if self.canvas_group is None else 1
             if n_lanes > 1:
                 if lanes is None or len(lanes.engines) != n_lanes:   # further engines: same run geometry, own copies of the condition canvas
                     more = [self.model.engine(precision or self.precision, lane=k) for k in range(1, n_lanes)]
@@ -791,12 +846,12 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                         if image_ids is not None:
                             e_.sampler_image_labels(image_ids)
                     lanes = StepLanes([eng] + more, dev)
-                lanes.run(n_step, lambda e_, first, count, ring: e_.sampler_step_tiles(
-                    i, first, count, ring, img, cond_canvas, x_start, noise_tiles, noise_canvas, passes, kind, scale, sub_batch,
-                    seed=self.device_noise_seed))
+                lanes.run(n_step, lambda e_, first, count, ring: _ddpm_step(
+                    e_, i, (first, count, ring), img, cond_canvas, x_start, noise_tiles, noise_canvas, passes, kind, scale, step_tiles,
+                    self.device_noise_seed))
             elif self.canvas_group is None:
-                eng.sampler_step(i, img, cond_canvas, x_start, noise_tiles, noise_canvas, passes, kind, scale, sub_batch,
-                                 seed=self.device_noise_seed)
+                _ddpm_step(eng, i, None, img, cond_canvas, x_start, noise_tiles, noise_canvas, passes, kind, scale, step_tiles,
+                           self.device_noise_seed)
             else:
                 from .parallel import sharded_step
                 sharded_step(eng, self.canvas_group, i, n_tiles * batch, img, cond_canvas, x_start, noise_tiles,
@@ -830,7 +885,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
     def _tiled_sample_images(self, batch_size, tile_size, conds, class_label, cond_scale, guidance_start_steps,
                              class_cond_scale, class_guidance_start_steps, generation_start_steps, num_sample_steps,
                              start_white_noise, precision, seeds=None, color_fix=None, reference=None, crop_border=4,
-                             back_project=None, guidance=None, solver=None, threshold=None, threshold_log=None):
+                             back_project=None, guidance=None, solver=None, threshold=None, threshold_log=None, joint=False):
         """Mixed-size lock-step (srgd_sampler_begin_images): every image keeps its own canvas, crop box, padding, inner box and
         tile grids; a step's tiles of all images share the U-Net launches.  Noise: the images of one noise class (canvas size)
         see the draw sequence a run of one of them alone sees.  Host noise: the generator state is taken once at entry and
@@ -854,7 +909,9 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
 
         ``threshold``: None, or the fp32 percentile of ``dynamic_threshold`` (validated by the caller): the step table is built with
         ``no_clamp``, the run keeps ``x_start`` and makes one batched threshold call for all images after every executed step, before
-        the guidance call; ``threshold_log`` (a list or None) receives the [executed steps, images] tensor of s."""
+        the guidance call; ``threshold_log`` (a list or None) receives the [executed steps, images] tensor of s.
+
+        ``joint``: ``joint_guidance`` is active (validated by the caller): steps with both scales current are three-pass steps."""
         from .lockstep import plan_mixed_group
         dev = self.device
         if dev.type != "cuda":
@@ -956,7 +1013,8 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
             if i < generation_start_steps:
                 continue
             passes, kind, scale = _step_guidance(i, cond_scale, guidance_start_steps, class_cond_scale,
-                                                 class_guidance_start_steps)
+                                                 class_guidance_start_steps, joint)
+            step_tiles = _launch_tiles(passes, sub_batch)
             last = i == num_sample_steps - 1
             noise_tiles = noise_canvas = None
             if host_noise:                  # each class in the reference's order: the step's tile noise, then the odd-step ring
@@ -966,19 +1024,19 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                 if i % 2 == 1:
                     noise_canvas = canvas_draw()
             n_step = n_grid[i % 2]
-            n_lanes = lanes_wanted(n_step, passes, sub_batch, self.step_lanes, prec)
+            n_lanes = lanes_wanted(n_step, passes, step_tiles, self.step_lanes, prec)
             if n_lanes > 1:
                 if lanes is None or len(lanes.engines) != n_lanes:   # further engines: the same mixed run, own condition canvas
                     more = [self.model.engine(prec, lane=k) for k in range(1, n_lanes)]
                     for e_ in more:
                         begin(e_, torch.empty_like(cond_canvas))
                     lanes = StepLanes([eng] + more, dev)
-                lanes.run(n_step, lambda e_, first, count, ring: e_.sampler_step_tiles(
-                    i, first, count, ring, img, cond_canvas, x_start, noise_tiles, noise_canvas, passes, kind, scale, sub_batch,
-                    seed=self.device_noise_seed))
+                lanes.run(n_step, lambda e_, first, count, ring: _ddpm_step(
+                    e_, i, (first, count, ring), img, cond_canvas, x_start, noise_tiles, noise_canvas, passes, kind, scale, step_tiles,
+                    self.device_noise_seed))
             else:
-                eng.sampler_step(i, img, cond_canvas, x_start, noise_tiles, noise_canvas, passes, kind, scale, sub_batch,
-                                 seed=self.device_noise_seed)
+                _ddpm_step(eng, i, None, img, cond_canvas, x_start, noise_tiles, noise_canvas, passes, kind, scale, step_tiles,
+                           self.device_noise_seed)
             if thresholded is not None:
                 thresholded.step(i, scalars, img, x_start)
             if guided is not None:
@@ -1011,13 +1069,14 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
     @torch.inference_mode()
     def sample(self, batch_size=16, condition_x=None, class_label=None, cond_scale=1.0, guidance_start_steps=0,
                class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0, num_sample_steps=None,
-               with_images=False, with_x0_images=False, x0=None, amp=False, precision=None):
+               with_images=False, with_x0_images=False, x0=None, amp=False, precision=None, joint_guidance=False):
         """Un-tiled sampling of a batch of ``image_size`` x ``image_size`` images (reference model.py:3417-3432,
         p_sample_loop :3191-3247): every image has its own noise (one ``randn`` over ``[B,3,S,S]`` per draw, host mode).
 
         Runs on the tiled machinery: the batch is laid out as one canvas of B stacked tiles (``[3, B*S, S]``, no padding, no
         ring re-noise), so one U-Net launch covers the whole batch.  Needs ``image_size == 256`` (the tile edge of the kernels;
-        the shipped config).  ``amp`` / ``precision`` as in ``tiled_sample``."""
+        the shipped config).  ``amp`` / ``precision`` as in ``tiled_sample``.  ``joint_guidance`` is ``tiled_sample``'s: both scales
+        are refused here with or without it."""
         num_sample_steps = self.num_sample_steps if num_sample_steps is None else num_sample_steps
         if cond_scale != 1.0 and class_cond_scale != 1.0:
             raise NotImplementedError("Currently, you cannot specify both cond_scale and class_cond_scale at the same time.")
@@ -1198,7 +1257,8 @@ class ConditionalElucidatedDiffusionSR(nn.Module):
                      generation_start_steps=0, num_sample_steps=None, clamp=True, zero_init=False, with_images=False,
                      with_x0_images=False, start_white_noise=True, amp=False, precision=None, seeds=None, color_fix=None,
                      reference=None, crop_border=4, back_project=0, consistency_guidance=0.0, consistency_guidance_start_steps=0,
-                     sampler="ddpm", eta=None, step_spacing="time", dynamic_threshold=None, threshold_log=None):
+                     sampler="ddpm", eta=None, step_spacing="time", dynamic_threshold=None, threshold_log=None,
+                     joint_guidance=False):
         """Reference model.py:2309-2475 (``start_white_noise`` and ``amp`` are accepted and unused there too; ``precision``
         is the engine-only override of ``self.precision``).  ``seeds`` (per-image noise seeds) is a DDPM-sampler feature and is
         refused here.  ``color_fix``: as in the DDPM wrapper's ``tiled_sample`` - the final image of every image of the batch
@@ -1207,7 +1267,8 @@ class ConditionalElucidatedDiffusionSR(nn.Module):
         too - N back-projection steps on the final image, after the colour fix and before the metrics.
         ``consistency_guidance``: a DDPM-sampler feature; a non-zero weight is refused here.
         ``sampler``, ``eta``, ``step_spacing``: the DDPM wrapper's few-step samplers; any non-default value is refused here.
-        ``dynamic_threshold``: a DDPM-sampler feature; a percentile other than None / 0 is refused here."""
+        ``dynamic_threshold``: a DDPM-sampler feature; a percentile other than None / 0 is refused here.
+        ``joint_guidance``: a DDPM-sampler feature; both scales are refused here with or without it."""
         color_fix = check_mode(color_fix)
         back_project = _back_project_steps(back_project, condition_x)
         if check_percentile(dynamic_threshold) is not None:
