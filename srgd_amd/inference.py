@@ -38,6 +38,7 @@ from .guidance import MIN_SIDE as GUIDANCE_MIN_SIDE
 from .metrics import KEYS as METRIC_KEYS
 from .metrics import metrics_on_device  # noqa: F401  (public: srgd_amd.inference.metrics_on_device)
 from .model import ConditionalElucidatedDiffusionSR, get_model
+from .region import MAX_BOXES as REGION_MAX_BOXES
 from .resize import FILTERS as OUTSCALE_FILTERS
 from .resize import check_filter, check_outscale, outscale_size
 from .selfens import OPS as SELF_ENSEMBLE_OPS
@@ -186,11 +187,35 @@ def parse_args(argv=None):
                         "--consistency_guidance and --dynamic_threshold act on every orientation against its own turned input, "
                         "--reference_dir, --consistency, --outscale, --alpha keep and --ensemble on the merged image (engine "
                         "extension, DDPM configs only)")
+    p.add_argument("--region_known_dir", type=str, default=None, metavar="DIR",
+                   help="resample rectangles of finished outputs: DIR holds an earlier run's output of every input, <name>_out.png "
+                        "(with --samples K: <name>_out_s<k>.png, or the one <name>_out.png for every sample - K alternatives of the "
+                        "region), exactly x4 of the input - checked before anything is sampled; inside the boxes of --region the "
+                        "image is sampled again, coherent with its surroundings, outside them the written file equals the known one "
+                        "byte for byte, and only the tiles that touch a box are evaluated; DDPM configs only, not with "
+                        "--self_ensemble or --ensemble (engine extension)")
+    p.add_argument("--region", action="append", default=None, metavar="T,L,H,W",
+                   help="with --region_known_dir: a box top,left,height,width in output pixels to sample again; repeatable up to 16 "
+                        "times, boxes may overlap; the same boxes are used for every input, so each must lie inside every output")
     args = p.parse_args(argv)
     try:
         args.self_ensemble = check_self_ensemble(args.self_ensemble)
     except ValueError as e:
         raise SystemExit(f"--self_ensemble: {e}")
+    if (args.region_known_dir is None) != (args.region is None):
+        raise SystemExit("--region_known_dir and --region go together: the finished outputs and the boxes to sample again")
+    if args.region is not None:
+        try:
+            args.region = [parse_region(text) for text in args.region]
+        except ValueError as e:
+            raise SystemExit(f"--region: {e}")
+        if len(args.region) > REGION_MAX_BOXES:
+            raise SystemExit(f"--region: at most {REGION_MAX_BOXES} boxes, got {len(args.region)}")
+        if args.self_ensemble > 1:
+            raise SystemExit("--region_known_dir: not together with --self_ensemble (a region run keeps one finished image; the "
+                             "orientations have none)")
+        if args.ensemble:
+            raise SystemExit("--region_known_dir: not together with --ensemble (outside the boxes every sample is the known image)")
     if not 0 <= args.alpha_bleed <= ALPHA_BLEED_MAX:
         raise SystemExit(f"--alpha_bleed: N must be in 0 .. {ALPHA_BLEED_MAX}, got {args.alpha_bleed}")
     if args.alpha_bleed and args.alpha != "keep":
@@ -365,6 +390,81 @@ def check_references(file_names, reference_dir, scale=4, crop_border=4):
         raise SystemExit("--reference_dir: " + str(len(problems)) + " input(s) without a usable reference:\n  " + "\n  ".join(problems))
 
 
+def parse_region(text):
+    """``--region T,L,H,W`` -> ``(top, left, height, width)``: four integers, the size positive, the corner non-negative
+    (``ValueError`` otherwise; whether the box lies inside an output is checked against the known files)."""
+    parts = str(text).split(",")
+    try:
+        box = tuple(int(v) for v in parts)
+    except ValueError:
+        box = ()
+    if len(parts) != 4 or len(box) != 4:
+        raise ValueError(f"{text!r} is not top,left,height,width (four integers)")
+    if box[0] < 0 or box[1] < 0 or box[2] < 1 or box[3] < 1:
+        raise ValueError(f"{text!r}: top and left must be >= 0, height and width >= 1")
+    return box
+
+
+def _region_kw(region_known, regions):
+    """``tiled_sample``'s ``region_known`` / ``regions`` keywords where a known image is given; nothing otherwise (the call a run
+    without the flags makes)."""
+    return {} if region_known is None else {"region_known": region_known, "regions": regions}
+
+
+def region_known_path(known_dir, file_name, k, samples=1):
+    """``--region_known_dir``: the known file of sample k of an input - ``known_dir/<name>_out.png`` (sample k >= 1:
+    ``<name>_out_s<k>.png``); under ``--samples`` a file without its own ``_out_s<k>.png`` starts every sample from the one
+    ``<name>_out.png``."""
+    own = os.path.join(known_dir, sample_output_name(file_name, k))
+    if k > 0 and samples > 1 and not os.path.isfile(own):
+        return os.path.join(known_dir, sample_output_name(file_name, 0))
+    return own
+
+
+def region_known_problems(file_names, known_dir, regions, scale=4, samples=1):
+    """``--region_known_dir`` pre-flight: one line per known file that is missing, unreadable or not exactly ``scale`` times its
+    input's size, and per box of ``regions`` that does not lie inside that output.  Only image headers are read."""
+    problems = []
+    for f in file_names:
+        name = os.path.basename(f)
+        try:
+            with Image.open(f) as im:
+                w, h = im.size
+        except (IOError, SyntaxError):
+            continue                                     # not an image: the sampling loop reports and skips it
+        for known in sorted({region_known_path(known_dir, f, k, samples) for k in range(samples)}):
+            if not os.path.isfile(known):
+                problems.append(f"{name}: known output {known} is missing")
+                continue
+            try:
+                with Image.open(known) as im:
+                    kw_, kh = im.size
+            except (IOError, SyntaxError):
+                problems.append(f"{name}: known output {known} cannot be read as an image")
+                continue
+            if (kw_, kh) != (w * scale, h * scale):
+                problems.append(f"{name}: known output {os.path.basename(known)} is {kw_}x{kh}, x{scale} of the {w}x{h} input is "
+                                f"{w * scale}x{h * scale}")
+        for (t, l, bh, bw) in regions:
+            if t + bh > h * scale or l + bw > w * scale:
+                problems.append(f"{name}: box {t},{l},{bh},{bw} does not lie inside the {w * scale}x{h * scale} output")
+    return problems
+
+
+def check_region_known(file_names, known_dir, regions, scale=4, samples=1):
+    """Ends the run (``SystemExit``, non-zero) with the lines ``region_known_problems`` lists, before any sampling."""
+    problems = region_known_problems(file_names, known_dir, regions, scale, samples)
+    if problems:
+        raise SystemExit("--region_known_dir: " + str(len(problems)) + " problem(s):\n  " + "\n  ".join(problems))
+
+
+def load_region_known(path):
+    """A known output as the fp32 ``[1,3,H,W]`` tensor in [0, 1] ``tiled_sample(region_known=...)`` takes: the file's bytes over
+    255, which ``mul(255).byte()`` writes back unchanged."""
+    with Image.open(path) as im:
+        return pil_to_unit_tensor(im)[None]
+
+
 def load_reference(path):
     """A ground-truth image as the uint8 ``[H,W,3]`` tensor ``tiled_sample(reference=...)`` takes (decoded on the host)."""
     with Image.open(path) as im:
@@ -511,10 +611,13 @@ def sr_target_image(image, sr_model, scale=4, batch_size=8, test_label=2, cond_s
                     num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None, reference=None,
                     crop_border=4, back_project=0, consistency_guidance=0.0,
                     consistency_guidance_start_steps=0, sampler="ddpm", eta=None, step_spacing="time", dynamic_threshold=None,
-                    joint_guidance=False):
+                    joint_guidance=False, region_known=None, regions=None):
     """``reference`` (engine extension; here and in the three group forms below): the ground truth as a uint8 ``[H,W,3]`` tensor (a
     list of one per image in the group forms).  The return value is then ``(image(s), metric dicts)``: PSNR / SSIM of every image as
-    saved, with ``crop_border`` pixels cut from every side (srgd_amd.metrics)."""
+    saved, with ``crop_border`` pixels cut from every side (srgd_amd.metrics).
+    ``region_known`` / ``regions`` (engine extension; here and in the three group forms below): the finished output as a fp32
+    ``[1,3,4h,4w]`` tensor in [0, 1] (a list of one per image in the group forms) and the boxes to sample again
+    (``tiled_sample(region_known=..., regions=...)``); without them the keywords are not passed at all."""
     width, height = image.size
     # the reference maps 'lanczos' to bicubic too (inference.py:66-69)
     condition_x = upsample_bicubic_on_device(image, scale, sr_model.device)
@@ -531,7 +634,7 @@ def sr_target_image(image, sr_model, scale=4, batch_size=8, test_label=2, cond_s
                                        **_reference_kw(reference, crop_border), **_back_project_kw(back_project),
                                        **_guidance_kw(consistency_guidance, consistency_guidance_start_steps),
                                        **_sampler_kw(sampler, eta, step_spacing), **_threshold_kw(dynamic_threshold),
-                                       **_joint_kw(joint_guidance))
+                                       **_joint_kw(joint_guidance), **_region_kw(region_known, regions))
     output, quality = _split_quality(output, reference)
     sr_img = unit_tensor_to_pil_on_device(output[0])
     assert sr_img.size == (width * 4, height * 4)
@@ -543,7 +646,7 @@ def sr_target_images(images, sr_model, scale=4, batch_size=8, test_label=2, cond
                      num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None, reference=None,
                      crop_border=4, back_project=0, consistency_guidance=0.0,
                      consistency_guidance_start_steps=0, sampler="ddpm", eta=None, step_spacing="time", dynamic_threshold=None,
-                     joint_guidance=False):
+                     joint_guidance=False, region_known=None, regions=None):
     """``sr_target_image`` for several same-sized images in lock-step (engine extension): one ``tiled_sample`` call on a
     ``[B,3,H,W]`` condition.  Each image is sampled exactly as it would be alone after the reference's per-image
     ``seed_everything(seed)`` (inference.py:73) - bit-identical outputs - while their tiles fill the U-Net launches.
@@ -564,7 +667,7 @@ def sr_target_images(images, sr_model, scale=4, batch_size=8, test_label=2, cond
                                        **_reference_kw(reference, crop_border), **_back_project_kw(back_project),
                                        **_guidance_kw(consistency_guidance, consistency_guidance_start_steps),
                                        **_sampler_kw(sampler, eta, step_spacing), **_threshold_kw(dynamic_threshold),
-                                       **_joint_kw(joint_guidance))
+                                       **_joint_kw(joint_guidance), **_region_kw(region_known, regions))
     output, quality = _split_quality(output, reference)
     outs = [unit_tensor_to_pil_on_device(o) for o in output]
     assert all(o.size == (width * 4, height * 4) for o in outs)
@@ -576,7 +679,7 @@ def sr_target_images_mixed(images, sr_model, scale=4, batch_size=8, test_label=2
                            num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None, reference=None,
                            crop_border=4, back_project=0, consistency_guidance=0.0,
                            consistency_guidance_start_steps=0, sampler="ddpm", eta=None, step_spacing="time", dynamic_threshold=None,
-                           joint_guidance=False):
+                           joint_guidance=False, region_known=None, regions=None):
     """``sr_target_image`` for several images of any sizes in lock-step (engine extension): one ``tiled_sample`` call on a list
     of conditions.  Each image comes out bit-identical to its own ``sr_target_image`` run (with its own label where
     ``test_label`` is a sequence of one label per image)."""
@@ -594,7 +697,7 @@ def sr_target_images_mixed(images, sr_model, scale=4, batch_size=8, test_label=2
                                        **_reference_kw(reference, crop_border), **_back_project_kw(back_project),
                                        **_guidance_kw(consistency_guidance, consistency_guidance_start_steps),
                                        **_sampler_kw(sampler, eta, step_spacing), **_threshold_kw(dynamic_threshold),
-                                       **_joint_kw(joint_guidance))
+                                       **_joint_kw(joint_guidance), **_region_kw(region_known, regions))
     output, quality = _split_quality(output, reference)
     outs = [unit_tensor_to_pil_on_device(o[0]) for o in output]
     assert all(o.size == (im.size[0] * 4, im.size[1] * 4) for o, im in zip(outs, images))
@@ -606,7 +709,7 @@ def sr_target_images_seeded(images, seeds, sr_model, scale=4, batch_size=8, test
                             num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None,
                             reference=None, crop_border=4, back_project=0, consistency_guidance=0.0,
                             consistency_guidance_start_steps=0, sampler="ddpm", eta=None, step_spacing="time", dynamic_threshold=None,
-                            joint_guidance=False):
+                            joint_guidance=False, region_known=None, regions=None):
     """``sr_target_images_mixed`` with one noise seed per image (engine extension, ``tiled_sample(seeds=...)``): image i comes out
     bit-identical to its own ``sr_target_image`` run with ``seed=seeds[i]``; an image may appear several times with different
     seeds (each PIL image is upsampled once).  ``seed`` seeds the process as the other entry points do and is not a noise seed."""
@@ -627,7 +730,7 @@ def sr_target_images_seeded(images, seeds, sr_model, scale=4, batch_size=8, test
                                        **_color_fix_kw(color_fix), **_reference_kw(reference, crop_border), **_back_project_kw(back_project),
                                        **_guidance_kw(consistency_guidance, consistency_guidance_start_steps),
                                        **_sampler_kw(sampler, eta, step_spacing), **_threshold_kw(dynamic_threshold),
-                                       **_joint_kw(joint_guidance))
+                                       **_joint_kw(joint_guidance), **_region_kw(region_known, regions))
     output, quality = _split_quality(output, reference)
     outs = [unit_tensor_to_pil_on_device(o[0]) for o in output]
     assert all(o.size == (im.size[0] * 4, im.size[1] * 4) for o, im in zip(outs, images))
@@ -674,8 +777,14 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
                            ensemble_name="ensemble.json", consistency=False, consistency_name="consistency.json", back_project=0,
                            consistency_guidance=0.0, consistency_guidance_start_steps=0, sampler="ddpm", eta=None,
                            step_spacing="time", outscale=None, outscale_filter="bicubic", alpha="drop", alpha_bleed=0,
-                           dynamic_threshold=0.0, self_ensemble=1, joint_guidance=False):
-    """``joint_guidance`` (``--joint_guidance``): handed by keyword to whichever ``sr_target_image*`` function samples a group only
+                           dynamic_threshold=0.0, self_ensemble=1, joint_guidance=False, region_known_dir=None, regions=None):
+    """``region_known_dir`` / ``regions`` (``--region_known_dir DIR``, ``--region T,L,H,W``): every planned entry's known file
+    (``region_known_path``: ``DIR/<name>_out.png``, its own ``_out_s<k>.png`` under ``samples`` where it exists) is checked first
+    (``check_region_known``), decoded on the writer pool while earlier groups sample, and handed with the boxes to whichever
+    ``sr_target_image*`` function samples the group (``tiled_sample(region_known=..., regions=...)``); everything below acts on the
+    composited image.  Without them nothing is checked, decoded or passed.  One without the other, or either together with
+    ``self_ensemble`` > 1 or ``ensemble``: ``ValueError`` before anything is sampled.
+    ``joint_guidance`` (``--joint_guidance``): handed by keyword to whichever ``sr_target_image*`` function samples a group only
     where it is set (``tiled_sample(joint_guidance=True)``: both guidance scales in one three-pass step).
     ``self_ensemble`` (``--self_ensemble N``, N in 1, 2, 4, 8): with N > 1 every planned entry (file, sample seed) becomes N
     consecutive entries of the grouping, one per op of ``srgd_amd.selfens.OPS[N]`` in that order, all with the entry's seed and label;
@@ -776,6 +885,15 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
                                  f"{GUIDANCE_MIN_SIDE} pixels on a side")
     if reference_dir is not None:
         check_references(file_names, reference_dir, scale, crop_border)
+    if (region_known_dir is None) != (regions is None):
+        raise ValueError("region_known_dir and regions go together")
+    if regions is not None:
+        if self_ensemble > 1 or ensemble:
+            raise ValueError("region_known_dir: not together with self_ensemble or ensemble")
+        regions = [parse_region(",".join(str(v) for v in box)) for box in regions]
+        if not 1 <= len(regions) <= REGION_MAX_BOXES:
+            raise ValueError(f"regions: 1 .. {REGION_MAX_BOXES} boxes, got {len(regions)}")
+        check_region_known(file_names, region_known_dir, regions, scale, samples)
     from concurrent.futures import ThreadPoolExecutor
     pending, saves = [], []                              # (image, save_path, label, noise seed, reference) of the current lock-step group; PNG writers
     file_records = []                                    # (input file name, written file name, metric dict) of --reference_dir
@@ -831,16 +949,23 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
             ref_kw = {}
             if reference_dir is not None and self_ensemble == 1:         # the decoded references of the group (one future per input file)
                 ref_kw = {"reference": [e[4].result() for e in pending], "crop_border": crop_border}
+            reg_kw = {}
+            if regions is not None:                      # the decoded known outputs of the group (one future per known file)
+                reg_kw = {"region_known": [e[10].result() for e in pending], "regions": regions}
             if len(pending) == 1:                        # a solo run with that seed: what every sample of a group is identical to
                 solo_kw = dict(ref_kw, reference=ref_kw["reference"][0]) if ref_kw else {}
+                if reg_kw:
+                    solo_kw = dict(solo_kw, region_known=reg_kw["region_known"][0], regions=regions)
                 outs = sr_target_image(pending[0][0], sr_model, test_label=group_labels[0], **dict(kw, seed=group_seeds[0]), **solo_kw)
                 outs = ([outs[0]], outs[1]) if ref_kw else [outs]
             elif len(set(group_seeds)) > 1:
-                outs = sr_target_images_seeded(group_images, group_seeds, sr_model, test_label=one_label, **kw, **ref_kw)
+                outs = sr_target_images_seeded(group_images, group_seeds, sr_model, test_label=one_label, **kw, **ref_kw, **reg_kw)
             elif lockstep_tiles is not None:
-                outs = sr_target_images_mixed(group_images, sr_model, test_label=one_label, **dict(kw, seed=group_seeds[0]), **ref_kw)
+                outs = sr_target_images_mixed(group_images, sr_model, test_label=one_label, **dict(kw, seed=group_seeds[0]), **ref_kw,
+                                              **reg_kw)
             else:
-                outs = sr_target_images(group_images, sr_model, test_label=one_label, **dict(kw, seed=group_seeds[0]), **ref_kw)
+                outs = sr_target_images(group_images, sr_model, test_label=one_label, **dict(kw, seed=group_seeds[0]), **ref_kw,
+                                        **reg_kw)
             if ref_kw:
                 outs, quality = outs
                 file_records.extend((e[5], os.path.basename(e[1]), q) for e, q in zip(pending, quality))
@@ -952,6 +1077,7 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
         opened = (None, None, None)                      # the K samples of a file share one decoded image and one reference
         plane = None                                     # --alpha keep: the alpha plane of the opened file, or None
         variants = (None, None)                          # --self_ensemble: (the opened input, its N orientations)
+        known_open = (None, None)                        # --region_known_dir: (the known file last opened, its decoding future)
         for filename, save_path, noise_seed in plan_sample_entries(file_names, output_dir, samples, seed):
             if opened[0] != filename:
                 if alpha == "keep":
@@ -978,6 +1104,12 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
                                             list(SELF_ENSEMBLE_OPS[self_ensemble]))
                 variants = (original, [Image.fromarray(t.cpu().numpy(), "RGB") for t in turned])
             label = labels.get(os.path.basename(filename), test_label)
+            known = None
+            if regions is not None:                      # decoded on the pool; the samples that start from one file share it
+                known_file = region_known_path(region_known_dir, filename, noise_seed - seed, samples)
+                if known_open[0] != known_file:
+                    known_open = (known_file, pool.submit(load_region_known, known_file))
+                known = known_open[1]
             for op, image in zip(SELF_ENSEMBLE_OPS[self_ensemble], variants[1] if self_ensemble > 1 else [original]):
                 if pending and (label is None) != (pending[0][2] is None): # an unlabelled image does not join a labelled group
                     flush()
@@ -985,11 +1117,11 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
                     hr = [(h * scale, w * scale) for (w, h) in [e[0].size for e in pending] + [image.size]]
                     if len(plan_lockstep_groups(hr, lockstep_tiles)) > 1:  # the image would push the group over the budget
                         flush()
-                    pending.append((image, save_path, label, noise_seed, ref, os.path.basename(filename), filename, plane, op, original))
+                    pending.append((image, save_path, label, noise_seed, ref, os.path.basename(filename), filename, plane, op, original, known))
                     continue
                 if pending and (len(pending) >= max(1, lockstep) or pending[0][0].size != image.size):
                     flush()
-                pending.append((image, save_path, label, noise_seed, ref, os.path.basename(filename), filename, plane, op, original))
+                pending.append((image, save_path, label, noise_seed, ref, os.path.basename(filename), filename, plane, op, original, known))
                 if len(pending) >= max(1, lockstep):
                     flush()
         flush()
@@ -1031,7 +1163,13 @@ def main(argv=None):
     if args.reference_dir is not None:                   # every rank checks the whole selection, before the model is built
         check_references(sorted(glob.glob(f"{args.input_dir}/*"))[args.start_index:args.end_index], args.reference_dir, 4,
                          args.crop_border)
+    if args.region_known_dir is not None:                # likewise: every known output and every box, before the model is built
+        check_region_known(sorted(glob.glob(f"{args.input_dir}/*"))[args.start_index:args.end_index], args.region_known_dir,
+                           args.region, 4, args.samples)
     conf = load_config(args.conf)
+    if args.region_known_dir is not None and conf.model == "conditional_elucidated":
+        raise SystemExit("--region_known_dir: region resampling is built for the DDPM sampler (model: conditional_continuous) only; "
+                         "this config samples with EDM")
     if args.self_ensemble > 1 and conf.model == "conditional_elucidated":     # before the model is built
         raise SystemExit("--self_ensemble: the orientations of an image are sampled in lock-step with per-image noise seeds, which is "
                          "built for the DDPM sampler (model: conditional_continuous) only; this config samples with EDM - run "
@@ -1091,6 +1229,7 @@ def main(argv=None):
                            alpha_bleed=args.alpha_bleed, dynamic_threshold=args.dynamic_threshold,
                            **({"self_ensemble": args.self_ensemble} if args.self_ensemble > 1 else {}),
                            **_joint_kw(args.joint_guidance),
+                           **({"region_known_dir": args.region_known_dir, "regions": args.region} if args.region else {}),
                            consistency_name="consistency.json" if world == 1 else f"consistency_rank{rank}.json")
 
 

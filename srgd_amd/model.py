@@ -37,6 +37,7 @@ from .threshold import check_percentile, threshold_step_flat
 from .threshold import records as threshold_records
 from .threshold import scratch_bytes as threshold_scratch_bytes
 from .lanes import StepLanes, lanes_setting_from_env, lanes_wanted
+from .region import RegionImage, _RegionRun, check_region_args
 
 __all__ = ["get_coord_and_pad", "get_coords", "get_area", "beta_linear_log_snr", "ConditionalSRUnet",
            "ConditionalContinuousTimeGaussianDiffusionSR", "ConditionalElucidatedDiffusionSR", "ModelEma", "get_model"]
@@ -609,7 +610,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                      start_white_noise=True, amp=False, precision=None, seeds=None, color_fix=None, reference=None,
                      crop_border=4, back_project=0, consistency_guidance=0.0, consistency_guidance_start_steps=0,
                      sampler="ddpm", eta=None, step_spacing="time", dynamic_threshold=None, threshold_log=None,
-                     joint_guidance=False):
+                     joint_guidance=False, region_known=None, regions=None, region_skip_tiles=True, region_log=None):
         """Tiled CFG-DDPM sampling (reference model.py:3288-3413).
 
         ``amp`` is accepted and ignored exactly as in the reference (which always computes fp32); the engine
@@ -694,7 +695,38 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
         step.  A joint step launches at most ``max(1, 2 * batch_size // 3)`` tiles at once, so the run needs no more memory than a
         two-pass run of the same arguments.  Works in all three drivers and with every other keyword, which act on the canvases
         after the step.  ``class_label=None``: ``ValueError`` before anything is sampled; not available on a canvas sharded over
-        ranks.  Picture quality on trained weights is not measured."""
+        ranks.  Picture quality on trained weights is not measured.
+
+        ``region_known``, ``regions`` (engine-only keywords, absent upstream; srgd_amd.region): without them nothing is allocated or
+        launched and the run is byte for byte what it is today.  ``region_known`` is a finished output of this image - fp32
+        ``[1,3,H,W]`` in [0, 1], the size of ``condition_x`` - and ``regions`` a list of 1 .. 16 ``(top, left, height, width)`` boxes
+        in output pixels, each inside the image; R is their union.  In a lock-step call ``region_known`` is a list with one entry per
+        image (``None``: that image is sampled whole, as today) and ``regions`` one box list for all of them or one per image.  With
+        k = 2 known - 1 and K(a, s) = ``srgd_sampler_q_start(known, z, a, s)`` on the image's canvas, the *replacement step* at (a, s)
+        sets ``img`` outside R to K(a, s) - R of ``img`` is copied into K, K over ``img`` - and, where the run keeps an ``x_start``
+        canvas, ``x_start`` outside R to K(1, 0), the padded known image.  It is applied to the start canvas at the start level, and
+        after the threshold, guidance and history calls of every step i at (alpha_next_i, sigma_next_i) - the last step at (1, 0)
+        without a draw.  z comes from ``srgd_randn`` with the image's noise seed (``seeds[i]``, else ``device_noise_seed``) and
+        stream ``(3 << 32) | i``; the start canvas takes index ``num_sample_steps``.  With ``region_skip_tiles`` (default True) step
+        i evaluates only the tiles of grid i % 2 that intersect R - each maximal run of consecutive tile indices is one
+        ``srgd_sampler_step_tiles`` call without the ring re-noise, which lies outside R and is overwritten - and the result is bit for
+        bit that of ``region_skip_tiles=False``, which evaluates all tiles (``dynamic_threshold`` and ``consistency_guidance`` read
+        ``x_start`` beyond R: with them the two differ, the skipped tiles showing the known image).  After ``color_fix`` and
+        ``back_project`` and before the ``reference`` metrics the output outside R is set to ``region_known`` by copy.
+        ``region_log``: a list that receives one row ``[tiles evaluated per image]`` per executed step.  Step lanes are off in a
+        region run.  ``ValueError`` before anything is sampled: a box outside the image, no box or more than 16, a ``region_known``
+        of another shape or dtype, one keyword without the other; not available on a canvas sharded over ranks or in the EDM
+        wrapper (``NotImplementedError``).  Picture quality on trained weights is not measured."""
+        region = None
+        if region_known is not None or regions is not None:
+            if self.canvas_group is not None:
+                raise NotImplementedError("region_known / regions on a canvas sharded over ranks (canvas_group)")
+            if not isinstance(condition_x, (list, tuple)) and (not torch.is_tensor(condition_x) or condition_x.dim() != 4):
+                raise ValueError("condition_x must be [B,3,H,W] (B=1 in the reference, whose tile gather assumes batch 1)")
+            region = check_region_args(region_known, regions, [(int(c.shape[-2]), int(c.shape[-1])) for c in condition_x])
+        if region_log is not None and not isinstance(region_log, list):
+            raise ValueError("region_log: None or a list")
+        region_kw = {} if region is None else dict(region=region, region_skip_tiles=bool(region_skip_tiles), region_log=region_log)
         sampler, eta, step_spacing = check_sampler(sampler, eta, step_spacing)
         threshold = check_percentile(dynamic_threshold)
         if threshold is not None and self.canvas_group is not None:
@@ -732,7 +764,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                                              generation_start_steps, num_sample_steps, start_white_noise, precision, seeds=seeds,
                                              color_fix=color_fix, reference=reference, crop_border=crop_border, back_project=back_project,
                                              guidance=guidance, solver=solver, threshold=threshold, threshold_log=threshold_log,
-                                             joint=joint)
+                                             joint=joint, **region_kw)
             if reference is not None:
                 return (outs[0] if as_list else torch.cat(outs[0], 0)), outs[1]
             return outs if as_list else torch.cat(outs, 0)
@@ -750,7 +782,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                                              generation_start_steps, num_sample_steps, start_white_noise, precision,
                                              color_fix=color_fix, reference=reference, crop_border=crop_border, back_project=back_project,
                                              guidance=guidance, solver=solver, threshold=threshold, threshold_log=threshold_log,
-                                             joint=joint)
+                                             joint=joint, **region_kw)
         joint = _check_joint(joint_guidance, cond_scale, class_cond_scale, class_label, self.canvas_group)
         if tile_size != 256 or tile_stride != 256:
             raise NotImplementedError("tile_size/tile_stride other than 256 are unusable in the reference too "
@@ -801,6 +833,14 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
             img = _host_randn(self.host_generator, 1, 3, hp, wp).to(dev).repeat(batch, 1, 1, 1)   # reference draw #1 (model.py:3311)
         else:
             img = eng.randn_(torch.empty(1, 3, hp, wp, device=dev), self.device_noise_seed, 0).repeat(batch, 1, 1, 1)
+        regional = None
+        if region is not None:              # the start canvas outside R: the known image at the start level
+            regional = _RegionRun(eng, [RegionImage(b * 3 * hp * wp, b * 3 * h * w, hp, wp, top, left, h, w, coords0, coords1, 0,
+                                                    None if region[b] is None else region[b][1]) for b in range(batch)],
+                                  [None if r is None else r[0] for r in region], [(hp, wp)], [self.device_noise_seed],
+                                  num_sample_steps, region_skip_tiles, dev, batch * 3 * hp * wp, batch * 3 * h * w)
+            ls0 = _start_log_snr(generation_start_steps, num_sample_steps, step_spacing)
+            regional.replace(num_sample_steps, float(ls0.sigmoid().sqrt()), float((-ls0).sigmoid().sqrt()), img)
         x_start = img.clone() if with_x0_images or guidance is not None or sampler == "dpmpp2m" or threshold is not None else None
         image_list = [img[:, :, top:bottom, left:right].clone().cpu()] if with_images else None
         x0_image_list = [img[:, :, top:bottom, left:right].clone().cpu()] if with_x0_images else None
@@ -836,8 +876,13 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                 if i % 2 == 1:
                     noise_canvas = _host_randn(self.host_generator, 1, 3, hp, wp).to(dev, non_blocking=True)
             n_step = n_tiles * batch
-            n_lanes = lanes_wanted(n_step, passes, step_tiles, self.step_lanes, precision or self.precision) if self.canvas_group is None else 1
-            if n_lanes > 1:
+            n_lanes = lanes_wanted(n_step, passes, step_tiles, self.step_lanes, precision or self.precision) \
+                if self.canvas_group is None and regional is None else 1
+            if regional is not None:        # the tiles that touch R, without the ring: it lies outside R and is replaced below
+                for first, count, ring in regional.step_ranges(i):
+                    _ddpm_step(eng, i, (first, count, ring), img, cond_canvas, x_start, noise_tiles, noise_canvas, passes, kind, scale,
+                               step_tiles, self.device_noise_seed)
+            elif n_lanes > 1:
                 if lanes is None or len(lanes.engines) != n_lanes:   # further engines: same run geometry, own copies of the condition canvas
                     more = [self.model.engine(precision or self.precision, lane=k) for k in range(1, n_lanes)]
                     for e_ in more:
@@ -862,6 +907,8 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                 guided.step(i, scalars, img, x_start, cond01)
             if history is not None:         # after the guidance: the history holds the corrected predictions
                 history.step(i, img, x_start)
+            if regional is not None:        # last: the canvases outside R are the known image at the step's end level
+                regional.after_step(i, scalars, img, x_start)
             if with_images:
                 image_list.append(img.clone().cpu())
             if with_x0_images:
@@ -875,6 +922,10 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
             color_fix_flat(out, cond01, [b * 3 * h * w for b in range(batch)], [(h, w)] * batch, color_fix)
         if back_project is not None:        # after the colour fix, in place: the image as it will be saved
             back_project_flat(out.view(-1), cond01.view(-1), [b * 3 * h * w for b in range(batch)], [(h, w)] * batch, back_project)
+        if regional is not None:            # the image as saved: outside R it is the known image, bit for bit
+            regional.composite(out)
+            if region_log is not None:
+                region_log.extend(regional.log)
         ret = ((out, image_list, x0_image_list) if with_x0_images else (out, image_list)) if with_images else out
         if reference is not None:           # of the image as saved: after the colour fix
             quality = metrics_flat(out.view(-1), reference[0], [b * 3 * h * w for b in range(batch)], reference[1], [(h, w)] * batch,
@@ -885,7 +936,8 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
     def _tiled_sample_images(self, batch_size, tile_size, conds, class_label, cond_scale, guidance_start_steps,
                              class_cond_scale, class_guidance_start_steps, generation_start_steps, num_sample_steps,
                              start_white_noise, precision, seeds=None, color_fix=None, reference=None, crop_border=4,
-                             back_project=None, guidance=None, solver=None, threshold=None, threshold_log=None, joint=False):
+                             back_project=None, guidance=None, solver=None, threshold=None, threshold_log=None, joint=False,
+                             region=None, region_skip_tiles=True, region_log=None):
         """Mixed-size lock-step (srgd_sampler_begin_images): every image keeps its own canvas, crop box, padding, inner box and
         tile grids; a step's tiles of all images share the U-Net launches.  Noise: the images of one noise class (canvas size)
         see the draw sequence a run of one of them alone sees.  Host noise: the generator state is taken once at entry and
@@ -911,7 +963,11 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
         ``no_clamp``, the run keeps ``x_start`` and makes one batched threshold call for all images after every executed step, before
         the guidance call; ``threshold_log`` (a list or None) receives the [executed steps, images] tensor of s.
 
-        ``joint``: ``joint_guidance`` is active (validated by the caller): steps with both scales current are three-pass steps."""
+        ``joint``: ``joint_guidance`` is active (validated by the caller): steps with both scales current are three-pass steps.
+
+        ``region``: None, or ``check_region_args``'s list of one ``None`` / ``(known image, boxes)`` per image (validated by the
+        caller): the run's ``_RegionRun`` plans the tile ranges of every step over all images - an image without a known image keeps
+        all its tiles - and makes the replacement step after the history call; lanes are off."""
         from .lockstep import plan_mixed_group
         dev = self.device
         if dev.type != "cuda":
@@ -992,6 +1048,16 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
         for p in plans:
             canvas_offs.append(canvas_offs[-1] + 3 * p.Hp * p.Wp)
             cond_offs.append(cond_offs[-1] + 3 * p.H * p.W)
+        regional = None
+        if region is not None:              # the start canvases outside R: the known images at the start level
+            regional = _RegionRun(eng, [RegionImage(canvas_offs[k], cond_offs[k], p.Hp, p.Wp, p.box[1], p.box[0], p.H, p.W, p.coords0,
+                                                    p.coords1, p.noise_class, None if region[k] is None else region[k][1])
+                                        for k, p in enumerate(plans)],
+                                  [None if r is None else r[0] for r in region], classes,
+                                  class_seeds if class_seeds is not None else [self.device_noise_seed] * len(classes),
+                                  num_sample_steps, region_skip_tiles, dev, canvas_offs[-1], cond_offs[-1])
+            ls0 = _start_log_snr(generation_start_steps, num_sample_steps, step_spacing)
+            regional.replace(num_sample_steps, float(ls0.sigmoid().sqrt()), float((-ls0).sigmoid().sqrt()), img)
         if guidance is not None or sampler_name == "dpmpp2m" or threshold is not None:
             x_start = img.clone()
         if threshold is not None:
@@ -1024,8 +1090,12 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                 if i % 2 == 1:
                     noise_canvas = canvas_draw()
             n_step = n_grid[i % 2]
-            n_lanes = lanes_wanted(n_step, passes, step_tiles, self.step_lanes, prec)
-            if n_lanes > 1:
+            n_lanes = lanes_wanted(n_step, passes, step_tiles, self.step_lanes, prec) if regional is None else 1
+            if regional is not None:        # the tiles that touch R (all tiles of an image sampled whole)
+                for first, count, ring in regional.step_ranges(i):
+                    _ddpm_step(eng, i, (first, count, ring), img, cond_canvas, x_start, noise_tiles, noise_canvas, passes, kind, scale,
+                               step_tiles, self.device_noise_seed)
+            elif n_lanes > 1:
                 if lanes is None or len(lanes.engines) != n_lanes:   # further engines: the same mixed run, own condition canvas
                     more = [self.model.engine(prec, lane=k) for k in range(1, n_lanes)]
                     for e_ in more:
@@ -1043,6 +1113,8 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                 guided.step(i, scalars, img, x_start, cond01)
             if history is not None:
                 history.step(i, img, x_start)
+            if regional is not None:
+                regional.after_step(i, scalars, img, x_start)
 
         out = torch.empty(sum(3 * p.H * p.W for p in plans), device=dev, dtype=torch.float32)
         eng.sampler_end(img, out)
@@ -1055,6 +1127,10 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
             color_fix_flat(out, cond01, starts[:-1], [(p.H, p.W) for p in plans], color_fix)
         if back_project is not None:        # after the colour fix, in place: the images as they will be saved
             back_project_flat(out, cond01, starts[:-1], [(p.H, p.W) for p in plans], back_project)
+        if regional is not None:            # the images as saved: outside R the known image, bit for bit
+            regional.composite(out)
+            if region_log is not None:
+                region_log.extend(regional.log)
         quality = None
         if reference is not None:           # on the same flat layout, after the colour fix
             quality = metrics_flat(out, reference[0], starts[:-1], reference[1], [(p.H, p.W) for p in plans], crop_border)
@@ -1258,7 +1334,7 @@ class ConditionalElucidatedDiffusionSR(nn.Module):
                      with_x0_images=False, start_white_noise=True, amp=False, precision=None, seeds=None, color_fix=None,
                      reference=None, crop_border=4, back_project=0, consistency_guidance=0.0, consistency_guidance_start_steps=0,
                      sampler="ddpm", eta=None, step_spacing="time", dynamic_threshold=None, threshold_log=None,
-                     joint_guidance=False):
+                     joint_guidance=False, region_known=None, regions=None, region_skip_tiles=True, region_log=None):
         """Reference model.py:2309-2475 (``start_white_noise`` and ``amp`` are accepted and unused there too; ``precision``
         is the engine-only override of ``self.precision``).  ``seeds`` (per-image noise seeds) is a DDPM-sampler feature and is
         refused here.  ``color_fix``: as in the DDPM wrapper's ``tiled_sample`` - the final image of every image of the batch
@@ -1268,7 +1344,11 @@ class ConditionalElucidatedDiffusionSR(nn.Module):
         ``consistency_guidance``: a DDPM-sampler feature; a non-zero weight is refused here.
         ``sampler``, ``eta``, ``step_spacing``: the DDPM wrapper's few-step samplers; any non-default value is refused here.
         ``dynamic_threshold``: a DDPM-sampler feature; a percentile other than None / 0 is refused here.
-        ``joint_guidance``: a DDPM-sampler feature; both scales are refused here with or without it."""
+        ``joint_guidance``: a DDPM-sampler feature; both scales are refused here with or without it.
+        ``region_known`` / ``regions``: region resampling is a DDPM-sampler feature and is refused here."""
+        if region_known is not None or regions is not None:
+            raise NotImplementedError("region_known / regions are built for the DDPM sampler only: the known image is forward-diffused "
+                                      "with the DDPM schedule's (alpha, sigma) after every step")
         color_fix = check_mode(color_fix)
         back_project = _back_project_steps(back_project, condition_x)
         if check_percentile(dynamic_threshold) is not None:
