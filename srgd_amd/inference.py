@@ -18,6 +18,9 @@ import math
 import os
 import random
 from argparse import ArgumentParser
+from concurrent.futures import ThreadPoolExecutor
+from dataclasses import dataclass, field, replace
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -35,6 +38,7 @@ from .consistency import MIN_SIDE as CONSISTENCY_MIN_SIDE
 from .consistency import consistency_on_device  # noqa: F401  (public: srgd_amd.inference.consistency_on_device)
 from .ensemble import ensemble_on_device  # noqa: F401  (public: srgd_amd.inference.ensemble_on_device)
 from .guidance import MIN_SIDE as GUIDANCE_MIN_SIDE
+from .lockstep import even_step_tiles, plan_lockstep_groups
 from .metrics import KEYS as METRIC_KEYS
 from .metrics import metrics_on_device  # noqa: F401  (public: srgd_amd.inference.metrics_on_device)
 from .model import ConditionalElucidatedDiffusionSR, get_model
@@ -355,6 +359,15 @@ def _split_quality(output, reference):
     return output if reference is not None else (output, None)
 
 
+def _header_size(path):
+    """``(width, height)`` from an image file's header, or None where the file cannot be read as an image."""
+    try:
+        with Image.open(path) as im:
+            return im.size
+    except (IOError, SyntaxError):
+        return None
+
+
 def reference_problems(file_names, reference_dir, scale=4, crop_border=4):
     """``--reference_dir`` pre-flight: one line per input file whose reference ``reference_dir/<same name>`` is missing, unreadable,
     not exactly ``scale`` times the input's size, or too small for an 11x11 window inside the crop.  Only image headers are read."""
@@ -362,20 +375,17 @@ def reference_problems(file_names, reference_dir, scale=4, crop_border=4):
     for f in file_names:
         name = os.path.basename(f)
         ref = os.path.join(reference_dir, name)
-        try:
-            with Image.open(f) as im:
-                w, h = im.size
-        except (IOError, SyntaxError):
+        size = _header_size(f)
+        if size is None:
             continue                                     # not an image: the sampling loop reports and skips it
         if not os.path.isfile(ref):
             problems.append(f"{name}: reference {ref} is missing")
             continue
-        try:
-            with Image.open(ref) as im:
-                rw, rh = im.size
-        except (IOError, SyntaxError):
+        ref_size = _header_size(ref)
+        if ref_size is None:
             problems.append(f"{name}: reference {ref} cannot be read as an image")
             continue
+        (w, h), (rw, rh) = size, ref_size
         if (rw, rh) != (w * scale, h * scale):
             problems.append(f"{name}: reference is {rw}x{rh}, x{scale} of the {w}x{h} input is {w * scale}x{h * scale}")
         elif min(rw, rh) - 2 * crop_border < 11:
@@ -427,23 +437,20 @@ def region_known_problems(file_names, known_dir, regions, scale=4, samples=1):
     problems = []
     for f in file_names:
         name = os.path.basename(f)
-        try:
-            with Image.open(f) as im:
-                w, h = im.size
-        except (IOError, SyntaxError):
+        size = _header_size(f)
+        if size is None:
             continue                                     # not an image: the sampling loop reports and skips it
+        w, h = size
         for known in sorted({region_known_path(known_dir, f, k, samples) for k in range(samples)}):
             if not os.path.isfile(known):
                 problems.append(f"{name}: known output {known} is missing")
                 continue
-            try:
-                with Image.open(known) as im:
-                    kw_, kh = im.size
-            except (IOError, SyntaxError):
+            known_size = _header_size(known)
+            if known_size is None:
                 problems.append(f"{name}: known output {known} cannot be read as an image")
                 continue
-            if (kw_, kh) != (w * scale, h * scale):
-                problems.append(f"{name}: known output {os.path.basename(known)} is {kw_}x{kh}, x{scale} of the {w}x{h} input is "
+            if known_size != (w * scale, h * scale):
+                problems.append(f"{name}: known output {os.path.basename(known)} is {known_size[0]}x{known_size[1]}, x{scale} of the {w}x{h} input is "
                                 f"{w * scale}x{h * scale}")
         for (t, l, bh, bw) in regions:
             if t + bh > h * scale or l + bw > w * scale:
@@ -471,9 +478,9 @@ def load_reference(path):
         return torch.from_numpy(np.asarray(im.convert("RGB"), dtype=np.uint8).copy())
 
 
-def mean_record(records):
-    """Key-wise arithmetic mean of metric dicts (PSNR averaged in dB, the SR convention); inf and NaN propagate."""
-    return {k: sum(r[k] for r in records) / len(records) for k in METRIC_KEYS}
+def mean_record(records, keys=METRIC_KEYS):
+    """Arithmetic mean of metric dicts, key by key of ``keys`` (PSNR averaged in dB, the SR convention); inf and NaN propagate."""
+    return {k: sum(r[k] for r in records) / len(records) for k in keys}
 
 
 def _json_record(record):
@@ -481,23 +488,29 @@ def _json_record(record):
     return {k: (v if math.isfinite(v) else ("nan" if math.isnan(v) else ("inf" if v > 0 else "-inf"))) for k, v in record.items()}
 
 
+def _records_document(head, file_records, samples, keys, ensemble):
+    """The layout ``metrics.json`` and ``consistency.json`` share: ``head``, then ``"files"``, ``"images"`` (with --samples only),
+    ``"mean"`` and, for a non-empty ``ensemble``, ``"ensemble"`` / ``"ensemble_mean"``; every mean is taken over ``keys``."""
+    per_image = {}
+    for name, _, rec in file_records:
+        per_image.setdefault(name, []).append(rec)
+    image_means = {name: mean_record(recs, keys) for name, recs in per_image.items()}
+    doc = dict(head, files={written: _json_record(rec) for _, written, rec in file_records})
+    if samples > 1:
+        doc["images"] = {name: _json_record(rec) for name, rec in image_means.items()}
+    doc["mean"] = _json_record(mean_record(list(image_means.values()), keys))
+    if ensemble:
+        doc["ensemble"] = {name: _json_record(rec) for name, rec in ensemble}
+        doc["ensemble_mean"] = _json_record(mean_record([rec for _, rec in ensemble], keys))
+    return doc
+
+
 def metrics_document(file_records, samples, crop_border, ensemble=None):
     """``metrics.json``: ``file_records`` = ``[(input file name, written file name, metric dict)]`` in run order ->
     ``{"crop_border", "files": {written file: record}, "images": {input file: mean over its samples} (with --samples only),
     "mean": mean over the images}``.  ``ensemble`` (``--ensemble``): ``[(input file name, metric dict of its mean image)]`` adds
     ``"ensemble": {input file: record}`` and ``"ensemble_mean"``, the mean over those; None or empty adds nothing."""
-    per_image = {}
-    for name, _, rec in file_records:
-        per_image.setdefault(name, []).append(rec)
-    image_means = {name: mean_record(recs) for name, recs in per_image.items()}
-    doc = {"crop_border": crop_border, "files": {written: _json_record(rec) for _, written, rec in file_records}}
-    if samples > 1:
-        doc["images"] = {name: _json_record(rec) for name, rec in image_means.items()}
-    doc["mean"] = _json_record(mean_record(list(image_means.values())))
-    if ensemble:
-        doc["ensemble"] = {name: _json_record(rec) for name, rec in ensemble}
-        doc["ensemble_mean"] = _json_record(mean_record([rec for _, rec in ensemble]))
-    return doc
+    return _records_document({"crop_border": crop_border}, file_records, samples, METRIC_KEYS, ensemble)
 
 
 def consistency_document(file_records, samples, ensemble=None):
@@ -506,19 +519,7 @@ def consistency_document(file_records, samples, ensemble=None):
     over the images}``; PSNR is averaged in dB as in ``metrics.json``.  ``ensemble`` (``--ensemble``): ``[(input file name, record of
     its mean image)]`` adds ``"ensemble": {input file: record}`` and ``"ensemble_mean"``, the mean over those; None or empty adds
     nothing.  Non-finite values are written as strings (``_json_record``)."""
-    mean = lambda recs: {k: sum(r[k] for r in recs) / len(recs) for k in CONSISTENCY_KEYS}       # noqa: E731
-    per_image = {}
-    for name, _, rec in file_records:
-        per_image.setdefault(name, []).append(rec)
-    image_means = {name: mean(recs) for name, recs in per_image.items()}
-    doc = {"files": {written: _json_record(rec) for _, written, rec in file_records}}
-    if samples > 1:
-        doc["images"] = {name: _json_record(rec) for name, rec in image_means.items()}
-    doc["mean"] = _json_record(mean(list(image_means.values())))
-    if ensemble:
-        doc["ensemble"] = {name: _json_record(rec) for name, rec in ensemble}
-        doc["ensemble_mean"] = _json_record(mean([rec for _, rec in ensemble]))
-    return doc
+    return _records_document({}, file_records, samples, CONSISTENCY_KEYS, ensemble)
 
 
 def ensemble_output_names(file_name):
@@ -606,6 +607,33 @@ def unit_tensor_to_pil_on_device(t: torch.Tensor) -> Image.Image:
     return Image.fromarray(unit_tensor_to_u8_on_device(t).cpu().numpy(), "RGB")
 
 
+def _tiled_sample_kw(opts):
+    """``tiled_sample``'s keywords out of the arguments of a ``sr_target_image*`` function (its ``locals()``, taken before it binds
+    anything else; a function that lacks one of them fails on its first call): the reference's own as they are, an engine extension
+    only where it is not at its default - so a run without a flag makes the call it made before the flag existed."""
+    own = ("cond_scale", "guidance_start_steps", "class_cond_scale", "class_guidance_start_steps", "generation_start_steps", "num_sample_steps")
+    return {**{k: opts[k] for k in own}, "amp": opts["enable_amp"], **_color_fix_kw(opts["color_fix"]),
+            **_reference_kw(opts["reference"], opts["crop_border"]), **_back_project_kw(opts["back_project"]),
+            **_guidance_kw(opts["consistency_guidance"], opts["consistency_guidance_start_steps"]),
+            **_sampler_kw(opts["sampler"], opts["eta"], opts["step_spacing"]), **_threshold_kw(opts["dynamic_threshold"]),
+            **_joint_kw(opts["joint_guidance"]), **_region_kw(opts["region_known"], opts["regions"])}
+
+
+def _sample_group(sr_model, condition_x, sizes, label, batch_size, seeds, opts):
+    """The one body of the four ``sr_target_image*`` functions: the reference's per-image reseed, one ``tiled_sample`` call on
+    ``condition_x`` (a ``[B,3,H,W]`` tensor or a list of ``[1,3,H,W]`` tensors; ``seeds``: None or one noise seed per image) and the
+    outputs as PIL images, each x4 of its entry of ``sizes`` -> ``(images, metric dicts or None)``."""
+    seed_everything(opts["seed"])
+    sr_model.device_noise_seed = opts["seed"]
+    with torch.inference_mode():
+        output = sr_model.tiled_sample(batch_size=batch_size, condition_x=condition_x, class_label=label,
+                                       **({} if seeds is None else {"seeds": list(seeds)}), **_tiled_sample_kw(opts))
+    output, quality = _split_quality(output, opts["reference"])
+    outs = [unit_tensor_to_pil_on_device(o[0] if o.dim() == 4 else o) for o in output]
+    assert len(outs) == len(sizes) and all(o.size == (w * 4, h * 4) for o, (w, h) in zip(outs, sizes))
+    return outs, quality
+
+
 def sr_target_image(image, sr_model, scale=4, batch_size=8, test_label=2, cond_scale=1.0, guidance_start_steps=0,
                     class_cond_scale=1.0, class_guidance_start_steps=0, generation_start_steps=0,
                     num_sample_steps=250, enable_amp=False, interpolation="bicubic", seed=71, color_fix=None, reference=None,
@@ -618,26 +646,11 @@ def sr_target_image(image, sr_model, scale=4, batch_size=8, test_label=2, cond_s
     ``region_known`` / ``regions`` (engine extension; here and in the three group forms below): the finished output as a fp32
     ``[1,3,4h,4w]`` tensor in [0, 1] (a list of one per image in the group forms) and the boxes to sample again
     (``tiled_sample(region_known=..., regions=...)``); without them the keywords are not passed at all."""
-    width, height = image.size
+    opts = locals()
     # the reference maps 'lanczos' to bicubic too (inference.py:66-69)
     condition_x = upsample_bicubic_on_device(image, scale, sr_model.device)
     label = torch.LongTensor([test_label]).to(sr_model.device) if test_label is not None else None
-    seed_everything(seed)
-    sr_model.device_noise_seed = seed
-    with torch.inference_mode():
-        output = sr_model.tiled_sample(batch_size=batch_size, condition_x=condition_x, class_label=label,
-                                       cond_scale=cond_scale, guidance_start_steps=guidance_start_steps,
-                                       class_cond_scale=class_cond_scale,
-                                       class_guidance_start_steps=class_guidance_start_steps,
-                                       generation_start_steps=generation_start_steps,
-                                       num_sample_steps=num_sample_steps, amp=enable_amp, **_color_fix_kw(color_fix),
-                                       **_reference_kw(reference, crop_border), **_back_project_kw(back_project),
-                                       **_guidance_kw(consistency_guidance, consistency_guidance_start_steps),
-                                       **_sampler_kw(sampler, eta, step_spacing), **_threshold_kw(dynamic_threshold),
-                                       **_joint_kw(joint_guidance), **_region_kw(region_known, regions))
-    output, quality = _split_quality(output, reference)
-    sr_img = unit_tensor_to_pil_on_device(output[0])
-    assert sr_img.size == (width * 4, height * 4)
+    (sr_img,), quality = _sample_group(sr_model, condition_x, [image.size], label, batch_size, None, opts)
     return sr_img if reference is None else (sr_img, quality)
 
 
@@ -651,26 +664,11 @@ def sr_target_images(images, sr_model, scale=4, batch_size=8, test_label=2, cond
     ``[B,3,H,W]`` condition.  Each image is sampled exactly as it would be alone after the reference's per-image
     ``seed_everything(seed)`` (inference.py:73) - bit-identical outputs - while their tiles fill the U-Net launches.
     ``test_label`` may be a sequence of one label per image."""
+    opts = locals()
     assert len({im.size for im in images}) == 1, "lock-step images must have the same size"
-    width, height = images[0].size
     condition_x = torch.cat([upsample_bicubic_on_device(im, scale, sr_model.device) for im in images], 0)
     label = _label_tensor(test_label, len(images), sr_model.device)
-    seed_everything(seed)
-    sr_model.device_noise_seed = seed
-    with torch.inference_mode():
-        output = sr_model.tiled_sample(batch_size=batch_size * len(images), condition_x=condition_x, class_label=label,
-                                       cond_scale=cond_scale, guidance_start_steps=guidance_start_steps,
-                                       class_cond_scale=class_cond_scale,
-                                       class_guidance_start_steps=class_guidance_start_steps,
-                                       generation_start_steps=generation_start_steps,
-                                       num_sample_steps=num_sample_steps, amp=enable_amp, **_color_fix_kw(color_fix),
-                                       **_reference_kw(reference, crop_border), **_back_project_kw(back_project),
-                                       **_guidance_kw(consistency_guidance, consistency_guidance_start_steps),
-                                       **_sampler_kw(sampler, eta, step_spacing), **_threshold_kw(dynamic_threshold),
-                                       **_joint_kw(joint_guidance), **_region_kw(region_known, regions))
-    output, quality = _split_quality(output, reference)
-    outs = [unit_tensor_to_pil_on_device(o) for o in output]
-    assert all(o.size == (width * 4, height * 4) for o in outs)
+    outs, quality = _sample_group(sr_model, condition_x, [im.size for im in images], label, batch_size * len(images), None, opts)
     return outs if reference is None else (outs, quality)
 
 
@@ -683,24 +681,10 @@ def sr_target_images_mixed(images, sr_model, scale=4, batch_size=8, test_label=2
     """``sr_target_image`` for several images of any sizes in lock-step (engine extension): one ``tiled_sample`` call on a list
     of conditions.  Each image comes out bit-identical to its own ``sr_target_image`` run (with its own label where
     ``test_label`` is a sequence of one label per image)."""
+    opts = locals()
     conds = [upsample_bicubic_on_device(im, scale, sr_model.device) for im in images]
     label = _label_tensor(test_label, len(images), sr_model.device)
-    seed_everything(seed)
-    sr_model.device_noise_seed = seed
-    with torch.inference_mode():
-        output = sr_model.tiled_sample(batch_size=batch_size * len(images), condition_x=conds, class_label=label,
-                                       cond_scale=cond_scale, guidance_start_steps=guidance_start_steps,
-                                       class_cond_scale=class_cond_scale,
-                                       class_guidance_start_steps=class_guidance_start_steps,
-                                       generation_start_steps=generation_start_steps,
-                                       num_sample_steps=num_sample_steps, amp=enable_amp, **_color_fix_kw(color_fix),
-                                       **_reference_kw(reference, crop_border), **_back_project_kw(back_project),
-                                       **_guidance_kw(consistency_guidance, consistency_guidance_start_steps),
-                                       **_sampler_kw(sampler, eta, step_spacing), **_threshold_kw(dynamic_threshold),
-                                       **_joint_kw(joint_guidance), **_region_kw(region_known, regions))
-    output, quality = _split_quality(output, reference)
-    outs = [unit_tensor_to_pil_on_device(o[0]) for o in output]
-    assert all(o.size == (im.size[0] * 4, im.size[1] * 4) for o, im in zip(outs, images))
+    outs, quality = _sample_group(sr_model, conds, [im.size for im in images], label, batch_size * len(images), None, opts)
     return outs if reference is None else (outs, quality)
 
 
@@ -713,27 +697,14 @@ def sr_target_images_seeded(images, seeds, sr_model, scale=4, batch_size=8, test
     """``sr_target_images_mixed`` with one noise seed per image (engine extension, ``tiled_sample(seeds=...)``): image i comes out
     bit-identical to its own ``sr_target_image`` run with ``seed=seeds[i]``; an image may appear several times with different
     seeds (each PIL image is upsampled once).  ``seed`` seeds the process as the other entry points do and is not a noise seed."""
+    opts = locals()
     conds = {}
     for im in images:
         if id(im) not in conds:
             conds[id(im)] = upsample_bicubic_on_device(im, scale, sr_model.device)
     label = _label_tensor(test_label, len(images), sr_model.device)
-    seed_everything(seed)
-    sr_model.device_noise_seed = seed
-    with torch.inference_mode():
-        output = sr_model.tiled_sample(batch_size=batch_size * len(images), condition_x=[conds[id(im)] for im in images],
-                                       class_label=label, cond_scale=cond_scale, guidance_start_steps=guidance_start_steps,
-                                       class_cond_scale=class_cond_scale,
-                                       class_guidance_start_steps=class_guidance_start_steps,
-                                       generation_start_steps=generation_start_steps,
-                                       num_sample_steps=num_sample_steps, amp=enable_amp, seeds=list(seeds),
-                                       **_color_fix_kw(color_fix), **_reference_kw(reference, crop_border), **_back_project_kw(back_project),
-                                       **_guidance_kw(consistency_guidance, consistency_guidance_start_steps),
-                                       **_sampler_kw(sampler, eta, step_spacing), **_threshold_kw(dynamic_threshold),
-                                       **_joint_kw(joint_guidance), **_region_kw(region_known, regions))
-    output, quality = _split_quality(output, reference)
-    outs = [unit_tensor_to_pil_on_device(o[0]) for o in output]
-    assert all(o.size == (im.size[0] * 4, im.size[1] * 4) for o, im in zip(outs, images))
+    outs, quality = _sample_group(sr_model, [conds[id(im)] for im in images], [im.size for im in images], label,
+                                  batch_size * len(images), seeds, opts)
     return outs if reference is None else (outs, quality)
 
 
@@ -769,6 +740,283 @@ def try_open_image_with_alpha(image_path):
         return None, None
 
 
+def _u8_to_pil(t, mode="RGB"):
+    """A uint8 ``[H,W,C]`` tensor, wherever it lives, as the PIL image that is saved."""
+    return Image.fromarray(t.cpu().numpy(), mode)
+
+
+def _upload_once(run, objects, as_tensor):
+    """``objects`` as tensors on the model's device, one upload per distinct object: the K samples of a file share input and plane."""
+    placed = {}
+    for o in objects:
+        if id(o) not in placed:
+            placed[id(o)] = run.place(as_tensor(o))
+    return [placed[id(o)] for o in objects]
+
+
+@dataclass
+class _Entry:
+    """One image of a lock-step group: a sample of an input file or, under ``self_ensemble``, one orientation of it."""
+    image: Image.Image                                   # what is sampled: the opened input (after alpha_bleed) or one orientation of it
+    save_path: str
+    label: object                                        # class label or None
+    seed: int                                            # noise seed, the run's seed + k
+    k: int                                               # sample index of --samples
+    reference: object                                    # --reference_dir: future of the decoded ground truth, or None
+    name: str                                            # base name of the input file
+    file_name: str                                       # the input file as listed
+    plane: object                                        # --alpha keep: the input's alpha plane, uint8 [h,w], or None
+    op: int                                              # --self_ensemble: the dihedral op that made `image` of `original`
+    original: Image.Image                                # the opened input (after alpha_bleed)
+    known: object                                        # --region_known_dir: future of the decoded known output, or None
+
+
+@dataclass
+class _Run:
+    """What one ``batch_sr_target_images`` call carries from group to group."""
+    sr_model: object
+    pool: object                                         # two workers: PNG encoding and decoding overlap the next group's sampling
+    opt: SimpleNamespace                                 # the resolved options; kw: the keywords every sr_target_image* call gets
+    device: object                                       # of the model; None for the stubs of the CPU tests
+    pending: list = field(default_factory=list)          # the entries of the current lock-step group
+    saves: list = field(default_factory=list)            # futures of the PNG writers
+    file_records: list = field(default_factory=list)     # --reference_dir: (input file name, written file name, metric dict)
+    ens_open: dict = field(default_factory=dict)         # --ensemble: input file -> [its K samples (PIL image of this run) or None (on disk), samples still to draw]
+    ens_ready: list = field(default_factory=list)        # files whose last sample is handled
+    ens_records: list = field(default_factory=list)      # ensemble.json rows
+    ens_quality: list = field(default_factory=list)      # metrics.json rows of the mean images
+    cons_records: list = field(default_factory=list)     # --consistency: consistency.json rows of the files written
+    cons_ensemble: list = field(default_factory=list)    # and of the mean images
+    held: dict = field(default_factory=dict)             # --self_ensemble: save path -> [(entry, output)] of the variants sampled so far
+
+    def place(self, t):
+        """``t`` on the model's device; as it is where the model has none."""
+        return t if self.device is None else t.to(self.device)
+
+
+def _queue(run, entry):
+    """Adds an entry to the pending group and flushes as the grouping asks, in this order: an unlabelled image does not join a
+    labelled group; with ``lockstep_tiles`` the image that would push the group over the tile budget (``plan_lockstep_groups``) closes
+    it; otherwise a full group or an image of another size closes it, and the group that the entry fills is sampled at once."""
+    opt = run.opt
+    if run.pending and (entry.label is None) != (run.pending[0].label is None):
+        _flush(run)
+    if opt.lockstep_tiles is not None:
+        hr = [(h * opt.scale, w * opt.scale) for (w, h) in [e.image.size for e in run.pending] + [entry.image.size]]
+        if len(plan_lockstep_groups(hr, opt.lockstep_tiles)) > 1:
+            _flush(run)
+        run.pending.append(entry)
+        return
+    if run.pending and (len(run.pending) >= max(1, opt.lockstep) or run.pending[0].image.size != entry.image.size):
+        _flush(run)
+    run.pending.append(entry)
+    if len(run.pending) >= max(1, opt.lockstep):
+        _flush(run)
+
+
+def _flush(run):
+    """Samples the pending group and takes it through the stages, in this order: ``_sample_entries``, ``_merge_self_ensemble`` (only
+    the entries whose last orientation arrived go on), ``_measure_consistency``, ``_outscale``, ``_attach_alpha``, ``_save`` and
+    ``_flush_ensembles``."""
+    if not run.pending:
+        return
+    entries = list(run.pending)
+    outs = _sample_entries(run, entries)
+    run.pending.clear()
+    if run.opt.self_ensemble > 1:
+        entries, outs = _merge_self_ensemble(run, entries, outs)
+        if not entries:
+            return
+    if run.opt.consistency:                              # the images as saved against the inputs the group was given
+        run.cons_records.extend(_measure_consistency(run, [(e.name, os.path.basename(e.save_path)) for e in entries],
+                                                     [pil_to_u8_tensor(sr) for sr in outs], [e.image for e in entries]))
+    if run.opt.outscale is not None:
+        outs = _outscale(run, entries, outs)
+    outs = _attach_alpha(run, entries, outs)
+    _save(run, entries, outs)
+    if run.opt.ensemble:
+        _flush_ensembles(run)
+
+
+def _sample_entries(run, entries):
+    """Picks and calls the sampler: one entry is a solo run with its seed (``sr_target_image``: what every image of a group is
+    identical to), entries with more than one distinct noise seed go to ``sr_target_images_seeded``, a ``lockstep_tiles`` group to
+    ``sr_target_images_mixed``, any other to ``sr_target_images`` - each with ``opt.kw``, in which a keyword at its default is absent.
+    ``reference_dir``: the decoded references (one future per input file) are handed on and the numbers of every file join
+    ``file_records`` - not under ``self_ensemble``, where the merged image is measured.  ``regions``: the decoded known outputs (one
+    future per known file) and the boxes are handed on."""
+    opt, sr_model = run.opt, run.sr_model
+    images, labels, seeds = [e.image for e in entries], [e.label for e in entries], [e.seed for e in entries]
+    if opt.lockstep_tiles is not None:
+        tiles = sum(even_step_tiles(h * opt.scale, w * opt.scale) for (w, h) in [im.size for im in images])
+        print(f"lock-step group: {len(entries)} images, {tiles} tiles per even step")
+    one_label = labels[0] if len(set(labels)) == 1 else labels
+    extra = {}
+    if opt.reference_dir is not None and opt.self_ensemble == 1:
+        extra.update(reference=[e.reference.result() for e in entries], crop_border=opt.crop_border)
+    if opt.regions is not None:
+        extra.update(region_known=[e.known.result() for e in entries], regions=opt.regions)
+    if len(entries) == 1:
+        solo = {k: v[0] if k in ("reference", "region_known") else v for k, v in extra.items()}
+        outs = sr_target_image(images[0], sr_model, test_label=labels[0], **dict(opt.kw, seed=seeds[0]), **solo)
+        outs = ([outs[0]], outs[1]) if "reference" in extra else [outs]
+    elif len(set(seeds)) > 1:
+        outs = sr_target_images_seeded(images, seeds, sr_model, test_label=one_label, **opt.kw, **extra)
+    elif opt.lockstep_tiles is not None:
+        outs = sr_target_images_mixed(images, sr_model, test_label=one_label, **dict(opt.kw, seed=seeds[0]), **extra)
+    else:
+        outs = sr_target_images(images, sr_model, test_label=one_label, **dict(opt.kw, seed=seeds[0]), **extra)
+    if "reference" in extra:
+        outs, quality = outs
+        run.file_records.extend((e.name, os.path.basename(e.save_path), q) for e, q in zip(entries, quality))
+    return outs
+
+
+def _merge_self_ensemble(run, entries, outs):
+    """``self_ensemble`` N > 1: the outputs of an entry's orientations are held, across ``_flush`` calls where they straddle them,
+    until the N-th arrives; the entries completed in one ``_flush`` are merged in one ``self_ensemble_on_device`` call (every output
+    turned back, the N averaged, halves up) and, with ``reference_dir``, measured in one ``metrics_on_device`` call on ``mean01``.
+    Returns what every later stage acts on: the completed entries, each with its original input as its image, and the merged images."""
+    opt = run.opt
+    for e, sr in zip(entries, outs):
+        run.held.setdefault(e.save_path, []).append((e, sr))
+    complete = [run.held.pop(path) for path in [path for path, parts in run.held.items() if len(parts) == opt.self_ensemble]]
+    if not complete:
+        return [], []
+    merged = self_ensemble_on_device([[(run.place(pil_to_u8_tensor(sr)), e.op) for e, sr in parts] for parts in complete],
+                                     return_mean01=opt.reference_dir is not None)
+    entries = [replace(parts[0][0], image=parts[0][0].original) for parts in complete]
+    if opt.reference_dir is not None:
+        quality = metrics_on_device([m[1] for m in merged], [e.reference.result() for e in entries], opt.crop_border)
+        run.file_records.extend((e.name, os.path.basename(e.save_path), q) for e, q in zip(entries, quality))
+        merged = [m[0] for m in merged]
+    return entries, [_u8_to_pil(m) for m in merged]
+
+
+def _measure_consistency(run, tags, outputs, inputs):
+    """One batched ``consistency_on_device`` call (srgd_amd.consistency: the output reduced x4 by Pillow's bicubic against its
+    input): ``outputs`` uint8 [4h,4w,3] tensors, ``inputs`` the PIL inputs, ``tags`` a tuple per image that ends in its name ->
+    ``[(*tag, record)]`` of the images large enough; a smaller one is reported and left out."""
+    keep = []
+    for i, im in enumerate(inputs):
+        if min(im.size) < CONSISTENCY_MIN_SIDE:
+            print(f"consistency: {tags[i][-1]} is {im.size[0]}x{im.size[1]}, smaller than {CONSISTENCY_MIN_SIDE} pixels on a side: "
+                  "left out")
+        else:
+            keep.append(i)
+    if not keep:
+        return []
+    lows = _upload_once(run, [inputs[i] for i in keep], pil_to_u8_tensor)
+    recs = consistency_on_device([run.place(outputs[i]) for i in keep], lows)
+    return [(*tags[i], rec) for i, rec in zip(keep, recs)]
+
+
+def _outscale(run, entries, outs):
+    """``outscale`` S other than None / 4: the images as they would have been saved, after everything above has been measured on them,
+    go through one batched ``resize_on_device`` call (srgd_amd.resize: Pillow's ``Image.resize`` bit for bit) to ``outscale_size``."""
+    from .resize import resize_on_device
+    resized = resize_on_device([run.place(pil_to_u8_tensor(sr)) for sr in outs],
+                               [outscale_size(e.image.size[1], e.image.size[0], run.opt.outscale) for e in entries], run.opt.outscale_filter)
+    return [_u8_to_pil(t) for t in resized]
+
+
+def _attach_alpha(run, entries, outs):
+    """``alpha="keep"``: the outputs whose input had an alpha plane get it in one batched ``attach_alpha_on_device`` call
+    (srgd_amd.alpha) and leave as RGBA images; the others, and every output of a run without planes, stay as they are."""
+    with_alpha = [i for i, e in enumerate(entries) if e.plane is not None]
+    if not with_alpha:
+        return outs
+    planes = _upload_once(run, [entries[i].plane for i in with_alpha], torch.from_numpy)
+    rgba = attach_alpha_on_device([run.place(pil_to_u8_tensor(outs[i])) for i in with_alpha], planes, run.opt.scale, run.opt.outscale_filter)
+    outs = list(outs)
+    for i, t in zip(with_alpha, rgba):
+        outs[i] = _u8_to_pil(t, "RGBA")
+    return outs
+
+
+def _save(run, entries, outs):
+    """Hands every image to the writer pool and, with ``ensemble``, files it as sample ``k`` of its input; an input whose last sample
+    this was is ready for ``_flush_ensembles``."""
+    for e, sr in zip(entries, outs):
+        run.saves.append(run.pool.submit(sr.save, e.save_path))
+        if e.file_name in run.ens_open:
+            state = run.ens_open[e.file_name]
+            state[0][e.k] = sr
+            state[1] -= 1
+            if state[1] == 0:
+                run.ens_ready.append(e.file_name)
+
+
+def _plan_ensembles(run, file_names):
+    """``ensemble``: what is left to do per input file.  A file whose samples, mean and spread all exist is skipped; one whose samples
+    are all on disk - found by the skip-if-exists rule - is ready at once."""
+    opt = run.opt
+    for filename in file_names:
+        paths = [os.path.join(opt.output_dir, sample_output_name(filename, k)) for k in range(opt.samples)]
+        missing = sum(not os.path.exists(p) for p in paths)
+        if missing == 0 and all(os.path.exists(os.path.join(opt.output_dir, n)) for n in ensemble_output_names(filename)):
+            continue
+        if missing == 0:
+            run.ens_ready.append(filename)
+        run.ens_open[filename] = [[None] * opt.samples, missing]
+
+
+def _flush_ensembles(run):
+    """``ensemble``: one batched ``ensemble_on_device`` call (srgd_amd.ensemble) for the files completed since the last one; their mean
+    images and spread maps go to ``<name>_out_mean.png`` / ``<name>_out_std.png``.  Samples of this run are the PIL images the samplers
+    returned, samples found on disk are decoded on the writer pool (a resumed run writes what an uninterrupted one does); one of another
+    size than x``scale`` of the input is reported and that file left out.  ``reference_dir`` and ``consistency`` measure the mean images."""
+    opt, pool = run.opt, run.pool
+    todo = []                                            # (file name, futures / tensors of its K samples)
+    for filename in run.ens_ready:
+        drawn = run.ens_open.pop(filename)[0]
+        todo.append((filename, [pool.submit(load_reference, os.path.join(opt.output_dir, sample_output_name(filename, k)))
+                                if sr is None else pil_to_u8_tensor(sr) for k, sr in enumerate(drawn)]))
+    run.ens_ready.clear()
+    names, stacks = [], []
+    for filename, parts in todo:
+        size = _header_size(filename)
+        if size is None:
+            continue                                     # not an image: the sampling loop has reported it
+        want = (size[1] * opt.scale, size[0] * opt.scale, 3)
+        try:
+            parts = [part if torch.is_tensor(part) else part.result() for part in parts]
+        except (IOError, SyntaxError) as err:
+            print(f"ensemble: a sample of {os.path.basename(filename)} cannot be read ({err}): no ensemble for this file")
+            continue
+        wrong = [k for k, part in enumerate(parts) if tuple(part.shape) != want]
+        if wrong:
+            for k in wrong:
+                print(f"ensemble: {sample_output_name(filename, k)} is {parts[k].shape[1]}x{parts[k].shape[0]}, x{opt.scale} of the "
+                      f"input is {want[1]}x{want[0]}: no ensemble for {os.path.basename(filename)}")
+            continue
+        names.append(filename)
+        stacks.append(torch.stack(parts))
+    if not names:
+        return
+    results = ensemble_on_device([run.place(st) for st in stacks], return_mean01=opt.reference_dir is not None)
+    if opt.reference_dir is not None:
+        refs = [pool.submit(load_reference, os.path.join(opt.reference_dir, os.path.basename(f))) for f in names]
+        quality = metrics_on_device([r[3] for r in results], [f.result() for f in refs], opt.crop_border)
+        run.ens_quality.extend((os.path.basename(f), q) for f, q in zip(names, quality))
+    if opt.consistency:                                  # the uint8 mean images against their inputs
+        lows = [try_open_image(f) for f in names]
+        have = [i for i, im in enumerate(lows) if im is not None]
+        run.cons_ensemble.extend(_measure_consistency(run, [(os.path.basename(names[i]),) for i in have], [results[i][0] for i in have],
+                                                      [lows[i] for i in have]))
+    for filename, res in zip(names, results):
+        mean_name, std_name = ensemble_output_names(filename)
+        for arr, out_name in ((res[0], mean_name), (res[1], std_name)):
+            run.saves.append(pool.submit(_u8_to_pil(arr).save, os.path.join(opt.output_dir, out_name)))
+        run.ens_records.append((os.path.basename(filename), mean_name, std_name, res[2]))
+
+
+def _write_document(path, doc):
+    with open(path, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+
+
 def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=8, test_label=2, cond_scale=1.0,
                            guidance_start_steps=0, class_cond_scale=1.0, class_guidance_start_steps=0,
                            generation_start_steps=0, num_sample_steps=250, start_index=0, end_index=None,
@@ -778,76 +1026,18 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
                            consistency_guidance=0.0, consistency_guidance_start_steps=0, sampler="ddpm", eta=None,
                            step_spacing="time", outscale=None, outscale_filter="bicubic", alpha="drop", alpha_bleed=0,
                            dynamic_threshold=0.0, self_ensemble=1, joint_guidance=False, region_known_dir=None, regions=None):
-    """``region_known_dir`` / ``regions`` (``--region_known_dir DIR``, ``--region T,L,H,W``): every planned entry's known file
-    (``region_known_path``: ``DIR/<name>_out.png``, its own ``_out_s<k>.png`` under ``samples`` where it exists) is checked first
-    (``check_region_known``), decoded on the writer pool while earlier groups sample, and handed with the boxes to whichever
-    ``sr_target_image*`` function samples the group (``tiled_sample(region_known=..., regions=...)``); everything below acts on the
-    composited image.  Without them nothing is checked, decoded or passed.  One without the other, or either together with
-    ``self_ensemble`` > 1 or ``ensemble``: ``ValueError`` before anything is sampled.
-    ``joint_guidance`` (``--joint_guidance``): handed by keyword to whichever ``sr_target_image*`` function samples a group only
-    where it is set (``tiled_sample(joint_guidance=True)``: both guidance scales in one three-pass step).
-    ``self_ensemble`` (``--self_ensemble N``, N in 1, 2, 4, 8): with N > 1 every planned entry (file, sample seed) becomes N
-    consecutive entries of the grouping, one per op of ``srgd_amd.selfens.OPS[N]`` in that order, all with the entry's seed and label;
-    their inputs are ``dihedral_on_device`` of the opened input (after ``alpha_bleed``), transformed once per opened file.  The
-    variants are ordinary images of their lock-step group (with neither lock-step argument they group as ``lockstep = N * samples``;
-    a transposed half of another size is split off by the flush at a size change), so ``color_fix``, ``back_project``,
-    ``consistency_guidance`` and ``dynamic_threshold`` act on each variant against its own transformed input; ``reference=`` is not
-    handed to the ``sr_target_image*`` functions.  The 8-bit outputs of an entry's variants are held, across ``flush()`` calls where
-    they straddle them, until the N-th arrives; all entries completed in one ``flush()`` are merged in one
-    ``self_ensemble_on_device`` call (every output turned back, the N averaged, halves up), and everything below - ``reference_dir``
-    (``metrics_on_device`` on the merged image's ``mean01``), ``consistency`` against the original input, ``outscale``, ``alpha``,
-    saving, ``ensemble`` - acts on the merged image of each completed entry.  With 1 (the default) the library is not loaded and
-    nothing is launched.  Any other N, and N > 1 with an EDM model, is a ``ValueError`` before anything is sampled.
-    ``dynamic_threshold`` (``--dynamic_threshold P``): P > 0 is handed by keyword to whichever ``sr_target_image*`` function samples
-    a group (``tiled_sample(dynamic_threshold=P)``: percentile clipping of the predicted clean image inside the sampling loop); with 0
-    the keyword is not passed at all.  A P outside [0, 1] is a ``ValueError`` before anything is sampled.
-    ``alpha`` / ``alpha_bleed`` (``--alpha keep``, ``--alpha_bleed N``): with "keep" every input is opened with its alpha plane
-    (``try_open_image_with_alpha``); an input that has one is, with N > 0, bled once per opened file (``bleed_on_device``: the bled RGB
-    image replaces the input for everything below, the K samples of a file share it), sampled and measured as RGB like every other
-    input, and last of all in ``flush()`` - after the ``outscale`` block - the outputs of such inputs get their alpha in one batched
-    ``attach_alpha_on_device`` call (srgd_amd.alpha) and are saved as RGBA files.  Inputs without transparency are written as RGB.
-    With "drop" (the default) the library is not loaded and nothing is launched.  Not together with ``ensemble``; N > 0 needs "keep"
-    (``ValueError``).
-    ``outscale`` / ``outscale_filter`` (``--outscale S``, ``--outscale_filter``): with S other than None / 4 every image a group
-    returned - the 8-bit image as it would have been saved, after everything above has been measured on it - goes through one batched
-    ``resize_on_device`` call per ``flush()`` (srgd_amd.resize: Pillow's ``Image.resize`` bit for bit) to ``outscale_size`` of its
-    input, and that image is saved; ``reference_dir`` and ``consistency`` keep measuring the x4 image.  With None / 4 the library is
-    not loaded and nothing is launched.  Not together with ``ensemble`` (``ValueError``).
-    ``sampler`` / ``eta`` / ``step_spacing`` (``--sampler``, ``--eta``, ``--step_spacing``): each is handed by keyword to whichever
-    ``sr_target_image*`` function samples a group only where it is not the default ("ddpm", None, "time"); bad values are a
-    ``ValueError`` before anything is sampled.
-    ``consistency_guidance`` / ``consistency_guidance_start_steps`` (``--consistency_guidance G``): G > 0 is handed by keyword to
-    whichever ``sr_target_image*`` function samples a group (``tiled_sample(consistency_guidance=G, ...)``: LR-consistency guidance
-    inside the sampling loop); with 0 the keywords are not passed at all.  An input smaller than 5 pixels on a side is then a
-    ``ValueError`` before anything is sampled.
-    ``back_project`` (``--back_project N``): N > 0 is handed by keyword to whichever ``sr_target_image*`` function samples a group
-    (``tiled_sample(back_project=N)``: the image is pulled back onto its input before it is saved, so every number below is taken of
-    the corrected file); with 0 the keyword is not passed at all.
-    ``consistency`` (``--consistency``): after a group is sampled, the images it returned - as saved - and the inputs it was given
-    go through one ``consistency_on_device`` call per ``flush()`` (srgd_amd.consistency: the output reduced x4 by Pillow's bicubic
-    against its input); with ``ensemble`` the mean image of every completed file is measured the same way.  An input smaller than 5
-    pixels on a side is reported and left out.  The numbers of the files written go to ``output_dir/consistency_name``
-    (``consistency_document``) when at least one file was sampled in this run.  Without it nothing is computed or written.
-    ``ensemble`` (``--ensemble``, ``samples`` >= 2): once the last sample of an input file has been handled and all its ``samples``
-    sample files exist - written by this run or found on disk by the skip-if-exists rule - the file's mean image and spread map
-    (srgd_amd.ensemble) are written to ``<name>_out_mean.png`` / ``<name>_out_std.png``; the files completed by one ``flush()`` go
-    through one batched ``ensemble_on_device`` call.  Samples of this run are taken from the PIL images the ``sr_target_image*``
-    functions return, samples found on disk are decoded on the writer pool, so a resumed run writes the same two files as an
-    uninterrupted one.  A file whose samples, mean and spread all exist is skipped; a sample on disk of another size than x``scale``
-    of the input is reported and that file's ensemble is left out.  The statistics of the files handled go to
-    ``output_dir/ensemble_name`` (``ensemble_document``) and, with ``reference_dir``, the mean images' PSNR / SSIM to ``metrics_name``.
-    ``reference_dir`` (``--reference_dir``): every input's ground truth ``reference_dir/<same name>`` is checked first (present,
-    exactly ``scale`` times the input: ``check_references``), decoded on the writer pool while earlier groups sample, and handed to
-    the group's ``sr_target_image*`` call; the numbers of every file written go to ``output_dir/metrics_name``
-    (``metrics_document``).  Without it nothing is checked, decoded or written.
-    ``color_fix``: ``--color_fix`` (None / "none", "wavelet", "adain"), handed by keyword to whichever ``sr_target_image*``
-    function samples a group.  ``lockstep``: groups of up to N consecutive same-sized images; ``lockstep_tiles``: groups of consecutive images of any
-    size up to that many tiles per even step (srgd_amd.lockstep.plan_lockstep_groups).  ``labels``: ``{file name: label}``
-    (``--label_file``) for the images that do not take ``test_label``; a group may mix labels.  ``samples``: every image is
-    sampled that many times with the noise seeds ``seed, seed + 1, ...`` (``--samples``); the samples of an image are consecutive
-    entries of the grouping, each counts as an image of its group, and with neither lock-step argument they group as
-    ``lockstep=samples``."""
-    from .lockstep import even_step_tiles, plan_lockstep_groups
+    """The folder driver.  Every argument is checked first: a bad value or an excluded combination is a ``ValueError``, a missing or
+    misshapen ground truth or known output a ``SystemExit`` (``check_references``, ``check_region_known``), before anything is sampled.
+    Then every planned entry (``plan_sample_entries``: ``samples`` noise seeds ``seed, seed + 1, ...`` per file, skip-if-exists per
+    output file; ``labels``: ``{file name: label}`` for the files that do not take ``test_label``) is opened and queued.  The entries of
+    a file share what is made once per opened file: the decoded image, its alpha plane and the bled image (``alpha="keep"``,
+    ``alpha_bleed``), the future of its ground truth (``reference_dir``), its N orientations (``self_ensemble``: N consecutive entries
+    per sample, the ops of ``srgd_amd.selfens.OPS[N]`` in order) and the future of its known output (``region_known_dir``).
+    ``_queue`` decides where a lock-step group ends and ``_flush`` takes the group through the stages, in this order:
+    ``_sample_entries``, ``_merge_self_ensemble``, ``_measure_consistency``, ``_outscale``, ``_attach_alpha``, ``_save``,
+    ``_flush_ensembles``.  Last, where at least one file was sampled, ``metrics_name`` (``reference_dir``), ``consistency_name``
+    (``consistency``) and ``ensemble_name`` (``ensemble``) are written.  A switch at its default loads no library, launches nothing
+    and writes nothing; with neither lock-step argument ``samples`` and ``self_ensemble`` group as ``lockstep = self_ensemble * samples``."""
     self_ensemble = check_self_ensemble(self_ensemble)
     if self_ensemble > 1 and isinstance(sr_model, ConditionalElucidatedDiffusionSR):
         raise ValueError("self_ensemble: the orientations of an image are sampled in lock-step with per-image noise seeds, which is "
@@ -894,254 +1084,58 @@ def batch_sr_target_images(input_dir, output_dir, sr_model, scale=4, batch_size=
         if not 1 <= len(regions) <= REGION_MAX_BOXES:
             raise ValueError(f"regions: 1 .. {REGION_MAX_BOXES} boxes, got {len(regions)}")
         check_region_known(file_names, region_known_dir, regions, scale, samples)
-    from concurrent.futures import ThreadPoolExecutor
-    pending, saves = [], []                              # (image, save_path, label, noise seed, reference) of the current lock-step group; PNG writers
-    file_records = []                                    # (input file name, written file name, metric dict) of --reference_dir
     if ensemble and not 2 <= samples <= 256:
         raise ValueError("ensemble: samples must be in 2..256")
-    ens_open = {}                                        # --ensemble: input file -> [its K samples (PIL image of this run) or None (on disk)], samples still to draw
-    ens_ready, ens_records, ens_quality = [], [], []     # files whose last sample is handled; ensemble.json rows; metrics.json rows
-    cons_records, cons_ensemble = [], []                 # --consistency: consistency.json rows of the files written; of the mean images
-    held = {}                                            # --self_ensemble: save path -> [(entry, 8-bit output)] of the variants sampled so far
-
-    def measure_consistency(names, outputs, inputs):
-        """One batched ``consistency_on_device`` call: ``outputs`` uint8 [4h,4w,3] tensors, ``inputs`` the PIL inputs ->
-        ``[(name, record)]`` of the images large enough."""
-        keep = []
-        for i, im in enumerate(inputs):
-            if min(im.size) < CONSISTENCY_MIN_SIDE:
-                print(f"consistency: {names[i]} is {im.size[0]}x{im.size[1]}, smaller than {CONSISTENCY_MIN_SIDE} pixels on a side: "
-                      "left out")
-            else:
-                keep.append(i)
-        if not keep:
-            return []
-        device = getattr(sr_model, "device", None)
-        place = (lambda t: t.to(device)) if device is not None else (lambda t: t)        # noqa: E731
-        lows = {}                                        # the K samples of a file share one upload of the input
-        for i in keep:
-            if id(inputs[i]) not in lows:
-                lows[id(inputs[i])] = place(pil_to_u8_tensor(inputs[i]))
-        recs = consistency_on_device([place(outputs[i]) for i in keep], [lows[id(inputs[i])] for i in keep])
-        return [(names[i], rec) for i, rec in zip(keep, recs)]
-    if ensemble:
-        for filename in file_names:
-            paths = [os.path.join(output_dir, sample_output_name(filename, k)) for k in range(samples)]
-            missing = sum(not os.path.exists(p) for p in paths)
-            if missing == 0 and all(os.path.exists(os.path.join(output_dir, n)) for n in ensemble_output_names(filename)):
-                continue                                 # samples, mean and spread exist: nothing to do for this file
-            if missing == 0:
-                ens_ready.append(filename)               # every sample is on disk: only the two ensemble files are missing
-            ens_open[filename] = [[None] * samples, missing]
-
+    opt = SimpleNamespace(scale=scale, lockstep=lockstep, lockstep_tiles=lockstep_tiles, samples=samples, output_dir=output_dir,
+                          reference_dir=reference_dir, crop_border=crop_border, self_ensemble=self_ensemble, regions=regions,
+                          consistency=consistency, outscale=outscale, outscale_filter=outscale_filter, ensemble=ensemble, kw=kw)
     with ThreadPoolExecutor(max_workers=2) as pool:      # PNG encoding overlaps the next group's sampling
-        def flush():
-            if not pending:
-                return
-            if lockstep_tiles is not None:
-                sizes = [e[0].size for e in pending]
-                tiles = sum(even_step_tiles(h * scale, w * scale) for (w, h) in sizes)
-                print(f"lock-step group: {len(pending)} images, {tiles} tiles per even step")
-            group_labels = [e[2] for e in pending]
-            group_seeds = [e[3] for e in pending]
-            one_label = group_labels[0] if len(set(group_labels)) == 1 else group_labels
-            group_images = [e[0] for e in pending]
-            ref_kw = {}
-            if reference_dir is not None and self_ensemble == 1:         # the decoded references of the group (one future per input file)
-                ref_kw = {"reference": [e[4].result() for e in pending], "crop_border": crop_border}
-            reg_kw = {}
-            if regions is not None:                      # the decoded known outputs of the group (one future per known file)
-                reg_kw = {"region_known": [e[10].result() for e in pending], "regions": regions}
-            if len(pending) == 1:                        # a solo run with that seed: what every sample of a group is identical to
-                solo_kw = dict(ref_kw, reference=ref_kw["reference"][0]) if ref_kw else {}
-                if reg_kw:
-                    solo_kw = dict(solo_kw, region_known=reg_kw["region_known"][0], regions=regions)
-                outs = sr_target_image(pending[0][0], sr_model, test_label=group_labels[0], **dict(kw, seed=group_seeds[0]), **solo_kw)
-                outs = ([outs[0]], outs[1]) if ref_kw else [outs]
-            elif len(set(group_seeds)) > 1:
-                outs = sr_target_images_seeded(group_images, group_seeds, sr_model, test_label=one_label, **kw, **ref_kw, **reg_kw)
-            elif lockstep_tiles is not None:
-                outs = sr_target_images_mixed(group_images, sr_model, test_label=one_label, **dict(kw, seed=group_seeds[0]), **ref_kw,
-                                              **reg_kw)
-            else:
-                outs = sr_target_images(group_images, sr_model, test_label=one_label, **dict(kw, seed=group_seeds[0]), **ref_kw,
-                                        **reg_kw)
-            if ref_kw:
-                outs, quality = outs
-                file_records.extend((e[5], os.path.basename(e[1]), q) for e, q in zip(pending, quality))
-            if self_ensemble > 1:                        # the entries whose last variant arrived are merged; the rest is held
-                for e, sr in zip(pending, outs):
-                    held.setdefault(e[1], []).append((e, sr))
-                complete = [held.pop(path) for path in [path for path, parts in held.items() if len(parts) == self_ensemble]]
-                pending.clear()
-                if not complete:
-                    return
-                device = getattr(sr_model, "device", None)
-                place = (lambda t: t.to(device)) if device is not None else (lambda t: t)        # noqa: E731
-                merged = self_ensemble_on_device([[(place(pil_to_u8_tensor(sr)), e[8]) for e, sr in parts] for parts in complete],
-                                                 return_mean01=reference_dir is not None)
-                # from here on the group is the completed entries, each with its original input and its merged image
-                pending.extend((parts[0][0][9],) + parts[0][0][1:] for parts in complete)
-                group_images = [e[0] for e in pending]
-                if reference_dir is not None:
-                    quality = metrics_on_device([m[1] for m in merged], [e[4].result() for e in pending], crop_border)
-                    file_records.extend((e[5], os.path.basename(e[1]), q) for e, q in zip(pending, quality))
-                    merged = [m[0] for m in merged]
-                outs = [Image.fromarray(m.cpu().numpy(), "RGB") for m in merged]
-            if consistency:                              # the images as saved against the inputs the group was given
-                written = [os.path.basename(e[1]) for e in pending]
-                source = dict(zip(written, (e[5] for e in pending)))
-                cons_records.extend((source[name], name, rec) for name, rec in
-                                    measure_consistency(written, [pil_to_u8_tensor(sr) for sr in outs], group_images))
-            if outscale is not None:                     # last of all: the images as they would have been saved, resized in one call
-                from .resize import resize_on_device
-                device = getattr(sr_model, "device", None)
-                u8 = [pil_to_u8_tensor(sr) for sr in outs]
-                resized = resize_on_device([t.to(device) for t in u8] if device is not None else u8,
-                                           [outscale_size(im.size[1], im.size[0], outscale) for im in group_images], outscale_filter)
-                outs = [Image.fromarray(t.cpu().numpy(), "RGB") for t in resized]
-            with_alpha = [i for i, e in enumerate(pending) if e[7] is not None]
-            if with_alpha:                               # --alpha keep: the outputs whose input had an alpha plane leave as RGBA
-                device = getattr(sr_model, "device", None)
-                place = (lambda t: t.to(device)) if device is not None else (lambda t: t)        # noqa: E731
-                lows = {}                                # the K samples of a file share one upload of the plane
-                for i in with_alpha:
-                    if id(pending[i][7]) not in lows:
-                        lows[id(pending[i][7])] = place(torch.from_numpy(pending[i][7]))
-                rgba = attach_alpha_on_device([place(pil_to_u8_tensor(outs[i])) for i in with_alpha],
-                                              [lows[id(pending[i][7])] for i in with_alpha], scale, outscale_filter)
-                outs = list(outs)
-                for i, t in zip(with_alpha, rgba):
-                    outs[i] = Image.fromarray(t.cpu().numpy(), "RGBA")
-            for e, sr in zip(pending, outs):
-                saves.append(pool.submit(sr.save, e[1]))
-                if e[6] in ens_open:                     # --ensemble: sample e[3] - seed of the file has been drawn
-                    state = ens_open[e[6]]
-                    state[0][e[3] - seed] = sr
-                    state[1] -= 1
-                    if state[1] == 0:
-                        ens_ready.append(e[6])
-            pending.clear()
-            if ensemble:
-                flush_ensembles()
-
-        def flush_ensembles():
-            """One batched ensemble call for the files completed since the last one."""
-            todo = []                                    # (file name, futures / tensors of its K samples)
-            for filename in ens_ready:
-                drawn = ens_open.pop(filename)[0]
-                todo.append((filename, [pool.submit(load_reference, os.path.join(output_dir, sample_output_name(filename, k)))
-                                        if sr is None else pil_to_u8_tensor(sr) for k, sr in enumerate(drawn)]))
-            ens_ready.clear()
-            names, stacks = [], []
-            for filename, parts in todo:
-                try:
-                    with Image.open(filename) as im:     # the header only
-                        want = (im.size[1] * scale, im.size[0] * scale, 3)
-                except (IOError, SyntaxError):
-                    continue                             # not an image: the sampling loop has reported it
-                try:
-                    parts = [part if torch.is_tensor(part) else part.result() for part in parts]
-                except (IOError, SyntaxError) as err:
-                    print(f"ensemble: a sample of {os.path.basename(filename)} cannot be read ({err}): no ensemble for this file")
-                    continue
-                wrong = [k for k, part in enumerate(parts) if tuple(part.shape) != want]
-                if wrong:
-                    for k in wrong:
-                        print(f"ensemble: {sample_output_name(filename, k)} is {parts[k].shape[1]}x{parts[k].shape[0]}, x{scale} of the "
-                              f"input is {want[1]}x{want[0]}: no ensemble for {os.path.basename(filename)}")
-                    continue
-                names.append(filename)
-                stacks.append(torch.stack(parts))
-            if not names:
-                return
-            device = getattr(sr_model, "device", None)
-            if device is not None:
-                stacks = [st.to(device) for st in stacks]
-            results = ensemble_on_device(stacks, return_mean01=reference_dir is not None)
-            if reference_dir is not None:
-                refs = [pool.submit(load_reference, os.path.join(reference_dir, os.path.basename(f))) for f in names]
-                quality = metrics_on_device([r[3] for r in results], [f.result() for f in refs], crop_border)
-                ens_quality.extend((os.path.basename(f), q) for f, q in zip(names, quality))
-            if consistency:                              # the uint8 mean images against their inputs
-                lows = [try_open_image(f) for f in names]
-                have = [i for i, im in enumerate(lows) if im is not None]
-                cons_ensemble.extend(measure_consistency([os.path.basename(names[i]) for i in have], [results[i][0] for i in have],
-                                                         [lows[i] for i in have]))
-            for filename, res in zip(names, results):
-                mean_name, std_name = ensemble_output_names(filename)
-                for arr, out_name in ((res[0], mean_name), (res[1], std_name)):
-                    saves.append(pool.submit(Image.fromarray(arr.cpu().numpy(), "RGB").save, os.path.join(output_dir, out_name)))
-                ens_records.append((os.path.basename(filename), mean_name, std_name, res[2]))
-
-        opened = (None, None, None)                      # the K samples of a file share one decoded image and one reference
-        plane = None                                     # --alpha keep: the alpha plane of the opened file, or None
-        variants = (None, None)                          # --self_ensemble: (the opened input, its N orientations)
+        run = _Run(sr_model, pool, opt, getattr(sr_model, "device", None))
+        if ensemble:
+            _plan_ensembles(run, file_names)
+        opened, original, plane, ref, variants = None, None, None, None, None      # shared by every entry of the opened file
         known_open = (None, None)                        # --region_known_dir: (the known file last opened, its decoding future)
         for filename, save_path, noise_seed in plan_sample_entries(file_names, output_dir, samples, seed):
-            if opened[0] != filename:
-                if alpha == "keep":
-                    image, plane = try_open_image_with_alpha(filename)
-                    if plane is not None and alpha_bleed:        # once per opened file: the bled image is the input from here on
-                        device = getattr(sr_model, "device", None)
-                        rgba = torch.from_numpy(np.dstack([np.asarray(image, dtype=np.uint8), plane]))
-                        bled = bleed_on_device([rgba.to(device) if device is not None else rgba], alpha_bleed)[0]
-                        image = Image.fromarray(bled.cpu().numpy(), "RGB")
-                    opened = (filename, image, None)
-                else:
-                    opened = (filename, try_open_image(filename), None)
-                if opened[1] is None:
+            name, k = os.path.basename(filename), noise_seed - seed
+            if opened != filename:
+                opened, ref = filename, None
+                original, plane = try_open_image_with_alpha(filename) if alpha == "keep" else (try_open_image(filename), None)
+                if original is None:
                     print("Invalid image or unable to open image:", filename)
-                elif reference_dir is not None:          # decoded on the pool while the groups before this one sample
-                    opened = opened[:2] + (pool.submit(load_reference, os.path.join(reference_dir, os.path.basename(filename))),)
-            original, ref = opened[1], opened[2]
-            if original is None:
+                    continue
+                if plane is not None and alpha_bleed:    # the bled image is the input from here on
+                    rgba = torch.from_numpy(np.dstack([np.asarray(original, dtype=np.uint8), plane]))
+                    original = _u8_to_pil(bleed_on_device([run.place(rgba)], alpha_bleed)[0])
+                if reference_dir is not None:            # decoded on the pool while the groups before this one sample
+                    ref = pool.submit(load_reference, os.path.join(reference_dir, name))
+                variants = [original]
+                if self_ensemble > 1:                    # the input in every orientation
+                    turned = dihedral_on_device([run.place(pil_to_u8_tensor(original))] * self_ensemble, list(SELF_ENSEMBLE_OPS[self_ensemble]))
+                    variants = [_u8_to_pil(t) for t in turned]
+            elif original is None:
                 continue
-            if self_ensemble > 1 and variants[0] is not original:          # once per opened file: the input in every orientation
-                device = getattr(sr_model, "device", None)
-                low = pil_to_u8_tensor(original)
-                turned = dihedral_on_device([low.to(device) if device is not None else low] * self_ensemble,
-                                            list(SELF_ENSEMBLE_OPS[self_ensemble]))
-                variants = (original, [Image.fromarray(t.cpu().numpy(), "RGB") for t in turned])
-            label = labels.get(os.path.basename(filename), test_label)
             known = None
             if regions is not None:                      # decoded on the pool; the samples that start from one file share it
-                known_file = region_known_path(region_known_dir, filename, noise_seed - seed, samples)
+                known_file = region_known_path(region_known_dir, filename, k, samples)
                 if known_open[0] != known_file:
                     known_open = (known_file, pool.submit(load_region_known, known_file))
                 known = known_open[1]
-            for op, image in zip(SELF_ENSEMBLE_OPS[self_ensemble], variants[1] if self_ensemble > 1 else [original]):
-                if pending and (label is None) != (pending[0][2] is None): # an unlabelled image does not join a labelled group
-                    flush()
-                if lockstep_tiles is not None:
-                    hr = [(h * scale, w * scale) for (w, h) in [e[0].size for e in pending] + [image.size]]
-                    if len(plan_lockstep_groups(hr, lockstep_tiles)) > 1:  # the image would push the group over the budget
-                        flush()
-                    pending.append((image, save_path, label, noise_seed, ref, os.path.basename(filename), filename, plane, op, original, known))
-                    continue
-                if pending and (len(pending) >= max(1, lockstep) or pending[0][0].size != image.size):
-                    flush()
-                pending.append((image, save_path, label, noise_seed, ref, os.path.basename(filename), filename, plane, op, original, known))
-                if len(pending) >= max(1, lockstep):
-                    flush()
-        flush()
+            for op, image in zip(SELF_ENSEMBLE_OPS[self_ensemble], variants):
+                _queue(run, _Entry(image=image, save_path=save_path, label=labels.get(name, test_label), seed=noise_seed, k=k, reference=ref,
+                                   name=name, file_name=filename, plane=plane, op=op, original=original, known=known))
+        _flush(run)
         if ensemble:
-            flush_ensembles()
-        for f in saves:
+            _flush_ensembles(run)
+        for f in run.saves:
             f.result()                                   # surface write errors
-    if file_records:                                     # --reference_dir, and at least one file was sampled in this run
-        with open(os.path.join(output_dir, metrics_name), "w") as f:
-            json.dump(metrics_document(file_records, samples, crop_border, **({"ensemble": ens_quality} if ens_quality else {})), f,
-                      indent=1)
-            f.write("\n")
-    if cons_records:                                     # --consistency, and at least one file was sampled in this run
-        with open(os.path.join(output_dir, consistency_name), "w") as f:
-            json.dump(consistency_document(cons_records, samples, **({"ensemble": cons_ensemble} if cons_ensemble else {})), f, indent=1)
-            f.write("\n")
-    if ens_records:                                      # --ensemble, and at least one file's ensemble was taken in this run
-        with open(os.path.join(output_dir, ensemble_name), "w") as f:
-            json.dump(ensemble_document(ens_records, samples), f, indent=1)
-            f.write("\n")
+    if run.file_records:                                 # --reference_dir, and at least one file was sampled in this run
+        _write_document(os.path.join(output_dir, metrics_name),
+                        metrics_document(run.file_records, samples, crop_border, **({"ensemble": run.ens_quality} if run.ens_quality else {})))
+    if run.cons_records:                                 # --consistency, and at least one file was sampled in this run
+        _write_document(os.path.join(output_dir, consistency_name),
+                        consistency_document(run.cons_records, samples, **({"ensemble": run.cons_ensemble} if run.cons_ensemble else {})))
+    if run.ens_records:                                  # --ensemble, and at least one file's ensemble was taken in this run
+        _write_document(os.path.join(output_dir, ensemble_name), ensemble_document(run.ens_records, samples))
 
 
 def rank_file_range(n_files, start_index, end_index, rank, world):
