@@ -42,6 +42,7 @@ from .lockstep import even_step_tiles, plan_lockstep_groups
 from .metrics import KEYS as METRIC_KEYS
 from .metrics import metrics_on_device  # noqa: F401  (public: srgd_amd.inference.metrics_on_device)
 from .model import ConditionalElucidatedDiffusionSR, get_model
+from .precision_schedule import describe_plan, executed_names, plan_steps
 from .region import MAX_BOXES as REGION_MAX_BOXES
 from .resize import FILTERS as OUTSCALE_FILTERS
 from .resize import check_filter, check_outscale, outscale_size
@@ -201,7 +202,19 @@ def parse_args(argv=None):
     p.add_argument("--region", action="append", default=None, metavar="T,L,H,W",
                    help="with --region_known_dir: a box top,left,height,width in output pixels to sample again; repeatable up to 16 "
                         "times, boxes may overlap; the same boxes are used for every input, so each must lie inside every output")
+    p.add_argument("--precision_schedule", type=str, default=None, metavar="SPEC",
+                   help="a precision per step instead of --precision, NAME[:COUNT](,NAME[:COUNT])* over the loop indices of "
+                        "--num_sample_steps: bf16:40,f16x3 takes the first 40 steps in bf16 and the rest in f16x3, bf16,f16x3:10 the last "
+                        "10 in f16x3; 1 to 4 entries, at most one without a count.  The canvases are fp32 in every precision, so a switch "
+                        "converts nothing and every step is the step its precision takes from that canvas; every named engine holds its "
+                        "own packed weights.  How far a mixed run lies from the reference is measured by "
+                        "tools/price_precision_schedule.py (DDPM configs only, engine extension)")
     args = p.parse_args(argv)
+    if args.precision_schedule is not None:
+        try:
+            args.precision_plan = plan_steps(args.precision_schedule, args.num_sample_steps)
+        except ValueError as e:
+            raise SystemExit(f"--precision_schedule: {e}")
     try:
         args.self_ensemble = check_self_ensemble(args.self_ensemble)
     except ValueError as e:
@@ -1168,6 +1181,9 @@ def main(argv=None):
         raise SystemExit("--self_ensemble: the orientations of an image are sampled in lock-step with per-image noise seeds, which is "
                          "built for the DDPM sampler (model: conditional_continuous) only; this config samples with EDM - run "
                          "without it")
+    if args.precision_schedule is not None and conf.model == "conditional_elucidated":   # before the model is built
+        raise SystemExit("--precision_schedule: a precision per step is built for the DDPM sampler (model: conditional_continuous) "
+                         "only; this config samples with EDM - use --precision")
     conf.num_sample_steps = args.num_sample_steps
     conf.ckpt_path = args.ckpt_path
     ema_model = get_model(conf, logger)
@@ -1187,20 +1203,27 @@ def main(argv=None):
                          "this config samples with EDM - run once per --seed instead")
     sr_model.noise_source = "device" if args.device_noise else "host"
     sr_model.precision = args.precision
-    print(f"engine precision: {args.precision} (noise: {sr_model.noise_source})")
-    if args.amp and args.precision in ("fp32", "f16x3", "f16mx2"):
+    precisions = [args.precision]                        # the engines to pack: with a schedule, those of its executed steps
+    if args.precision_schedule is not None:              # --precision is then not used
+        sr_model.precision_schedule = args.precision_schedule
+        precisions = executed_names(args.precision_plan, args.generation_start_steps)
+        print(f"engine precision schedule: {describe_plan(args.precision_plan)} (noise: {sr_model.noise_source})")
+    else:
+        print(f"engine precision: {args.precision} (noise: {sr_model.noise_source})")
+    if args.precision_schedule is None and args.amp and args.precision in ("fp32", "f16x3", "f16mx2"):
         # callers of earlier builds got bf16 from amp=True; upstream's sampler ignores amp and so does this one
         print("note: amp is accepted and ignored as upstream (the sampler computes at fp32 accuracy: f16x3 ~3.4x, fp32 ~10x slower "
               "than the bf16 engine); pass --precision bf16 for the throughput mode")
     import time
     t_pack = time.perf_counter()
     unet = getattr(sr_model, "model", None) or sr_model.net
-    unet.engine(args.precision)                         # pack + upload the weights now, not inside the first image
     from .lanes import AUTO_LANE_PRECISIONS
-    if (sr_model.step_lanes is None and args.precision in AUTO_LANE_PRECISIONS) or (sr_model.step_lanes or 1) > 1:
-        # small steps run as two concurrent halves through a second engine instance (srgd_amd.lanes: a second copy of the packed
-        # weights, scratch and graphs): built here, not inside the first image's sampling loop
-        unet.engine(args.precision, lane=1)
+    for name in precisions:
+        unet.engine(name)                               # pack + upload the weights now, not inside the first image
+        if (sr_model.step_lanes is None and name in AUTO_LANE_PRECISIONS) or (sr_model.step_lanes or 1) > 1:
+            # small steps run as two concurrent halves through a second engine instance (srgd_amd.lanes: a second copy of the packed
+            # weights, scratch and graphs): built here, not inside the first image's sampling loop
+            unet.engine(name, lane=1)
     torch.cuda.synchronize()
     print(f"engine ready: {len(sr_model.state_dict())} tensors packed and uploaded in {time.perf_counter() - t_pack:.2f} s")
     print(args)

@@ -37,6 +37,7 @@ from .threshold import check_percentile, threshold_step_flat
 from .threshold import records as threshold_records
 from .threshold import scratch_bytes as threshold_scratch_bytes
 from .lanes import StepLanes, lanes_setting_from_env, lanes_wanted
+from .precision_schedule import executed_names, parse_schedule, plan_steps
 from .region import RegionImage, _RegionRun, check_region_args
 
 __all__ = ["get_coord_and_pad", "get_coords", "get_area", "beta_linear_log_snr", "ConditionalSRUnet",
@@ -507,6 +508,7 @@ class ConditionalSRUnet(nn.Module):
 # the sampler
 # ---------------------------------------------------------------------------------------------
 _BOTH_SCALES = "Currently, you cannot specify both cond_scale and class_cond_scale at the same time."
+_SCHEDULE_SHARDED = "precision_schedule on a canvas sharded over ranks (canvas_group)"
 
 
 def _step_guidance(i, cond_scale, guidance_start_steps, class_cond_scale, class_guidance_start_steps, joint=False):
@@ -591,6 +593,9 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
         # "fp8" (MX-fp8 3x3 convolutions, BASELINE configs[4]), "fp8_mixed" (fp8 below the top resolution only: 53 dB vs
         # bf16 instead of 34 dB).  tiled_sample(precision=...) overrides it per call.
         self.precision = "fp32"
+        # None, or a precision schedule (srgd_amd.precision_schedule, e.g. "bf16:40,f16x3"): tiled_sample then takes every step
+        # in the precision the schedule plans for it; tiled_sample(precision_schedule=...) or (precision=...) overrides it per call
+        self.precision_schedule = None
         # set by srgd_amd.parallel.shard_canvas: a torch.distributed group whose ranks share ONE canvas - each rank
         # runs a contiguous slice of every step's tiles and the updated tiles are all-gathered
         self.canvas_group = None
@@ -603,6 +608,20 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
     def device(self):
         return next(self.model.parameters()).device
 
+    def _precision_plan(self, precision, schedule, num_sample_steps, generation_start_steps):
+        """``(plan, names)`` of a tiled run: the precision of every loop index and the distinct precisions of the executed steps
+        in order of first use.  ``schedule``: the call's parsed ``precision_schedule`` or None; without it and without
+        ``precision`` the wrapper's ``precision_schedule`` attribute holds, and without any schedule every step has the run's one
+        precision."""
+        if schedule is None and precision is None and self.precision_schedule is not None:
+            schedule = parse_schedule(self.precision_schedule)
+        if schedule is None:
+            return [precision or self.precision] * num_sample_steps, [precision or self.precision]
+        if self.canvas_group is not None:
+            raise NotImplementedError(_SCHEDULE_SHARDED)
+        plan = plan_steps(schedule, num_sample_steps)
+        return plan, executed_names(plan, generation_start_steps)
+
     @torch.inference_mode()
     def tiled_sample(self, batch_size=4, tile_size=256, tile_stride=256, condition_x=None, class_label=None,
                      cond_scale=1.0, guidance_start_steps=0, class_cond_scale=1.0, class_guidance_start_steps=0,
@@ -610,7 +629,8 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                      start_white_noise=True, amp=False, precision=None, seeds=None, color_fix=None, reference=None,
                      crop_border=4, back_project=0, consistency_guidance=0.0, consistency_guidance_start_steps=0,
                      sampler="ddpm", eta=None, step_spacing="time", dynamic_threshold=None, threshold_log=None,
-                     joint_guidance=False, region_known=None, regions=None, region_skip_tiles=True, region_log=None):
+                     joint_guidance=False, region_known=None, regions=None, region_skip_tiles=True, region_log=None,
+                     precision_schedule=None, precision_log=None):
         """Tiled CFG-DDPM sampling (reference model.py:3288-3413).
 
         ``amp`` is accepted and ignored exactly as in the reference (which always computes fp32); the engine
@@ -716,7 +736,31 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
         ``region_log``: a list that receives one row ``[tiles evaluated per image]`` per executed step.  Step lanes are off in a
         region run.  ``ValueError`` before anything is sampled: a box outside the image, no box or more than 16, a ``region_known``
         of another shape or dtype, one keyword without the other; not available on a canvas sharded over ranks or in the EDM
-        wrapper (``NotImplementedError``).  Picture quality on trained weights is not measured."""
+        wrapper (``NotImplementedError``).  Picture quality on trained weights is not measured.
+
+        ``precision_schedule`` (engine-only keyword, absent upstream; srgd_amd.precision_schedule): None (default) is the wrapper's
+        ``precision_schedule`` attribute, and with that None too the run is byte for byte what it is today.  Otherwise a schedule
+        ``NAME[:COUNT](,NAME[:COUNT])*`` or a sequence of ``(name, count or None)`` pairs - ``"bf16:40,f16x3"``: loop indices 0 .. 39 in
+        bf16, the rest in f16x3; ``"bf16,f16x3:10"``: the last 10 in f16x3 - planned over the absolute loop indices of
+        ``num_sample_steps``.  Step i runs on the engine of its precision; the canvases are fp32 in every precision and the noise
+        draws do not depend on the engine, so nothing is converted at a switch and a step is bit for bit the step a run of that one
+        precision takes from the same canvas.  Every precision with an executed step gets its engine begun once before the loop with
+        the run's geometry, scalars, labels and seeds and its own condition canvas; the start canvas comes from the engine of the first
+        executed step and the final image from that of the last (entries that do not depend on the precision).  A schedule whose
+        executed steps share one name is ``precision=NAME``, call for call.  Step lanes are decided per step with the step's
+        precision.  Works in all three drivers and with every other keyword, which act on the fp32 canvases.  ``precision_log``: a
+        list that receives the precision of every executed step.  ``ValueError`` before anything is sampled: a malformed schedule,
+        counts that do not fit ``num_sample_steps``, ``precision`` and ``precision_schedule`` in one call; not available on a canvas
+        sharded over ranks or in the EDM wrapper (``NotImplementedError``).  Picture quality on trained weights is not measured."""
+        if precision_schedule is not None:
+            if precision is not None:
+                raise ValueError("precision and precision_schedule in one call: a run has one precision or one schedule")
+            precision_schedule = parse_schedule(precision_schedule)
+            if self.canvas_group is not None:
+                raise NotImplementedError(_SCHEDULE_SHARDED)
+        if precision_log is not None and not isinstance(precision_log, list):
+            raise ValueError("precision_log: None or a list")
+        schedule_kw = dict(precision_schedule=precision_schedule, precision_log=precision_log)
         region = None
         if region_known is not None or regions is not None:
             if self.canvas_group is not None:
@@ -744,6 +788,8 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
         if reference is not None:
             reference = _packed_reference(reference, condition_x, crop_border, self)
         num_sample_steps = self.num_sample_steps if num_sample_steps is None else num_sample_steps
+        if precision_schedule is not None:  # the counts against the run's length, before anything is sampled
+            plan_steps(precision_schedule, num_sample_steps)
         if seeds is not None:
             as_list = isinstance(condition_x, (list, tuple))
             seeds = _noise_seeds(seeds, len(condition_x) if as_list else int(condition_x.shape[0]))
@@ -764,7 +810,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                                              generation_start_steps, num_sample_steps, start_white_noise, precision, seeds=seeds,
                                              color_fix=color_fix, reference=reference, crop_border=crop_border, back_project=back_project,
                                              guidance=guidance, solver=solver, threshold=threshold, threshold_log=threshold_log,
-                                             joint=joint, **region_kw)
+                                             joint=joint, **region_kw, **schedule_kw)
             if reference is not None:
                 return (outs[0] if as_list else torch.cat(outs[0], 0)), outs[1]
             return outs if as_list else torch.cat(outs, 0)
@@ -782,7 +828,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                                              generation_start_steps, num_sample_steps, start_white_noise, precision,
                                              color_fix=color_fix, reference=reference, crop_border=crop_border, back_project=back_project,
                                              guidance=guidance, solver=solver, threshold=threshold, threshold_log=threshold_log,
-                                             joint=joint, **region_kw)
+                                             joint=joint, **region_kw, **schedule_kw)
         joint = _check_joint(joint_guidance, cond_scale, class_cond_scale, class_label, self.canvas_group)
         if tile_size != 256 or tile_stride != 256:
             raise NotImplementedError("tile_size/tile_stride other than 256 are unusable in the reference too "
@@ -798,7 +844,9 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
         class_id, image_ids = _run_labels(_image_class_ids(class_label, batch))
         if image_ids is not None and self.canvas_group is not None:
             raise NotImplementedError("per-image class labels on a canvas sharded over ranks (canvas_group)")
-        eng = self.model.engine(precision or self.precision)
+        plan, names = self._precision_plan(precision, precision_schedule, num_sample_steps, generation_start_steps)
+        engines = {name: self.model.engine(name) for name in names}
+        eng = engines[names[0]]             # of the first executed step: the start canvas and the region run's draws
 
         (left, top, right, bottom), pad = get_coord_and_pad(h, w)
         hp, wp = h + pad[2] + pad[3], w + pad[0] + pad[1]
@@ -817,10 +865,16 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
 
         cond01 = condition_x.to(dev, torch.float32).contiguous()
         cond_canvas = torch.empty(batch, 3, hp, wp, device=dev, dtype=torch.float32)
-        eng.sampler_begin(geo, cond01, cond_canvas, [(a, c_) for (a, _, c_, _) in coords0],
-                          [(a, c_) for (a, _, c_, _) in coords1], scalars, log_snrs, class_id)
-        if image_ids is not None:
-            eng.sampler_image_labels(image_ids)
+
+        def begin(e_, canvas):
+            e_.sampler_begin(geo, cond01, canvas, [(a, c_) for (a, _, c_, _) in coords0],
+                             [(a, c_) for (a, _, c_, _) in coords1], scalars, log_snrs, class_id)
+            if image_ids is not None:
+                e_.sampler_image_labels(image_ids)
+        # every precision of the plan: its engine begun with the same run and its own copy of the condition canvas
+        canvases = {name: cond_canvas if name == names[0] else torch.empty_like(cond_canvas) for name in names}
+        for name in names:
+            begin(engines[name], canvases[name])
 
         host_noise = self.noise_source == "host"
         if generation_start_steps > 0 or not start_white_noise:
@@ -858,10 +912,15 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
 
         sub_batch = self.max_tiles_per_launch or batch_size
         grids = (coords0, coords1)
-        lanes = None
+        lanes_of = {}                       # one StepLanes per precision, built on first need
+        eng_i = eng
         for i in range(num_sample_steps):
             if i < generation_start_steps:
                 continue
+            prec_i = plan[i]                # the step's precision: its engine and that engine's condition canvas
+            eng_i, cond_canvas = engines[prec_i], canvases[prec_i]
+            if precision_log is not None:
+                precision_log.append(prec_i)
             passes, kind, scale = _step_guidance(i, cond_scale, guidance_start_steps, class_cond_scale,
                                                  class_guidance_start_steps, joint)
             step_tiles = _launch_tiles(passes, sub_batch)
@@ -876,30 +935,28 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                 if i % 2 == 1:
                     noise_canvas = _host_randn(self.host_generator, 1, 3, hp, wp).to(dev, non_blocking=True)
             n_step = n_tiles * batch
-            n_lanes = lanes_wanted(n_step, passes, step_tiles, self.step_lanes, precision or self.precision) \
+            n_lanes = lanes_wanted(n_step, passes, step_tiles, self.step_lanes, prec_i) \
                 if self.canvas_group is None and regional is None else 1
             if regional is not None:        # the tiles that touch R, without the ring: it lies outside R and is replaced below
                 for first, count, ring in regional.step_ranges(i):
-                    _ddpm_step(eng, i, (first, count, ring), img, cond_canvas, x_start, noise_tiles, noise_canvas, passes, kind, scale,
+                    _ddpm_step(eng_i, i, (first, count, ring), img, cond_canvas, x_start, noise_tiles, noise_canvas, passes, kind, scale,
                                step_tiles, self.device_noise_seed)
             elif n_lanes > 1:
+                lanes = lanes_of.get(prec_i)
                 if lanes is None or len(lanes.engines) != n_lanes:   # further engines: same run geometry, own copies of the condition canvas
-                    more = [self.model.engine(precision or self.precision, lane=k) for k in range(1, n_lanes)]
+                    more = [self.model.engine(prec_i, lane=k) for k in range(1, n_lanes)]
                     for e_ in more:
-                        e_.sampler_begin(geo, cond01, torch.empty_like(cond_canvas), [(a, c_) for (a, _, c_, _) in coords0],
-                                         [(a, c_) for (a, _, c_, _) in coords1], scalars, log_snrs, class_id)
-                        if image_ids is not None:
-                            e_.sampler_image_labels(image_ids)
-                    lanes = StepLanes([eng] + more, dev)
+                        begin(e_, torch.empty_like(cond_canvas))
+                    lanes = lanes_of[prec_i] = StepLanes([eng_i] + more, dev)
                 lanes.run(n_step, lambda e_, first, count, ring: _ddpm_step(
                     e_, i, (first, count, ring), img, cond_canvas, x_start, noise_tiles, noise_canvas, passes, kind, scale, step_tiles,
                     self.device_noise_seed))
             elif self.canvas_group is None:
-                _ddpm_step(eng, i, None, img, cond_canvas, x_start, noise_tiles, noise_canvas, passes, kind, scale, step_tiles,
+                _ddpm_step(eng_i, i, None, img, cond_canvas, x_start, noise_tiles, noise_canvas, passes, kind, scale, step_tiles,
                            self.device_noise_seed)
             else:
                 from .parallel import sharded_step
-                sharded_step(eng, self.canvas_group, i, n_tiles * batch, img, cond_canvas, x_start, noise_tiles,
+                sharded_step(eng_i, self.canvas_group, i, n_tiles * batch, img, cond_canvas, x_start, noise_tiles,
                              noise_canvas, passes, kind, scale, sub_batch, self.device_noise_seed)
             if thresholded is not None:     # the lanes have joined the main stream: plain launches after the step's
                 thresholded.step(i, scalars, img, x_start)
@@ -915,7 +972,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                 x0_image_list.append(x_start.clone().cpu())
 
         out = torch.empty(batch, 3, h, w, device=dev, dtype=torch.float32)
-        eng.sampler_end(img, out)
+        eng_i.sampler_end(img, out)         # the engine of the last executed step
         if thresholded is not None and threshold_log is not None:
             threshold_log.append(thresholded.log())
         if color_fix is not None:           # in place on the [B,3,H,W] result; the trajectories above stay raw
@@ -937,7 +994,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                              class_cond_scale, class_guidance_start_steps, generation_start_steps, num_sample_steps,
                              start_white_noise, precision, seeds=None, color_fix=None, reference=None, crop_border=4,
                              back_project=None, guidance=None, solver=None, threshold=None, threshold_log=None, joint=False,
-                             region=None, region_skip_tiles=True, region_log=None):
+                             region=None, region_skip_tiles=True, region_log=None, precision_schedule=None, precision_log=None):
         """Mixed-size lock-step (srgd_sampler_begin_images): every image keeps its own canvas, crop box, padding, inner box and
         tile grids; a step's tiles of all images share the U-Net launches.  Noise: the images of one noise class (canvas size)
         see the draw sequence a run of one of them alone sees.  Host noise: the generator state is taken once at entry and
@@ -967,7 +1024,12 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
 
         ``region``: None, or ``check_region_args``'s list of one ``None`` / ``(known image, boxes)`` per image (validated by the
         caller): the run's ``_RegionRun`` plans the tile ranges of every step over all images - an image without a known image keeps
-        all its tiles - and makes the replacement step after the history call; lanes are off."""
+        all its tiles - and makes the replacement step after the history call; lanes are off.
+
+        ``precision_schedule``: None, or the parsed schedule of the call (validated by the caller; without it and without
+        ``precision`` the wrapper's attribute holds): every precision with an executed step has its engine begun with the run and
+        its own condition canvas, and step i runs on the engine of its precision; ``precision_log`` (a list or None) receives the
+        precision of every executed step."""
         from .lockstep import plan_mixed_group
         dev = self.device
         if dev.type != "cuda":
@@ -983,9 +1045,10 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
             plans, classes = plan_mixed_group(sizes, tile_size)
         else:
             plans, classes, class_seeds = plan_mixed_group(sizes, tile_size, seeds=seeds)
-        prec = precision or self.precision
+        plan, names = self._precision_plan(precision, precision_schedule, num_sample_steps, generation_start_steps)
         class_id, image_ids = _run_labels(_image_class_ids(class_label, len(conds)))
-        eng = self.model.engine(prec)
+        engines = {name: self.model.engine(name) for name in names}
+        eng = engines[names[0]]             # of the first executed step: the start canvas and the region run's draws
         images = [_lib.SamplerImage(H=p.H, W=p.W, Hp=p.Hp, Wp=p.Wp, left=p.box[0], top=p.box[1], inner_l=p.inner[0],
                                     inner_t=p.inner[1], inner_r=p.inner[2], inner_b=p.inner[3], n_even=len(p.coords0),
                                     n_odd=len(p.coords1), noise_class=p.noise_class) for p in plans]
@@ -1004,7 +1067,10 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                 e_.sampler_image_labels(image_ids)
             if class_seeds is not None and not host_noise:   # host noise arrives drawn: the engine makes no draw of its own
                 e_.sampler_noise_seeds(class_seeds)
-        begin(eng, cond_canvas)
+        # every precision of the plan: its engine begun with the same run and its own copy of the condition canvas
+        canvases = {name: cond_canvas if name == names[0] else torch.empty_like(cond_canvas) for name in names}
+        for name in names:
+            begin(engines[name], canvases[name])
 
         first_of_class = [next(p for p in plans if p.noise_class == k) for k in range(len(classes))]
         if host_noise:
@@ -1074,10 +1140,15 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
 
         sub_batch = self.max_tiles_per_launch or batch_size
         n_grid = (len(tiles_even), len(tiles_odd))
-        lanes = None
+        lanes_of = {}                       # one StepLanes per precision, built on first need
+        eng_i = eng
         for i in range(num_sample_steps):
             if i < generation_start_steps:
                 continue
+            prec_i = plan[i]                # the step's precision: its engine and that engine's condition canvas
+            eng_i, cond_canvas = engines[prec_i], canvases[prec_i]
+            if precision_log is not None:
+                precision_log.append(prec_i)
             passes, kind, scale = _step_guidance(i, cond_scale, guidance_start_steps, class_cond_scale,
                                                  class_guidance_start_steps, joint)
             step_tiles = _launch_tiles(passes, sub_batch)
@@ -1090,22 +1161,23 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                 if i % 2 == 1:
                     noise_canvas = canvas_draw()
             n_step = n_grid[i % 2]
-            n_lanes = lanes_wanted(n_step, passes, step_tiles, self.step_lanes, prec) if regional is None else 1
+            n_lanes = lanes_wanted(n_step, passes, step_tiles, self.step_lanes, prec_i) if regional is None else 1
             if regional is not None:        # the tiles that touch R (all tiles of an image sampled whole)
                 for first, count, ring in regional.step_ranges(i):
-                    _ddpm_step(eng, i, (first, count, ring), img, cond_canvas, x_start, noise_tiles, noise_canvas, passes, kind, scale,
+                    _ddpm_step(eng_i, i, (first, count, ring), img, cond_canvas, x_start, noise_tiles, noise_canvas, passes, kind, scale,
                                step_tiles, self.device_noise_seed)
             elif n_lanes > 1:
+                lanes = lanes_of.get(prec_i)
                 if lanes is None or len(lanes.engines) != n_lanes:   # further engines: the same mixed run, own condition canvas
-                    more = [self.model.engine(prec, lane=k) for k in range(1, n_lanes)]
+                    more = [self.model.engine(prec_i, lane=k) for k in range(1, n_lanes)]
                     for e_ in more:
                         begin(e_, torch.empty_like(cond_canvas))
-                    lanes = StepLanes([eng] + more, dev)
+                    lanes = lanes_of[prec_i] = StepLanes([eng_i] + more, dev)
                 lanes.run(n_step, lambda e_, first, count, ring: _ddpm_step(
                     e_, i, (first, count, ring), img, cond_canvas, x_start, noise_tiles, noise_canvas, passes, kind, scale, step_tiles,
                     self.device_noise_seed))
             else:
-                _ddpm_step(eng, i, None, img, cond_canvas, x_start, noise_tiles, noise_canvas, passes, kind, scale, step_tiles,
+                _ddpm_step(eng_i, i, None, img, cond_canvas, x_start, noise_tiles, noise_canvas, passes, kind, scale, step_tiles,
                            self.device_noise_seed)
             if thresholded is not None:
                 thresholded.step(i, scalars, img, x_start)
@@ -1117,7 +1189,7 @@ class ConditionalContinuousTimeGaussianDiffusionSR(nn.Module):
                 regional.after_step(i, scalars, img, x_start)
 
         out = torch.empty(sum(3 * p.H * p.W for p in plans), device=dev, dtype=torch.float32)
-        eng.sampler_end(img, out)
+        eng_i.sampler_end(img, out)         # the engine of the last executed step
         if thresholded is not None and threshold_log is not None:
             threshold_log.append(thresholded.log())
         starts = [0]
@@ -1334,7 +1406,8 @@ class ConditionalElucidatedDiffusionSR(nn.Module):
                      with_x0_images=False, start_white_noise=True, amp=False, precision=None, seeds=None, color_fix=None,
                      reference=None, crop_border=4, back_project=0, consistency_guidance=0.0, consistency_guidance_start_steps=0,
                      sampler="ddpm", eta=None, step_spacing="time", dynamic_threshold=None, threshold_log=None,
-                     joint_guidance=False, region_known=None, regions=None, region_skip_tiles=True, region_log=None):
+                     joint_guidance=False, region_known=None, regions=None, region_skip_tiles=True, region_log=None,
+                     precision_schedule=None, precision_log=None):
         """Reference model.py:2309-2475 (``start_white_noise`` and ``amp`` are accepted and unused there too; ``precision``
         is the engine-only override of ``self.precision``).  ``seeds`` (per-image noise seeds) is a DDPM-sampler feature and is
         refused here.  ``color_fix``: as in the DDPM wrapper's ``tiled_sample`` - the final image of every image of the batch
@@ -1345,7 +1418,10 @@ class ConditionalElucidatedDiffusionSR(nn.Module):
         ``sampler``, ``eta``, ``step_spacing``: the DDPM wrapper's few-step samplers; any non-default value is refused here.
         ``dynamic_threshold``: a DDPM-sampler feature; a percentile other than None / 0 is refused here.
         ``joint_guidance``: a DDPM-sampler feature; both scales are refused here with or without it.
-        ``region_known`` / ``regions``: region resampling is a DDPM-sampler feature and is refused here."""
+        ``region_known`` / ``regions``: region resampling is a DDPM-sampler feature and is refused here.
+        ``precision_schedule`` / ``precision_log``: a precision per step is a DDPM-sampler feature and is refused here."""
+        if precision_schedule is not None or precision_log is not None:
+            raise NotImplementedError("precision_schedule is built for the DDPM sampler only: the EDM loop begins one engine per run")
         if region_known is not None or regions is not None:
             raise NotImplementedError("region_known / regions are built for the DDPM sampler only: the known image is forward-diffused "
                                       "with the DDPM schedule's (alpha, sigma) after every step")
